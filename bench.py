@@ -53,6 +53,44 @@ def algorithmic_bytes(label, images, hw, C=256, taps=9, nets=1):
             "rb_wgrad": 2 * act + 2 * w}.get(label)
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6        # --dump-outputs: all files together, .npy headers included
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(model, out_dir, seed=0):
+    """--dump-outputs: what a caller of the timed step holds after its last iteration — the recipe's visuals, losses and
+    metrics (BaseGAN.get_loggable_data) — as out_dir/{visual,loss,metric}_<name>.npy, float64 tensors as float64 and every
+    other one as float32. A tensor that does not fit its share of DUMP_LIMIT_BYTES (equal shares, what the smaller ones leave
+    going to the larger) is written as the flat sample x.flatten()[idx], idx = sorted draws of torch.randint(numel) from a
+    Generator seeded with `seed`: the same elements for the same shapes in every run.
+    -> {file name: [shape written, shape of the tensor]}"""
+    import numpy as np
+    import torch
+    arrays = {}
+    for kind, group in (("visual", model.visuals), ("loss", model.losses), ("metric", model.metrics)):
+        for name, v in group.items():
+            if v is None:
+                continue
+            t = v.detach() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+            arrays[f"{kind}_{name}"] = t if t.dtype == torch.float64 else t.float()
+    left, share = DUMP_LIMIT_BYTES - NPY_HEADER_BYTES * len(arrays), {}
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size())):
+        share[name] = min(t.numel(), left // (len(arrays) - i) // t.element_size())
+        left -= share[name] * t.element_size()
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        full_shape = list(t.shape)
+        if share[name] < t.numel():
+            g = torch.Generator().manual_seed(seed)
+            idx = torch.randint(t.numel(), (share[name],), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[f"{name}.npy"] = [list(a.shape), full_shape]
+    return written
+
+
 def make_pix2pix_conf(batch, n_iters):
     """BASELINE configs[2]: cityscapes_label2photo pix2pix.yaml:25-48 — Unet2D(num_downs 7, ngf 128, dropout) +
     PatchGAN2D(n_layers 4, 6 ch), 256x512 (a parity-test workload, measured with --workload pix2pix)"""
@@ -324,7 +362,13 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short timed runs of the other BASELINE configs attached to the headline line as `secondary`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (visuals, losses, metrics) as "
+                         "DIR/<kind>_<name>.npy, at most 64 MB in all (see dump_outputs); inputs and weights are seeded, "
+                         "so two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # a timed kernel must never be one that was told to skip work: the ablation switches of round 1 are compiled out
     # of the library; refuse to run if somebody still sets them, or any other kernel "variant" selector
@@ -372,7 +416,9 @@ def main():
         dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29571", rank=0, world_size=1)
     dev = torch.device(f"cuda:{local_rank}")
 
-    torch.manual_seed(0)
+    # torch (weights, device draws), numpy and python's random (image-pool coin flips, dropout seeds, CUT's flips)
+    from ganslate_amd.utils.environment import set_seed
+    set_seed(0)
     g = torch.Generator().manual_seed(1234 + rank)
     if args.workload == "pix2pix":
         args.no_cpu_baseline = args.no_kernel_timing = True
@@ -450,6 +496,11 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before the kernel-timing steps below: they run the step again, launch by launch, over the same buffers
+        written = dump_outputs(model, args.dump_outputs)
+        print(f"bench.py: {len(written)} outputs of step {args.warmup + args.steps} written to {args.dump_outputs}: "
+              f"{json.dumps(written)}", file=sys.stderr)
 
     ops = next(iter(model.networks.values())).ops
     graphed = bool(getattr(model, "_graph", None) is not None and model.step_graph_enabled)

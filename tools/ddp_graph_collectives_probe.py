@@ -1,5 +1,6 @@
 import os, sys, random, datetime
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch, torch.distributed as dist
 from tests.helpers import build_product_cyclegan, load_golden_steps, golden_inputs
 from tests.test_step_graph_gpu import _run
