@@ -71,20 +71,13 @@ OptDef g_opts[GS_OPT_COUNT] = {
     {"hstrip_regs", 1},         // hstrip.hip: persistent form with the weights in registers for the k7 boundary convs (0: one tile per workgroup)
     {"gconv_twin", 1},          // gconv.hip: twin batches on the im2col kernel as one launch (0: the two halves as two launches)
     {"wgrad_twin", 1},          // wgrad.hip: twin batches on the im2col weight-gradient kernel as one launch (0: two launches)
-    {"gconv_smallk", 0},        // gconv.hip: layers with at most this many K-steps take 128 x 128 tiles on 8 waves (two workgroups per
-                                // CU overlap each other's prologue / epilogue) instead of one 256 x 128 tile per CU; 0 = off
     {"gconv_persist", 16},      // pconv.hip: 256 x 128 im2col launches with more tiles than CUs and at most this many K-steps run as
                                 // persistent workgroups (the K-step stream continues across tiles); 0 = off
     {"hconvt_persist", 1},      // hconvt.hip: launches with more tiles than CUs run as persistent workgroups (0: one tile each)
-    {"ring_apply", 0},          // hconvw.hip: gs_gconv_ring_apply is offered (the consumer's norm backward inside the fused data gradient).
-                                // OFF: the in-launch rendezvous costs more than the launch it saves (profiles/r05_ring_apply.txt);
-                                // bits 2 / 4 / 8 / 16 are timing ablations (wrong results)
-    {"norm_xcd", 0},            // norm.hip: the channel-group norm kernels take image n on XCD n % 8 (1: last image first, 2: in order)
     {"wgrad_rows", 1},          // wgrad.hip: the im2col weight gradient stores whole tile rows through LDS; one split adds without atomics
     {"splitk_multi", 1},        // gconv.hip: split-K over the merged parity classes of a small stride-2 layer (one launch + one finalize)
     {"splitk_ring", 1},         // gconv.hip: split-K launches of the 128 x 128 tile run a 4-stage ring (three K-steps of cold weights in flight)
     {"gconv_ring4", 16},        // gconv.hip: 128-pixel im2col tiles in a grid of <= 2 workgroups per CU with at least this many K-steps run a 4-stage ring; 0 = off
-    {"ring_dbg", 0},            // hconvw.hip RING: timing ablations (wrong results): 1 no ring MFMAs, 2 no y / g2 loads, 4 no sums, 8 no ring adds
     {"hconv5", 64},             // hconv5.hip: register-resident-weights kernel for the 16 -> 16 channel k5 volume convs; smallest volume
                                 // (batch x voxels / 2048) it takes (0 = off)
     {"hconv5_seg", 0},          // ... z segments per column (0 = as many as fill the chip; tests force long segments with 1 / 2)
@@ -94,8 +87,6 @@ OptDef g_opts[GS_OPT_COUNT] = {
                                 // >= 2: also 64 -> 64 channels — wide on both sides — instead of the split-K im2col launch + its finalize;
                                 // >= 3: 32-channel layers on <= 128 boxes as two 16-channel groups per box; >= 4: 64-channel layers on <= 64 boxes as four)
     {"pwise", 8},               // pwise.hip: register-operand kernels for one-tap layers with <= 8 channels on one side (smallest volume in 2048-voxel units, 0 = off)
-    {"adam_blocks", 8192},      // optim.hip: largest grid of the Adam update (the chunks launched under a backward pass take fewer: they
-                                // must not crowd the pass's own launches out of the CUs)
 };
 }  // namespace
 int gs_opt(int id) { return g_opts[id].value; }

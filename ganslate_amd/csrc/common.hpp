@@ -143,9 +143,7 @@ __device__ __forceinline__ float act_grad_from_out(float o, int act, float slope
 }
 
 // dy of the InstanceNorm backward, dy = rstd * (ghat - mean ghat - yhat * mean(ghat * yhat)) with ghat = g * act'(yhat), from the
-// pieces both of its homes hold — norm.hip's apply pass by channel group and hconvw.hip's in-launch apply (gs_gconv_ring_apply)
-// — with explicit roundings: left to the compiler the two sites contract it differently (an fma here, a select there), and the
-// one-launch form must reproduce the two-launch form bit for bit
+// pieces norm.hip's apply pass by channel group holds — with explicit roundings, so that no fma contraction decides the bits
 __device__ __forceinline__ float inorm_dy(float g, float yh, float m, float s1, float s2, float rs) {
   const float gh = __fmul_rn(g, m);
   return __fmul_rn(rs, __fsub_rn(__fsub_rn(gh, s1), __fmul_rn(yh, s2)));
@@ -197,7 +195,7 @@ __device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v,
 enum GsOpt {
   GS_OPT_SPLITK, GS_OPT_SPLITK_MAX_BLOCKS, GS_OPT_SPLITK_TARGET, GS_OPT_HCONV, GS_OPT_HCONV_WIDE,
   GS_OPT_HWGRAD, GS_OPT_HWGRAD_WIDE, GS_OPT_HWGRAD_PLANES, GS_OPT_NORM_BWD_PPB, GS_OPT_NORM_APPLY_UNROLL,
-  GS_OPT_GCONV_TILE288, GS_OPT_GCONV_MULTI, GS_OPT_HCONVW_RING, GS_OPT_HCONVT, GS_OPT_HSTRIP, GS_OPT_WFOLD_ROWS, GS_OPT_HWGRAD_FT, GS_OPT_GCONV_BIG, GS_OPT_HCONV_BOX8, GS_OPT_HCONVW_PERSIST, GS_OPT_HSTRIP_REGS, GS_OPT_GCONV_TWIN, GS_OPT_WGRAD_TWIN, GS_OPT_GCONV_SMALLK, GS_OPT_GCONV_PERSIST, GS_OPT_HCONVT_PERSIST, GS_OPT_RING_APPLY, GS_OPT_NORM_XCD, GS_OPT_WGRAD_ROWS, GS_OPT_SPLITK_MULTI, GS_OPT_SPLITK_RING, GS_OPT_GCONV_RING4, GS_OPT_RING_DBG, GS_OPT_HCONV5, GS_OPT_HCONV5_SEG, GS_OPT_HWGRAD2, GS_OPT_HCONV2, GS_OPT_PWISE, GS_OPT_ADAM_BLOCKS,
+  GS_OPT_GCONV_TILE288, GS_OPT_GCONV_MULTI, GS_OPT_HCONVW_RING, GS_OPT_HCONVT, GS_OPT_HSTRIP, GS_OPT_WFOLD_ROWS, GS_OPT_HWGRAD_FT, GS_OPT_GCONV_BIG, GS_OPT_HCONV_BOX8, GS_OPT_HCONVW_PERSIST, GS_OPT_HSTRIP_REGS, GS_OPT_GCONV_TWIN, GS_OPT_WGRAD_TWIN, GS_OPT_GCONV_PERSIST, GS_OPT_HCONVT_PERSIST, GS_OPT_WGRAD_ROWS, GS_OPT_SPLITK_MULTI, GS_OPT_SPLITK_RING, GS_OPT_GCONV_RING4, GS_OPT_HCONV5, GS_OPT_HCONV5_SEG, GS_OPT_HWGRAD2, GS_OPT_HCONV2, GS_OPT_PWISE,
   GS_OPT_COUNT
 };
 int gs_opt(int id);

@@ -578,14 +578,10 @@ __global__ __launch_bounds__(256) void gconv_splitk_finalize_kernel(const SplitF
 
 // ---- host side ------------------------------------------------------------------------------------
 namespace {
-struct TileCfg { int bm, bn; int waves = 16; };
+struct TileCfg { int bm, bn; };
 TileCfg pick_tile(const gs_gconv_desc* d) {
   if (d->Co <= 16) return {256, 16};
   if (d->Co <= 64) return {128, 64};
-  // few K-steps: a tile's fixed cost (tables, ring fill, epilogue) is most of its time, and one 150-KB workgroup per CU pays it
-  // in series. 128 x 128 tiles on 8 waves need 64 KB and <= 128 registers: two workgroups per CU, one's loop under the other's
-  // prologue / epilogue (the 16-wave 128 x 128 tile holds 96 registers per lane: one workgroup per CU whatever its LDS)
-  if ((d->Kp >> 6) <= gs_opt(GS_OPT_GCONV_SMALLK)) return {128, 128, 8};
   // big tile (8 waves, 3 stages, 1 workgroup per CU) once it still fills the chip; else the 4-wave 128x128 tile
   const long long pix = (long long)d->Dc * d->Hc * d->Wc;
   const long long big = (long long)d->N * ((pix + 255) / 256) * ((d->Co + 127) / 128);
@@ -644,7 +640,6 @@ int launch_tile(const TileCfg& tc, const GConvK& k, int blocks, hipStream_t st) 
   for (int c = 0; c < k.n_cls; ++c) nk = std::min(nk, k.cls[c].Kp >> 6);
   const bool ring4 = gs_opt(GS_OPT_GCONV_RING4) != 0 && blocks <= 2 * 256 && nk >= gs_opt(GS_OPT_GCONV_RING4);
   if (tc.bn == 64) return ring4 ? launch<128, 64, 4, 2, 4>(k, blocks, st) : launch<128, 64, 4, 2, 2>(k, blocks, st);
-  if (tc.bm == 128 && tc.waves == 8) return launch<128, 128, 2, 4, 2>(k, blocks, st);
   if (tc.bm == 128) return ring4 ? launch<128, 128, 4, 4, 4>(k, blocks, st) : launch<128, 128, 4, 4, 2>(k, blocks, st);
   if (tc.bm == 320) return launch<320, 128, 5, 2, 2>(k, blocks, st);
   if (tc.bm == 288) return launch<288, 128, 6, 2, 2>(k, blocks, st);

@@ -63,11 +63,7 @@ __device__ __forceinline__ void mfma_v(f32x4& acc, const bf16x8& a, const bf16x8
 }
 template <int U>
 __device__ __forceinline__ void mfma_u(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-#ifdef HCONV5_BUILTIN
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-#else
   if constexpr (U < A_IN_AGPR) mfma_a(acc, a, b); else mfma_v(acc, a, b);
-#endif
 }
 
 template <int... I, class F>

@@ -356,9 +356,14 @@ int gs_pwise_multi_try(const gs_gconv_desc* const* descs, int count, const void*
   k.Ci = d->Ci; k.Co = d->Co; k.in_cs = d->in_cs; k.in_co = d->in_co; k.out_cs = d->out_cs; k.out_co = d->out_co;
   k.Kp = d->Kp; k.w_rows = d->w_rows; k.act = d->act; k.slope = d->slope;
   k.rcp_wc = 1.0f / (float)d->Wc; k.rcp_hc = 1.0f / (float)d->Hc;
-  k.bm = d->Co <= 16 ? 256 : 128;                    // gconv.hip pick_tile: one statistics slot per pixel tile and class
+  k.bm = gs_tile_m(d);                               // the im2col kernel's pixel tile: one statistics slot per tile and class
   k.tiles_m = (int)((pix + k.bm - 1) / k.bm);
   k.stats_slots = d->stats_slots;
+  if (k.stats_slots > 0)
+    for (int c = 0; c < 8; ++c)
+      GS_REQUIRE(k.cslot0[c] + k.tiles_m <= k.stats_slots,
+                 "gs_gconv_forward_multi: class %d writes statistics slots %d..%d of %d", c, k.cslot0[c],
+                 k.cslot0[c] + k.tiles_m - 1, k.stats_slots);
   const long long blocks = (long long)d->N * k.tiles_m;
   if (blocks >= (1LL << 31)) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -38,7 +38,8 @@ class HipOps(TwinSplit):
             raise RuntimeError("HipOps needs an MI355X (torch.cuda.is_available() is False); there is no CPU path")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         L.check(self.lib.gs_init(self.device.index or 0), "gs_init")
-        self._desc_cache = {}
+        self._desc_cache = {}        # descriptors: built from the layer spec alone, valid whatever the options
+        self._plans = {}             # answers of the library's planning queries: depend on the options (set_option clears them)
         self._timing_filter, self._timing_events, self._timing_images = None, {}, {}
         self.sync_options()
 
@@ -46,17 +47,16 @@ class HipOps(TwinSplit):
     # The library reads no environment variable (gs_set_option, include/ganslate_hip.h); the GS_* variables of the
     # host side are mapped onto its options here, when the backend is created and whenever a model is built.
     ENV_OPTIONS = {"GS_SPLITK": "splitk", "GS_SPLITK_MAXB": "splitk_max_blocks", "GS_SPLITK_TARGET": "splitk_target",
-                   "GS_HCONV": "hconv", "GS_HCONV_WIDE": "hconv_wide", "GS_HCONVW_PERSIST": "hconvw_persist", "GS_HSTRIP_REGS": "hstrip_regs", "GS_GCONV_TWIN": "gconv_twin", "GS_GCONV_SMALLK": "gconv_smallk", "GS_GCONV_PERSIST": "gconv_persist", "GS_HCONVT_PERSIST": "hconvt_persist", "GS_RING_APPLY": "ring_apply", "GS_NORM_XCD": "norm_xcd", "GS_WGRAD_ROWS": "wgrad_rows", "GS_SPLITK_MULTI": "splitk_multi", "GS_SPLITK_RING": "splitk_ring", "GS_GCONV_RING4": "gconv_ring4", "GS_WGRAD_TWIN": "wgrad_twin",
+                   "GS_HCONV": "hconv", "GS_HCONV_WIDE": "hconv_wide", "GS_HCONVW_PERSIST": "hconvw_persist", "GS_HSTRIP_REGS": "hstrip_regs", "GS_GCONV_TWIN": "gconv_twin", "GS_GCONV_PERSIST": "gconv_persist", "GS_HCONVT_PERSIST": "hconvt_persist", "GS_WGRAD_ROWS": "wgrad_rows", "GS_SPLITK_MULTI": "splitk_multi", "GS_SPLITK_RING": "splitk_ring", "GS_GCONV_RING4": "gconv_ring4", "GS_WGRAD_TWIN": "wgrad_twin",
                    "GS_HWGRAD": "hwgrad", "GS_HWGRAD_WIDE": "hwgrad_wide", "GS_HWGRAD_PLANES": "hwgrad_planes",
                    "GS_BWD_PPB": "norm_bwd_ppb", "GS_APPLY_U": "norm_apply_unroll", "GS_GCONV_TILE288": "gconv_tile288", "GS_GCONV_MULTI": "gconv_multi",
                    "GS_HCONVW_RING": "hconvw_ring", "GS_HCONVT": "hconvt", "GS_HSTRIP": "hstrip",
                    "GS_WFOLD_ROWS": "wfold_rows", "GS_HWGRAD_FT": "hwgrad_ft", "GS_GCONV_BIG": "gconv_big", "GS_HCONV_BOX8": "hconv_box8",
-                   "GS_HCONV5": "hconv5", "GS_RING_DBG": "ring_dbg", "GS_HWGRAD2": "hwgrad2", "GS_HCONV2": "hconv2", "GS_PWISE": "pwise"}
+                   "GS_HCONV5": "hconv5", "GS_HWGRAD2": "hwgrad2", "GS_HCONV2": "hconv2", "GS_PWISE": "pwise"}
 
     def set_option(self, name, value):
         L.check(self.lib.gs_set_option(name.encode(), int(value)), "gs_set_option")
-        self._desc_cache = {k: v for k, v in self._desc_cache.items()
-                            if not (isinstance(k, tuple) and k[0] in ("splitk", "wgrad_ws", "multi"))}
+        self._plans.clear()
 
     def get_option(self, name):
         v = C.c_int(0)
@@ -133,10 +133,10 @@ class HipOps(TwinSplit):
     def _splitk_floats(self, d) -> int:
         """workspace floats the split-K form of this launch wants (0: no split); cached per descriptor"""
         key = ("splitk", id(d))
-        n = self._desc_cache.get(key)
+        n = self._plans.get(key)
         if n is None:
             n = int(self.lib.gs_gconv_splitk_ws_floats(C.byref(d)))
-            self._desc_cache[key] = n
+            self._plans[key] = n
         return n
 
     def _cout1(self, d) -> bool:
@@ -144,10 +144,10 @@ class HipOps(TwinSplit):
         if os.environ.get("GS_COUT1", "1") == "0":
             return False
         key = ("cout1", id(d))
-        v = self._desc_cache.get(key)
+        v = self._plans.get(key)
         if v is None:
             v = bool(self.lib.gs_conv_cout1_eligible(C.byref(d)))
-            self._desc_cache[key] = v
+            self._plans[key] = v
         return v
 
     def tile_m(self, g: GConv, N: int) -> int:
@@ -237,45 +237,6 @@ class HipOps(TwinSplit):
             return None
         return slots, torch.empty(N * (slots + 1) * 3 * C_, dtype=torch.float32, device=self.device)
 
-    def ring_apply_plan(self, g: GConv, N: int, C_: int, twin: bool = False):
-        """the rendezvous buffer (zero int32 words, one per launching stream, left zero by every launch) when the ring-form
-        launch of class g can also carry the consumer's whole InstanceNorm backward (gs_gconv_ring_apply: dy and the total
-        gradient come out of the data-gradient launch, no gs_inorm_act_backward behind it), else None. Twin batches only
-        where the launch is one launch. GS_RING_APPLY=0 switches it off."""
-        if g is None or g.Co != C_:
-            return None
-        if twin and not self.twin_native(g, N, ring=True):
-            return None
-        words = self.lib.gs_gconv_ring_apply_words(C.byref(self._gdesc(g, N, g.Ci, 0, g.Co, 0, "none", 0.0, 0, 0)))
-        if words <= 0:
-            return None
-        if not hasattr(self, "_ring_sync"):
-            self._ring_sync = {}
-        key = int(_stream().value or 0)                        # one buffer per launching stream
-        buf = self._ring_sync.get(key)
-        if buf is None or buf.numel() < words:
-            buf = torch.zeros(max(words, 4096), dtype=torch.int32, device=self.device)
-            self._ring_sync[key] = buf
-        return buf
-
-    def gconv_ring_apply(self, g: GConv, x, wpack, dy, total, fuse, sync):
-        """the ring-form fused data gradient with the norm backward applied in the launch: writes dy (and total = gx + g2)"""
-        N = x.shape[0]
-        d = self._gdesc(g, N, x.shape[-1], 0, dy.shape[-1], 0, "none", 0.0, 0, 0, False)
-        f = self._fuse_struct(fuse)
-        tw = None
-        if isinstance(wpack, Twin):
-            tw = L.Twin()
-            tw.n_split, tw.w_delta, tw.bias_delta = N // 2, wpack.delta(), 0
-            w = C.c_void_p(wpack.a.data_ptr() + 2 * g.pack_offset)
-        else:
-            w = C.c_void_p(wpack.data_ptr() + 2 * g.pack_offset)
-        t_end = self._time_begin("gconv", g, True, N)
-        L.check(self.lib.gs_gconv_ring_apply(C.byref(d), _ptr(x), w, C.byref(f), _ptr(dy), _ptr(total), _ptr(sync),
-                                             C.byref(tw) if tw is not None else None, _stream()), "gs_gconv_ring_apply")
-        if t_end is not None:
-            t_end.record()
-
     def multi_twin_native(self, classes, N: int) -> bool:
         """a twin batch of N images over the output-parity classes of one layer runs as ONE launch (the halo-resident class
         kernel picks the packs per box, gs_gconv_multi_twin_native) — else as two launches of N / 2"""
@@ -283,11 +244,11 @@ class HipOps(TwinSplit):
             return False
         g = classes[0]
         key = ("multi_twin", tuple(id(c) for c in classes), N)
-        v = self._desc_cache.get(key)
+        v = self._plans.get(key)
         if v is None:
             arr, _ = self._multi_descs(classes, N, g.Ci, g.Co)
             v = bool(self.lib.gs_gconv_multi_twin_native(arr, len(classes)))
-            self._desc_cache[key] = v
+            self._plans[key] = v
         return v
 
     def stat_slots(self, g: GConv, N: int, twin: bool = False, multi=None) -> int:
@@ -418,16 +379,20 @@ class HipOps(TwinSplit):
             if ent is None:
                 descs = [self._gdesc(g, N, x.shape[-1], in_co, out.shape[-1], out_co, act, float(slope), stats_slots,
                                      slot0(i)) for i, g in enumerate(classes)]
+                arr = (C.POINTER(L.GConvDesc) * len(descs))(*[C.pointer(d) for d in descs])
+                ent = (arr, descs)
+                self._desc_cache[key] = ent
+            plan = self._plans.get(key)
+            if plan is None:
+                arr, descs = ent
                 tn = 16 if g0.Co <= 16 else (64 if g0.Co <= 64 else 128)
                 tm = self.tile_m(g0, N)
                 blocks = len(classes) * N * ((g0.pixels + tm - 1) // tm) * ((g0.Co + tn - 1) // tn)
                 use = blocks >= 128 or not any(self._splitk_floats(d) for d in descs)
-                arr = (C.POINTER(L.GConvDesc) * len(descs))(*[C.pointer(d) for d in descs])
                 # a merged grid that still leaves the chip empty: split K over it (one launch + one finalize for all classes)
                 nws = 0 if use else int(self.lib.gs_gconv_multi_splitk_ws_floats(arr, len(descs)))
-                ent = (arr, descs, use or nws > 0, nws)
-                self._desc_cache[key] = ent
-            merged = ent[2]
+                plan = self._plans[key] = (use or nws > 0, nws)
+            merged = plan[0]
         if not merged:
             for i, g in enumerate(classes):
                 self.gconv(g, x, wpack, bias, out, in_co=in_co, out_co=out_co, act=act, slope=slope, stats=stats,
@@ -436,10 +401,11 @@ class HipOps(TwinSplit):
         base = wpack.data_ptr()
         ws = (C.c_void_p * len(classes))(*[base + 2 * g.pack_offset for g in classes])
         t_end = self._time_begin("gconv_multi", classes, False, N)
-        if ent[3]:
-            part = torch.empty(ent[3], dtype=torch.float32, device=self.device)
+        nws = plan[1]
+        if nws:
+            part = torch.empty(nws, dtype=torch.float32, device=self.device)
             L.check(self.lib.gs_gconv_forward_multi_ws(ent[0], len(classes), _ptr(x), ws, _ptr(bias), _ptr(out), _ptr(stats),
-                                                       _ptr(part), ent[3], _stream()), "gs_gconv_forward_multi_ws")
+                                                       _ptr(part), nws, _stream()), "gs_gconv_forward_multi_ws")
         else:
             L.check(self.lib.gs_gconv_forward_multi(ent[0], len(classes), _ptr(x), ws, _ptr(bias), _ptr(out), _ptr(stats),
                                                     _stream()), "gs_gconv_forward_multi")
@@ -479,11 +445,11 @@ class HipOps(TwinSplit):
         key = ("wadam", id(w), a.shape[0], a.shape[-1], g.shape[-1])
         ent = self._desc_cache.get(key)
         if ent is None:
-            d = self._wdesc(w, a.shape[0], a.shape[-1], 0, g.shape[-1], 0)
-            ok = bool(self.lib.gs_wgrad_adam_eligible(C.byref(d))) and getattr(w, "p_real", 0) != 1
-            ent = (d, ok, w)
-            self._desc_cache[key] = ent
-        if not ent[1]:
+            ent = self._desc_cache[key] = (self._wdesc(w, a.shape[0], a.shape[-1], 0, g.shape[-1], 0), w)
+        ok = self._plans.get(key)
+        if ok is None:
+            ok = self._plans[key] = bool(self.lib.gs_wgrad_adam_eligible(C.byref(ent[0]))) and getattr(w, "p_real", 0) != 1
+        if not ok:
             return False
         ad = L.AdamFuse()
         ad.p, ad.m, ad.v, ad.hyper = p.data_ptr(), m.data_ptr(), v.data_ptr(), hyper_dev.data_ptr()
@@ -512,25 +478,16 @@ class HipOps(TwinSplit):
         key = ("w", id(w), a.shape[0], a_cs, a_co, g_cs, g_co, fresh)
         ent = self._desc_cache.get(key)
         if ent is None:
-            d = L.WGradDesc()
-            d.dw_fresh = int(fresh)
-            d.N, d.Ha, d.Wa, d.P = a.shape[0], w.Ha, w.Wa, w.P
-            d.Da, d.Dg = w.Da, w.Dg
-            d.a_cs, d.a_co = (a_cs if a_cs is not None else a.shape[-1]), a_co
-            d.Hg, d.Wg, d.Q = w.Hg, w.Wg, w.Q
-            d.g_cs, d.g_co = (g_cs if g_cs is not None else g.shape[-1]), g_co
-            d.si, d.T, d.border, d.dw_ld = w.si, w.T, L.BORDER[w.border], w.T * w.Q
-            for i, (p, q, r) in enumerate(zip(w.dh, w.dw, w.dd)):
-                d.dh[i], d.dw_[i], d.dd[i] = p, q, r
-            ent = (d, w)
-            self._desc_cache[key] = ent
+            d = self._wdesc(w, a.shape[0], a_cs if a_cs is not None else a.shape[-1], a_co,
+                            g_cs if g_cs is not None else g.shape[-1], g_co, fresh)
+            ent = self._desc_cache[key] = (d, w)
         if getattr(w, "p_real", 0) == 1 and os.environ.get("GS_COUT1", "1") != "0" and \
                 os.environ.get("GS_WGRAD_DET", "1") != "0":
             ckey = ("cout1_w", id(ent[0]))
-            nws = self._desc_cache.get(ckey)
+            nws = self._plans.get(ckey)
             if nws is None:
                 nws = int(self.lib.gs_wgrad_cout1_ws_floats(C.byref(ent[0])))
-                self._desc_cache[ckey] = nws
+                self._plans[ckey] = nws
             if nws > 0 and (not twin or dw.delta() % 16 == 0):
                 # one output channel: x[q] times the 4 x 4 patch of dy around q on the vector ALUs (csrc/cout1.hip)
                 tw = None
@@ -545,11 +502,11 @@ class HipOps(TwinSplit):
                 return
         if twin:      # both networks' images in one launch where the layer's kernel has the form, else the two halves
             wkey = ("wgrad_ws", id(ent[0]), pair is not None, "twin")
-            nws = self._desc_cache.get(wkey)
+            nws = self._plans.get(wkey)
             if nws is None:
                 nws = int(self.lib.gs_wgrad_ws_floats_twin(C.byref(ent[0]), int(pair is not None))) \
                     if self.lib.gs_wgrad_twin_native(C.byref(ent[0]), int(pair is not None)) else -1
-                self._desc_cache[wkey] = nws
+                self._plans[wkey] = nws
             if nws <= 0:
                 return self.twin_wgrad(w, a, g, dw, a_cs=a_cs, a_co=a_co, g_cs=g_cs, g_co=g_co, pair=pair)
             tw = L.Twin()
@@ -565,13 +522,13 @@ class HipOps(TwinSplit):
         t_end = self._time_begin("wgrad", w, pair is not None, a.shape[0])
         if os.environ.get("GS_WGRAD_DET", "1") != "0":
             # deterministic accumulation (default): partial sums to a per-launch workspace, fixed-order second stage
-            wkey = ("wgrad_ws", id(ent[0]), pair is not None)        # (set_option drops these plans)
-            nws = self._desc_cache.get(wkey)
+            wkey = ("wgrad_ws", id(ent[0]), pair is not None)
+            nws = self._plans.get(wkey)
             if nws is None:
                 nws = int(self.lib.gs_wgrad_ws_floats(C.byref(ent[0]), int(pair is not None)))
                 if nws < 0:
                     L.check(2, "gs_wgrad_ws_floats")
-                self._desc_cache[wkey] = nws
+                self._plans[wkey] = nws
             # (0 floats: single-contributor layers accumulate straight into dw, no workspace)
             ws = torch.empty(nws, dtype=torch.float32, device=self.device) if nws else None   # stream-safe via the allocator
             a2, g2 = pair if pair is not None else (None, None)

@@ -159,17 +159,11 @@ class BaseGAN(ABC):
         """before the backward pass of a network group that takes ONE backward pass per step: its optimiser updates the layers
         the pass is done with while the pass goes on (NativeAdam.arm_early) — by default as launches of the same stream, between
         the pass's own (Pix2Pix: 3.82 -> 3.65 ms per step, profiles/r06_ab_pix2pix.txt). GS_EARLY_ADAM=0: the update after the
-        pass; =stream: the chunks on the 'opt' stream beside the pass (measured: slower, 4.1 ms)."""
-        mode = os.environ.get("GS_EARLY_ADAM", "1")
+        pass."""
         optim = self.optimizers[name]
-        if mode == "0" or not hasattr(optim, "arm_early"):
+        if os.environ.get("GS_EARLY_ADAM", "1") == "0" or not hasattr(optim, "arm_early"):
             return False
-        if mode != "stream":
-            return optim.arm_early(None)
-        st = getattr(self, "_side", {}).get("opt")
-        if st is None or not self._side_stream_enabled("opt"):
-            return False
-        return optim.arm_early(st["stream"])
+        return optim.arm_early()
 
     # ---- captured training step -------------------------------------------------------------------------------
     def _init_step_graph(self):

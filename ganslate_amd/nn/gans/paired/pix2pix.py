@@ -26,7 +26,7 @@ class Pix2PixConditionalGANConfig(configs.base.BaseGANConfig):
 
 class Pix2PixConditionalGAN(BaseGAN):
     graph_capturable = True      # fixed launch sequence, no image pool
-    side_stream_names = ("D", "opt")
+    side_stream_names = ("D",)
 
     def __init__(self, conf):
         super().__init__(conf)

@@ -60,9 +60,6 @@ class CycleGAN(BaseGAN):
         the chip at batch 1 and the per-network PReLU-norm launches stay halves: profiles/r06_ab_vnet_twin.txt) — executors
         that set twin_default = False pair up only with GS_TWIN=all."""
         self.twin_G = self.twin_D = None
-        for name in ("G_AB", "G_BA"):      # (GS_WGRAD_STREAM=1: their weight gradients beside the data-gradient chain, net.py)
-            if name in self.networks and self.networks[name] is not None:
-                self.networks[name].wgrad_side_stream = True
         mode = os.environ.get("GS_TWIN", "1")
         if not self.is_train or mode == "0":
             return

@@ -26,14 +26,6 @@ from .twin import Twin
 
 import os
 import weakref
-# (GS_BWD_ORDER=0 — backward passes of one network unordered across streams — is gone: since the one-split weight-gradient
-# launches add to dw with plain loads / stores (gs_wgrad_desc.dw_fresh note in ganslate_hip.h), overlapping them loses updates)
-_BWD_ORDER = True
-# GS_WGRAD_STREAM=1: networks a recipe marks (wgrad_side_stream) launch their weight-gradient kernels on a stream of their own.
-# Nothing inside a backward pass waits for a weight gradient — the chain is apply -> data gradient -> apply -> ... — so the
-# (compute-bound, long) weight-gradient launches can fill in beside the chain's memory-bound norm passes
-_WGRAD_STREAM = os.environ.get("GS_WGRAD_STREAM", "0") == "1"
-_wgrad_streams = {}
 
 
 @dataclass
@@ -423,7 +415,7 @@ class NativeNet:
     # the previous backward pass of the SAME network has finished, whatever stream that ran on. Only networks a recipe
     # marks (multi_stream_passes) pay for the events.
     def _order_backward_begin(self):
-        if self.device.type == "cuda" and _BWD_ORDER and self.multi_stream_passes:
+        if self.device.type == "cuda" and self.multi_stream_passes:
             ev = getattr(self, "_bwd_done", None)
             # An event from before a stream capture began (or from inside one that has ended) orders nothing here: the
             # capture's own begin / end already does. A pass on the stream the previous one ran on is ordered by the
@@ -433,7 +425,7 @@ class NativeNet:
                 torch.cuda.current_stream().wait_event(ev[0])
 
     def _order_backward_end(self):
-        if self.device.type == "cuda" and _BWD_ORDER and self.multi_stream_passes:
+        if self.device.type == "cuda" and self.multi_stream_passes:
             from ...utils.streams import new_event
             ev = new_event()
             ev.record()
@@ -718,29 +710,6 @@ class NativeNet:
         skip: Dict[int, torch.Tensor] = {}
         db_items = []        # bias gradients of the convs in front of norms: one batched launch at the end of the pass
         final_pass = want_w and self._dist is not None and self._fw_pending == 0 and not self.external_reduce
-        # weight gradients on their own stream (see _WGRAD_STREAM): not when this pass reduces buckets as it goes
-        wst = None
-        if _WGRAD_STREAM and want_w and dev.type == "cuda" and getattr(self, "wgrad_side_stream", False) and not final_pass:
-            wst = _wgrad_streams.get(dev.index)
-            if wst is None:
-                wst = _wgrad_streams[dev.index] = torch.cuda.Stream(device=dev)
-        wst_used = False
-
-        def on_wgrad_stream(fn, *tensors):
-            """fn() behind everything launched so far, on the weight-gradient stream; `tensors` are its operands"""
-            nonlocal wst_used
-            if wst is None:
-                return fn()
-            from ...utils.streams import new_event
-            ev = new_event()
-            ev.record()
-            wst.wait_event(ev)
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(wst)
-            wst_used = True
-            with torch.cuda.stream(wst):
-                return fn()
         # another recorded forward of this net still awaits its backward (G_AB(real_A) and G_AB(fake_A) in one step):
         # hold the weight gradients of mergeable layers back and issue both passes as one launch then
         more_passes = want_w and self._fw_pending > 0 and start is None
@@ -764,28 +733,10 @@ class NativeNet:
                     self.grad_dirty = True
             g_pad, fold, g2, fmode = pending[:4]
             pre = pending[4] if len(pending) > 4 else None
-            applied = pending[5] if len(pending) > 5 else None
             x_out = s.acts[i + 1]
             # ---- gradient w.r.t. the conv output y ---------------------------------------------------------------
             need_total = nd.res is not None
-            if applied is not None:
-                # the data-gradient launch of the layer above already ran this norm's backward (gs_gconv_ring_apply): dy, the
-                # total gradient for the skip path and the per-image totals for the bias gradient are there
-                dy, total = applied["dy"], applied["total"]
-                if want_w and sp.bias:
-                    db = grad[self.b_off[i]:self.b_off[i] + sp.cout_p]
-                    holder, off = pre[1], pre[1].numel() - N * 3 * sp.cout_p
-                    if tw is None:
-                        items = [(holder, off, s.mrs[i], db, N, sp.cout_p, lw.out_pixels)]
-                    else:
-                        hm = s.mrs[i].numel() // 2
-                        items = [(holder, off + h * Nh * 3 * sp.cout_p, s.mrs[i][h * hm:(h + 1) * hm], db.half(h), Nh,
-                                  sp.cout_p, lw.out_pixels) for h in (0, 1)]
-                    if final_pass:
-                        ops.norm_bias_grads(items)
-                    else:
-                        db_items += items
-            elif nd.norm or nd.act != "none" or fold > 0 or g2 is not None:
+            if nd.norm or nd.act != "none" or fold > 0 or g2 is not None:
                 dy = torch.empty_like(x_out)
                 gsum = torch.empty_like(x_out) if (need_total and (fold > 0 or g2 is not None)) else None
                 if nd.norm:
@@ -838,13 +789,12 @@ class NativeNet:
                         held[1].record_stream(torch.cuda.current_stream())
                         held[2].record_stream(torch.cuda.current_stream())
                     self._wgrad_written(i, tw)
-                    on_wgrad_stream(lambda: ops.wgrad(lw.wgrad, a_t, g_t, dw, pair=(held[1], held[2])),
-                                    a_t, g_t, held[1], held[2])
+                    ops.wgrad(lw.wgrad, a_t, g_t, dw, pair=(held[1], held[2]))
                 elif more_passes and ops.can_merge_wgrad(lw.wgrad):
                     self._deferred[i] = (lw.wgrad, a_t, g_t, tw)      # (noted as written when it is launched)
                 else:
                     fresh = self._wgrad_written(i, tw)
-                    on_wgrad_stream(lambda: ops.wgrad(lw.wgrad, a_t, g_t, dw, fresh=fresh), a_t, g_t)
+                    ops.wgrad(lw.wgrad, a_t, g_t, dw, fresh=fresh)
                 if sp.bias and not nd.norm:
                     for h in range(N // Nh):
                         gh_ = grad.half(h) if tw is not None else grad
@@ -877,26 +827,11 @@ class NativeNet:
                     plan = ops.fused_multi_plan(lw.dgrad, N, sp.cin_p, twin=tw is not None)
                 ring = ops.fused_ring_plan(lw.dgrad_ring, N, sp.cin_p, twin=tw is not None) \
                     if (plan is not None and nodes[i - 1].act != "tanh") else None     # (the ring form has no tanh' path)
-                if ring is None:
-                    gx = torch.empty(N, *lw.dgrad_dims, sp.cin_p, dtype=self.ops.act_dtype, device=dev)
-                # ... and where every workgroup of that launch is resident at once, the WHOLE norm backward does: the launch
-                # writes the previous layer's dy (and the total gradient its skip path wants) instead of gx. Passes of this
-                # network on several streams could run two such launches at once (each waits for its own workgroups): not then.
-                sync = ops.ring_apply_plan(lw.dgrad_ring, N, sp.cin_p, twin=tw is not None) \
-                    if (ring is not None and not self.multi_stream_passes and (i - 1) not in inj_y) else None
-                if sync is not None:
-                    fz = {"y": s.ys[i - 1], "mean_rstd": s.mrs[i - 1], "g2": g2n, "partial": ring[1], "fold": f,
-                          "fold_mode": fmode_n, "act": nodes[i - 1].act, "slope": nodes[i - 1].slope}
-                    dy_prev = torch.empty(N, *lw.in_dims, sp.cin_p, dtype=self.ops.act_dtype, device=dev)
-                    want_total = nodes[i - 1].res is not None and g2n is not None
-                    tot_prev = torch.empty_like(dy_prev) if want_total else None
-                    ops.gconv_ring_apply(lw.dgrad_ring, dy, dpack, dy_prev, tot_prev, fz, sync)
-                    assert nodes[i - 1].res is None or g2n is not None, "a residual join always brings its skip gradient"
-                    pending = (None, 0, g2n, fmode_n, ring, {"dy": dy_prev, "total": tot_prev})
-                elif ring is not None:
-                    # reflect-padded wide 3x3 layer: the launch folds the ring of padded-domain pixels itself, the gradient
-                    # arrives on the unpadded domain
-                    gx = torch.empty(N, *lw.in_dims, sp.cin_p, dtype=self.ops.act_dtype, device=dev)
+                # (the ring form: the gradient arrives on the unpadded domain)
+                gx = torch.empty(N, *(lw.in_dims if ring is not None else lw.dgrad_dims), sp.cin_p, dtype=self.ops.act_dtype,
+                                 device=dev)
+                if ring is not None:
+                    # reflect-padded wide 3x3 layer: the launch folds the ring of padded-domain pixels itself
                     ops.gconv(lw.dgrad_ring, dy, dpack, None, gx,
                               fuse={"y": s.ys[i - 1], "mean_rstd": s.mrs[i - 1], "g2": g2n, "partial": ring[1], "fold": f,
                                     "fold_mode": fmode_n, "act": nodes[i - 1].act, "slope": nodes[i - 1].slope})
@@ -916,9 +851,6 @@ class NativeNet:
                 s.acts[i + 1] = None  # release as we go
         if db_items:
             ops.norm_bias_grads(db_items)
-        if wst_used:           # whatever follows this pass (the optimiser, another pass of this network) sees its weight gradients
-            from ...utils.streams import wait_stream
-            wait_stream(torch.cuda.current_stream(), wst)
         if not need_input_grad:
             return None
         gx, f, _, fmode = pending[:4]

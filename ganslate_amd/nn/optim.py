@@ -46,13 +46,12 @@ class NativeAdam(torch.optim.Optimizer):
     # are done with once its own gradients are launched (NativeNet._early_step_at), so for networks that take ONE backward pass
     # per step the update of the layers already passed can be launched while the pass goes on: same arithmetic per element.
     # Pix2Pix's 178 M-parameter generator (update 1.1 ms at HBM rate): as launches BETWEEN the pass's own, each chunk right
-    # behind the weight gradients it consumes, the step takes 3.65 instead of 3.82 ms; on a stream of its own beside the pass
-    # it takes 4.1 ms (the HBM-bound chunks slow the pass's weight-streaming launches more than they hide;
-    # profiles/r06_ab_pix2pix.txt). arm_early() before backward(), step() as always (it updates what the pass did not hand over).
+    # behind the weight gradients it consumes, the step takes 3.65 instead of 3.82 ms (profiles/r06_ab_pix2pix.txt).
+    # arm_early() before backward(), step() as always (it updates what the pass did not hand over).
     EARLY_MIN = 1 << 21          # smallest chunk worth a launch (elements)
 
-    def arm_early(self, stream=None):
-        """stream: the CUDA stream the chunks run on (None: the current one — tests). Returns False (and arms nothing) where the
+    def arm_early(self):
+        """the chunks run on the current stream, between the pass's own launches. Returns False (and arms nothing) where the
         early form does not apply: data-parallel networks (the gradient is all-reduced first), executors without the hook."""
         nets = [p._owner_net for group in self.param_groups for p in group["params"]]
         if self.deferred_to is not None or any(getattr(n, "_dist", None) is not None or not hasattr(n, "_early_step_at")
@@ -60,7 +59,7 @@ class NativeAdam(torch.optim.Optimizer):
             return False
         if not self.external_prepare:
             self.prepare()
-        self._early = {"stream": stream, "prepared": True, "launched": False,
+        self._early = {"prepared": True,
                        "tr": os.environ.get("GS_WGRAD_ADAM_TR", "1") != "0"}       # (A/B switch: transposed packs by the fused launch)
         fuse = os.environ.get("GS_WGRAD_ADAM", "1") != "0"       # (A/B switch)
         for net in nets:
@@ -133,27 +132,11 @@ class NativeAdam(torch.optim.Optimizer):
                                        grad_scale=1.0, zero_grad=True, packs=tgt[1] if tgt else None)
 
     def _early_chunk(self, net, start, end):
-        from ..utils import streams
         p = net.master
         if p.grad is None or start % 8 or start >= end:
             net._early_cursor = end          # (not handed over: step() takes it)
             return
-        side = self._early["stream"]
-        self._early["launched"] = True
-        if side is None:
-            self._update_range(p, net, start, end)
-            return
-        ev = streams.new_event()
-        ev.record()
-        side.wait_event(ev)
-        ops = get_ops()
-        cap = int(os.environ.get("GS_EARLY_ADAM_BLOCKS", "0")) if hasattr(ops, "lib") else 0
-        if cap:      # (the grid is fixed when the launch is enqueued)
-            ops.lib.gs_set_option(b"adam_blocks", cap)
-        with torch.cuda.stream(side):
-            self._update_range(p, net, start, end)
-        if cap:
-            ops.lib.gs_set_option(b"adam_blocks", 8192)
+        self._update_range(p, net, start, end)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -169,9 +152,6 @@ class NativeAdam(torch.optim.Optimizer):
     def launch(self):
         ops = get_ops()
         early, self._early = getattr(self, "_early", None), None
-        if early and early["stream"] is not None and early["launched"]:
-            from ..utils import streams
-            streams.wait_stream(torch.cuda.current_stream(), early["stream"])
         for group in self.param_groups:
             for p in group["params"]:
                 net = p._owner_net

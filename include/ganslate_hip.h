@@ -107,16 +107,17 @@ int gs_init(int device);                 /* torch.cuda.set_device + lazy cuDNN h
 void gs_shutdown(void);
 const char* gs_last_error(void);
 /* Kernel-selection switches (A/B measurements, parity tests): the library reads NO environment variable; the host
- * side maps its GS_* variables onto these (ganslate_amd/hip/ops.py). Names: splitk, splitk_max_blocks, splitk_target,
- * hconv, hconv_wide, hconvw_persist, hstrip_regs, gconv_twin, wgrad_twin, hwgrad, hwgrad_wide, hwgrad_planes, norm_bwd_ppb, norm_apply_unroll, gconv_tile288,
- * gconv_multi, hconvw_ring, hconvt (smallest grid the parity-class halo kernel takes, 0 = off), hstrip (same for the k7
- * boundary-conv kernel); round 5 / 6: gconv_persist, hconvt_persist, wgrad_rows, splitk_multi, splitk_ring, gconv_ring4,
+ * side maps its GS_* variables onto these (ganslate_amd/hip/ops.py). Names, in the order of the table in api.hip:
+ * splitk, splitk_max_blocks, splitk_target, hconv, hconv_wide, hwgrad, hwgrad_wide, hwgrad_planes, norm_bwd_ppb,
+ * norm_apply_unroll, gconv_tile288, gconv_multi, hconvw_ring, hconvt (smallest grid the parity-class halo kernel takes,
+ * 0 = off), hstrip (same for the k7 boundary-conv kernel), wfold_rows, hwgrad_ft, gconv_big, hconv_box8, hconvw_persist,
+ * hstrip_regs, gconv_twin, wgrad_twin, gconv_persist, hconvt_persist, wgrad_rows, splitk_multi, splitk_ring, gconv_ring4,
  * hconv5 (register-resident-weights kernel for the 16 -> 16 channel k5 volume convs: smallest volume in units of 2048 voxels,
  * 0 = off), hconv5_seg (z segments per column, 0 = auto), hwgrad2 / hconv2 (double-buffered volume forms of the narrow weight
  * gradient / forward kernels), pwise (one-tap layers with <= 8 channels on one side — the V-Net's 32 -> 1 output conv — on
- * register-operand kernels: smallest volume in units of 2048 voxels, 0 = off). Every setting computes the same function (up to the fp32 summation order and, for hconvw_ring,
- * where the bf16 rounding of the folded gradient happens); none skips work — EXCEPT the timing ablations ring_apply > 1 and
- * ring_dbg != 0, which produce wrong results by design and exist for profiles/ only. Unknown name -> non-zero. */
+ * register-operand kernels: smallest volume in units of 2048 voxels, 0 = off). Every setting computes the same function (up to
+ * the fp32 summation order and, for hconvw_ring, where the bf16 rounding of the folded gradient happens); none skips work.
+ * Unknown name -> non-zero. */
 int gs_set_option(const char* name, int value);
 int gs_get_option(const char* name, int* value);
 int gs_tile_m(const gs_gconv_desc* d);   /* pixel-tile height of the im2col kernel for this class */
@@ -184,20 +185,6 @@ int gs_gconv_forward_multi_fused(const gs_gconv_desc* const* descs, int32_t coun
  * slots = gs_gconv_ring_slots(d). Returns 0 slots when the layer / grid does not suit the halo kernel; the padded form
  * above is always available. */
 int gs_gconv_ring_slots(const gs_gconv_desc* d);
-/* The same launch with the consumer's WHOLE InstanceNorm backward inside it (round 5): where gs_inorm_act_backward(pre_slots)
- * would follow the ring-form launch — ganslate/nn/generators/resnet/resnet2d.py:80-93 backward: conv <- ReflectionPad <-
- * [ReLU <-] InstanceNorm2d (ganslate/nn/utils.py:53-59) — the boxes of an image meet inside the launch (their partial sums
- * written through to memory, one arrival counter per image and channel tile), add the slots up in slot order and write
- * dy = rstd * (ghat - mean ghat - yhat * mean(ghat * yhat)) instead of the input gradient; with a residual-join gradient
- * fuse->g2 and total != NULL also the total gradient gx + g2 the skip path wants. Bit for bit the results of the two launches;
- * fuse->partial keeps its layout ([N][slots][3][C] partial sums, then [N][3][C] per-image totals for gs_norm_bias_grads).
- * gs_gconv_ring_apply_words(d): int32 words of the rendezvous buffer `sync` (zero-filled once by the caller, left zero by every
- * launch; one buffer per stream), 0 when the launch cannot run in this form — every workgroup must be resident at once, so
- * only persistent grids of at most one workgroup per CU qualify, and the caller must not run two such launches concurrently
- * on different streams. */
-int gs_gconv_ring_apply_words(const gs_gconv_desc* d);
-int gs_gconv_ring_apply(const gs_gconv_desc* d, const void* in, const void* w_pack, const gs_gconv_fuse* fuse, void* dy,
-                        void* total, int32_t* sync, const gs_twin* tw, void* stream);
 /* Twin batches (gs_twin above). gs_gconv_twin_native: 1 when the kernel gs_gconv_forward (fuse == NULL) or
  * gs_gconv_forward_fused (fuse != NULL) would pick for `d` — d->N = the whole batch of both networks — selects the weight
  * set per image; 0: the caller runs the two halves as two launches (always possible: the halves are contiguous).

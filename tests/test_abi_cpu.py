@@ -28,6 +28,21 @@ def test_library_exports_every_declared_symbol():
     assert sorted(L.EXPORTS) == names, "ctypes prototypes and header declarations differ"
 
 
+def test_every_env_option_is_a_library_option():
+    """HipOps.ENV_OPTIONS maps the host's GS_* variables onto gs_set_option names. sync_options skips names the library does
+    not know (an older build in an A/B), so a stale entry would go unnoticed: every name must be an option of this build
+    (gs_get_option is host code, no GPU needed)."""
+    from ganslate_amd.hip import lib as L
+    from ganslate_amd.hip.ops import HipOps
+    if not L.library_path().is_file():
+        import __graft_entry__
+        __graft_entry__.build()
+    lib = L.load()
+    value = ctypes.c_int(0)
+    for env, name in HipOps.ENV_OPTIONS.items():
+        assert lib.gs_get_option(name.encode(), ctypes.byref(value)) == 0, f"{env} -> '{name}': not an option of the library"
+
+
 def test_descriptor_layouts_match_header():
     from ganslate_amd.hip import lib as L
     # gs_gconv_desc: 26 int32 + float + 3 int32 + 3 * GS_MAX_TAPS int8
