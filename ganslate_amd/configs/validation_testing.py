@@ -1,5 +1,7 @@
-"""ganslate/configs/validation_testing.py restated — parsed so YAMLs with val/test sections load; the
-validation/test engines themselves are out of the hot-path scope."""
+"""ganslate/configs/validation_testing.py restated: the `val` section drives the Validator inside training, the `test`
+section the Tester (engines/validator.py). Every metric flag below is honoured on the GPU (utils/val_metrics.py);
+`cycle_metrics` adds cycle_SSIM in validation, `compute_over_input` the Original_* scores, `save_to_csv` the Tester's
+per-sample metrics.csv."""
 from dataclasses import dataclass, field
 from typing import Any, Dict, Optional, Tuple
 

@@ -1,12 +1,29 @@
-"""Validator — the in-training validation pass (ganslate/engines/validator_tester.py:9-60,100-112 +
-trainer.py:95-108): shares the Trainer's model, runs `infer` (sliding-window when configured) over the validation
-loader(s) and reports the scalar metrics of utils/metrics/val_test_metrics.py that need no third-party package
-(mae, mse, nmse, psnr; ssim / nmi / histogram_chi2 rely on scikit-image / scipy in the reference and are skipped with a
-log line). Saving generated tensors and the W&B / TensorBoard trackers stay out of scope."""
+"""Validator and Tester (ganslate/engines/validator_tester.py:9-135 + trainer.py:95-108). The Validator shares the
+Trainer's model; the Tester builds the generator itself and loads `test.checkpointing.load_iter` (BaseGAN.setup). Both
+run `infer` (sliding-window when configured) over their loader(s) and score every sample with the metrics of
+utils/metrics/val_test_metrics.py that `<mode>.metrics` enables.
+
+- Model on the GPU: all seven metrics (mae, mse, nmse, psnr, ssim, nmi, histogram_chi2) on the device
+  (utils/val_metrics.py, valmetrics.hip), plus `cycle_SSIM` = ssim(real_A, infer(fake_B, direction="BA")) in validation
+  when `val.metrics.cycle_metrics` is set. A model whose `infer` takes no `direction` (Pix2Pix, CUT) gets a log line and
+  no cycle metric; the reference raises a RuntimeError there, which with the default `cycle_metrics: true` stops every
+  Pix2Pix / CUT validation. The per-sample tables stay on the device until the end of each dataset.
+- Model on the CPU (the oracle backend of the test-suite): the host path of mae, mse, nmse and psnr below; ssim, nmi and
+  histogram_chi2 are skipped there with a log line.
+
+Batches that carry `masks` are scored without them (masked metrics are out of scope). The Tester writes
+`<test.output_dir>/test/metrics.csv` when `test.metrics.save_to_csv` is set: one row per sample, one column per metric,
+plus a `dataset` column with `multi_dataset`. Saving generated tensors and the W&B / TensorBoard trackers stay out of
+scope."""
+import csv
+import inspect
+from pathlib import Path
+
 import numpy as np
 import torch
 
-from ..utils.builders import build_loader
+from ..utils import environment
+from ..utils.builders import build_gan, build_loader
 from .base import BaseEngineWithInference
 
 
@@ -31,60 +48,177 @@ def _psnr(gt, pred):
 METRICS = {"mae": _mae, "mse": _mse, "nmse": _nmse, "psnr": _psnr}
 
 
-class Validator(BaseEngineWithInference):
+def _takes_direction(fn):
+    try:
+        params = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(p.name == "direction" or p.kind == p.VAR_KEYWORD for p in params)
 
-    def __init__(self, conf, model):
+
+class BaseValTestEngine(BaseEngineWithInference):
+    """The metric loop shared by the Validator and the Tester; subclasses set `self.model` and call `_init_metrics`."""
+
+    def __init__(self, conf):
         super().__init__(conf)
-        self.model = model
         self.data_loaders = build_loader(self.conf)
         if not isinstance(self.data_loaders, dict):
             self.data_loaders = {None: self.data_loaders}
         self.history = []          # (iteration, dataset name, {metric: mean over the samples})
-        wanted = self.conf.val.metrics
-        self.metric_names = [k for k in METRICS if getattr(wanted, k, False)]
-        skipped = [k for k in ("ssim", "nmi", "histogram_chi2") if getattr(wanted, k, False)]
-        if skipped:
-            self.logger.info(f"validation metrics {skipped} need scikit-image / scipy in the reference; skipped here")
+        self.samples = {}          # dataset name -> per-sample rows of the last run
+        self.metricizer = None
+        self._masks_logged = False
 
-    def _set_mode(self):
-        self.conf.mode = "val"
+    def _init_metrics(self):
+        wanted = self.conf[self.conf.mode].metrics
+        self.on_device = self.model.device.type == "cuda"
+        self.cycle = False
+        if self.on_device:
+            from ..utils.val_metrics import DeviceValTestMetrics
+            self.metricizer = DeviceValTestMetrics(self.conf)
+            if getattr(wanted, "cycle_metrics", False):
+                self.cycle = _takes_direction(self.model.infer)
+                if not self.cycle:
+                    self.logger.info(f"{self.conf.mode}.metrics.cycle_metrics: `{type(self.model).__name__}.infer` has no "
+                                     "`direction`; cycle_SSIM skipped")
+        else:
+            self.metric_names = [k for k in METRICS if getattr(wanted, k, False)]
+            skipped = [k for k in ("ssim", "nmi", "histogram_chi2") if getattr(wanted, k, False)]
+            if skipped:
+                self.logger.info(f"{self.conf.mode} metrics {skipped} need scikit-image / scipy in the reference; "
+                                 "skipped here")
 
     def run(self, current_idx=None):
-        self.logger.info("Validation started.")
+        self.logger.info(f'{"Validation" if self.conf.mode == "val" else "Testing"} started.')
         was_training = [getattr(net, "training", True) for net in self.model.networks.values()]
         self.model.eval()
         try:
             for name, loader in self.data_loaders.items():
-                rows = []
                 dataset = loader.dataset
                 if getattr(getattr(dataset, "conf", None), "device_transforms", False) or \
                         getattr(dataset, "device_transforms", False):
-                    raise NotImplementedError("validation datasets run the host transform path: set "
-                                              "`val.dataset.device_transforms: false` (the device-side pipeline batches "
-                                              "training samples only)")
+                    raise NotImplementedError(f"{self.conf.mode} datasets run the host transform path: set "
+                                              f"`{self.conf.mode}.dataset.device_transforms: false` (the device-side "
+                                              "pipeline batches training samples only)")
                 # Denormalize the data if the dataset defines `denormalize` (validator_tester.py:72-77)
                 denormalize = getattr(dataset, "denormalize", None)
-                over_input = bool(getattr(self.conf.val.metrics, "compute_over_input", False))
-                for data in loader:
-                    real_A = data["A"].to(self.model.device)
-                    with torch.no_grad():
-                        fake_B = self.infer(real_A)
-                    pred, target, original = fake_B.detach().float().cpu(), data["B"].float(), data["A"].float()
-                    if denormalize:
-                        pred, target = denormalize(pred.clone()), denormalize(target.clone())
-                        if over_input:
-                            original = denormalize(original.clone())
-                    pred, target, original = pred.numpy(), target.numpy(), original.numpy()
-                    # one score per SAMPLE of the batch (ValTestMetrics.get_metrics iterates zip(inputs, targets),
-                    # val_test_metrics.py:152-153): psnr's data range and nmse's norm are per sample
-                    for i in range(pred.shape[0]):
-                        row = {k: METRICS[k](target[i], pred[i]) for k in self.metric_names}
-                        if over_input:
-                            row.update({f"Original_{k}": METRICS[k](target[i], original[i]) for k in self.metric_names})
-                        rows.append(row)
+                over_input = bool(getattr(self.conf[self.conf.mode].metrics, "compute_over_input", False))
+                score = self._device_rows if self.on_device else self._host_rows
+                rows = score(loader, denormalize, over_input)
+                self.samples[name] = rows
                 mean = {k: float(np.mean([r[k] for r in rows])) for k in rows[0]} if rows else {}
                 self.history.append((current_idx, name, mean))
-                self.logger.info(f"val @ {current_idx} [{name}] {mean}")
+                self.logger.info(f"{self.conf.mode} @ {current_idx} [{name}] {mean}")
         finally:
             for net, flag in zip(self.model.networks.values(), was_training):
                 net.train(flag)
+
+    def _log_masks(self, data):
+        if "masks" in data and not self._masks_logged:
+            self.logger.info("batches carry `masks`: masked metrics are out of scope, the masks are ignored")
+            self._masks_logged = True
+
+    def _host_rows(self, loader, denormalize, over_input):
+        rows = []
+        for data in loader:
+            self._log_masks(data)
+            real_A = data["A"].to(self.model.device)
+            with torch.no_grad():
+                fake_B = self.infer(real_A)
+            pred, target, original = fake_B.detach().float().cpu(), data["B"].float(), data["A"].float()
+            if denormalize:
+                pred, target = denormalize(pred.clone()), denormalize(target.clone())
+                if over_input:
+                    original = denormalize(original.clone())
+            pred, target, original = pred.numpy(), target.numpy(), original.numpy()
+            # one score per SAMPLE of the batch (ValTestMetrics.get_metrics iterates zip(inputs, targets),
+            # val_test_metrics.py:152-153): psnr's data range and nmse's norm are per sample
+            for i in range(pred.shape[0]):
+                row = {k: METRICS[k](target[i], pred[i]) for k in self.metric_names}
+                if over_input:
+                    row.update({f"Original_{k}": METRICS[k](target[i], original[i]) for k in self.metric_names})
+                rows.append(row)
+        return rows
+
+    def _device_rows(self, loader, denormalize, over_input):
+        """per-batch device tables, one host copy per dataset (validator_tester.py:62-112)"""
+        m = self.metricizer
+        tables, originals, cycles = [], [], []
+        for data in loader:
+            self._log_masks(data)
+            real_A = data["A"].to(self.model.device)
+            with torch.no_grad():
+                fake_B = self.infer(real_A)
+                target = data["B"].to(self.model.device)
+                pred, target, original = fake_B.detach().float(), target.float(), real_A.float()
+                if denormalize:
+                    pred, target = denormalize(pred.clone()), denormalize(target.clone())
+                    if over_input:
+                        original = denormalize(original.clone())
+                tables.append(m.table(pred, target))
+                if over_input:
+                    originals.append(m.table(original, target))
+                if self.cycle:
+                    rec_A = self.infer(fake_B, direction="BA")
+                    cycles.append(m.cycle_table(rec_A, real_A))
+        if not tables:
+            return []
+        cols = m.to_lists(torch.cat(tables))
+        if over_input:
+            cols.update(m.to_lists(torch.cat(originals), prefix="Original_"))
+        if self.cycle:
+            cols["cycle_SSIM"] = torch.cat(cycles).cpu().tolist()
+        n = len(next(iter(cols.values()))) if cols else 0
+        return [{k: v[i] for k, v in cols.items()} for i in range(n)]
+
+
+class Validator(BaseValTestEngine):
+
+    def __init__(self, conf, model):
+        super().__init__(conf)
+        self.model = model
+        self._init_metrics()
+
+    def _set_mode(self):
+        self.conf.mode = "val"
+
+
+class Tester(BaseValTestEngine):
+    """Scores the generator of checkpoint `test.checkpointing.load_iter` on the test set(s) (validator_tester.py:127-135)
+    and writes the per-sample metrics.csv. There is no cycle metric in test mode (TestMetricsConfig has no such flag, and
+    a CycleGAN built outside training holds only G_AB)."""
+
+    def __init__(self, conf):
+        super().__init__(conf)
+        # under this engine's own `test.output_dir`, as the reference's tracker does (trackers/base.py:18);
+        # BaseEngine's directory follows the caller's conf, whose mode is still "train"
+        self.output_dir = Path(self.conf.test.output_dir) / "test"
+        environment.setup_logging()
+        self.model = build_gan(self.conf)
+        self._init_metrics()
+
+    def _set_mode(self):
+        self.conf.mode = "test"
+
+    def run(self, current_idx=None):
+        super().run(current_idx)
+        if self.conf.test.metrics.save_to_csv:
+            self.write_csv()
+
+    def write_csv(self):
+        multi = self.conf.test.multi_dataset is not None
+        names = []
+        for rows in self.samples.values():
+            for r in rows:
+                names += [k for k in r if k not in names]
+        fields = (["dataset"] if multi else []) + ["sample"] + names
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        path = self.output_dir / "metrics.csv"
+        with open(path, "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=fields)
+            w.writeheader()
+            for name, rows in self.samples.items():
+                for i, r in enumerate(rows):
+                    w.writerow({**({"dataset": name} if multi else {}), "sample": i, **r})
+        self.logger.info(f"Per-sample test metrics written to `{path}`")
+        return path

@@ -9,6 +9,8 @@ from pathlib import Path
 GS_MAX_TAPS = 352
 BORDER = {"zero": 0, "reflect": 1, "replicate": 2}
 ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
+VM_FLAGS = {"ssim": 1, "hist": 2}     # GS_VM_SSIM, GS_VM_HIST
+VM_BINS = 100
 
 
 class GConvDesc(C.Structure):
@@ -219,6 +221,9 @@ _PROTOS = {
     "gs_ssim_distance_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_ssim_backward_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gs_valmetrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_valmetric_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gs_patchnce_param_floats": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_work_bytes": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_forward": (C.c_int, [C.POINTER(PatchNCEDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,

@@ -911,6 +911,39 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_ssim_distance(_ptr(x), _ptr(y), NC, H, W, _ptr(out), _ptr(scratch), _stream()),
                 "gs_ssim_distance")
 
+    # ---- validation / test image metrics (valmetrics.hip) --------------------------------------------------
+    VALMETRIC_COLUMNS = ("mae", "mse", "nmse", "psnr", "ssim", "nmi", "histogram_chi2")
+
+    def valmetrics(self, target, pred, ssim=True, hist=True, return_counts=False):
+        """Per-sample image metrics of val_test_metrics.py on the device: a [N, 7] fp64 table in VALMETRIC_COLUMNS order
+        (columns not asked for hold NaN). target / pred: [N, C, H, W] (the C channels are the SSIM planes) or
+        [N, C, D, H, W] (all C*D depth slices are). With return_counts, also the raw bin counts (t [N, 100], p [N, 100],
+        joint [N, 100, 100] indexed [t bin, p bin]) as int64 tensors. Enqueued on the current stream; nothing syncs."""
+        if target.shape != pred.shape:
+            raise ValueError(f"target {tuple(target.shape)} and prediction {tuple(pred.shape)} differ in shape")
+        if target.dim() not in (4, 5):
+            raise NotImplementedError(f"image metrics for {target.dim() - 1}-D samples are not implemented")
+        N, H, W = target.shape[0], target.shape[-2], target.shape[-1]
+        P = target[0].numel() // (H * W)
+        if ssim and (H < 7 or W < 7):
+            raise ValueError(f"SSIM needs planes of at least 7 x 7 (the window size); got {H} x {W}")
+        if P * H * W >= 2 ** 31:
+            raise ValueError("a sample must hold fewer than 2^31 elements")
+        hist = hist or return_counts
+        t = target.detach().contiguous().float()
+        p = pred.detach().contiguous().float()
+        table = torch.empty(N, 7, dtype=torch.float64, device=t.device)
+        counts = torch.empty(N, 2 * L.VM_BINS + L.VM_BINS ** 2, dtype=torch.int32, device=t.device) if hist else None
+        scratch = torch.empty(self.lib.gs_valmetric_scratch_bytes(N, P, H, W), dtype=torch.uint8, device=t.device)
+        flags = (L.VM_FLAGS["ssim"] if ssim else 0) | (L.VM_FLAGS["hist"] if hist else 0)
+        L.check(self.lib.gs_valmetrics(_ptr(t), _ptr(p), N, P, H, W, flags, _ptr(table), _ptr(counts), _ptr(scratch),
+                                       _stream()), "gs_valmetrics")
+        if not return_counts:
+            return table
+        B = L.VM_BINS
+        c = counts.long()
+        return table, (c[:, :B], c[:, B:2 * B], c[:, 2 * B:].reshape(N, B, B))
+
     # ---- optimiser -----------------------------------------------------------------------------------------
     def adam_step(self, p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, zero_grad=True):
         bc1 = 1.0 - beta1 ** step

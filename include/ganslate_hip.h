@@ -489,6 +489,21 @@ int gs_ssim_distance_backward(const float* x, const float* y, int32_t NC, int32_
                               const float* grad_scale, float* grad_y, float* scratch, void* stream);
 int64_t gs_ssim_backward_scratch_floats(int32_t NC, int32_t H, int32_t W);
 
+/* ---- validation / test image metrics (ganslate/utils/metrics/val_test_metrics.py:37-166, valmetrics.hip) ----
+ * t (target) and p (prediction): N samples of P planes of H x W fp32, contiguous. table = device [N][7] fp64, one row per
+ * sample: mae, mse, nmse (:37-53), psnr = 10 log10(max(t)^2 / mse) (:56-59), ssim = mean over the P planes of skimage
+ * structural_similarity with defaults (7x7 uniform window, sample covariance, K1 0.01, K2 0.03, data range max(t) of the
+ * sample; :62-87), nmi (:90-107) and histogram_chi2 (:110-131) from 100-bin histograms with numpy's float32 edges.
+ * mae..psnr are always computed; GS_VM_SSIM adds ssim (needs H, W >= 7), GS_VM_HIST adds nmi and histogram_chi2 and needs
+ * counts = device [N][2*100 + 100*100] uint32 (t bins, p bins, joint [t bin][p bin]), which it leaves holding the raw
+ * bin counts. Columns not computed hold NaN. No float atomics: results are bitwise reproducible. At most four launches.
+ * Inputs must be finite: where numpy raises ValueError on an inf / NaN histogram range, inf / NaN values are binned here
+ * without an error. */
+enum { GS_VM_SSIM = 1, GS_VM_HIST = 2 };
+int gs_valmetrics(const float* t, const float* p, int32_t N, int32_t P, int32_t H, int32_t W, int32_t flags,
+                  double* table, uint32_t* counts, void* scratch, void* stream);
+int64_t gs_valmetric_scratch_bytes(int32_t N, int32_t P, int32_t H, int32_t W);
+
 /* ---- PatchNCE + patch MLP of CUT (ganslate/nn/gans/unpaired/cut.py:229-294, ganslate/nn/losses/cut_losses.py:14-43) ----
  * For every feature level l: sampled patches xq[l], xk[l] are [batch*patches][channels[l]] fp32 (target = query, source =
  * key, row = image * patches + patch); FeaturePatchMLP level l = Linear(C_l, nc) - ReLU - Linear(nc, nc) - x/(||x||+1e-7);

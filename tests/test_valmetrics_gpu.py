@@ -1,0 +1,122 @@
+"""Device validation / test metrics (valmetrics.hip through HipOps.valmetrics and utils/val_metrics.py) against the
+float64 restatement of val_test_metrics.py (tests/valmetrics_ref.py), and the GPU Validator / Tester built on them."""
+import csv
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from tests import valmetrics_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(2, 3, 256, 256), (1, 1, 155, 240, 240), (3, 1, 16, 24, 20), (1, 3, 7, 7), (2, 1, 9, 300)]
+CONFIGS = Path(__file__).parent / "configs"
+
+
+def _data(shape, kind, seed=0):
+    rng = np.random.default_rng(seed)
+    if kind == "uniform":
+        t = rng.uniform(-1, 1, shape)
+        p = np.clip(t + rng.normal(0, 0.2, shape), -1, 1)
+    elif kind == "ct":                  # denormalised CT-like values with a flat region (air / water)
+        t = rng.uniform(-1000, 3000, shape)
+        t[..., : shape[-2] // 2, : shape[-1] // 2] = 40.0
+        p = t + rng.normal(0, 60, shape)
+    elif kind == "int":                 # many values exactly on bin edges
+        t = rng.integers(0, 101, shape)
+        p = np.clip(t + rng.integers(-3, 4, shape), 0, 100)
+    else:                               # one constant target sample: histogram range [c - 0.5, c + 0.5]
+        t = rng.uniform(-1, 1, shape)
+        p = rng.uniform(-1, 1, shape)
+        t[0] = 0.25
+    return t.astype(np.float32), p.astype(np.float32)
+
+
+@pytest.mark.parametrize("kind", ["uniform", "ct", "int", "constant"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_device_metrics_match_the_restatement(hip_ops, shape, kind):
+    t, p = _data(shape, kind)
+    table, (ht, hp, hj) = hip_ops.valmetrics(torch.from_numpy(t).cuda(), torch.from_numpy(p).cuda(), return_counts=True)
+    table, ht, hp, hj = table.cpu().numpy(), ht.cpu().numpy(), hp.cpu().numpy(), hj.cpu().numpy()
+    assert table.shape == (shape[0], 7)
+    for i in range(shape[0]):
+        want = ref.metrics(t[i], p[i])
+        got = dict(zip(ref.COLUMNS, table[i]))
+        for k in ("mae", "mse", "nmse", "psnr", "nmi", "histogram_chi2"):
+            assert got[k] == pytest.approx(want[k], rel=1e-9, abs=0), (i, k)
+        assert abs(got["ssim"] - want["ssim"]) <= 1e-5, (i, got["ssim"], want["ssim"])
+        wt, wp, wj = ref.bin_counts(t[i], p[i])
+        np.testing.assert_array_equal(ht[i], wt)
+        np.testing.assert_array_equal(hp[i], wp)
+        np.testing.assert_array_equal(hj[i], wj)
+
+
+def test_flags_launch_only_what_is_asked(hip_ops):
+    t, p = (torch.from_numpy(a).cuda() for a in _data((2, 1, 9, 300), "uniform"))
+    only = hip_ops.valmetrics(t, p, ssim=False, hist=False).cpu().numpy()
+    full = hip_ops.valmetrics(t, p).cpu().numpy()
+    assert np.isnan(only[:, 4:]).all() and not np.isnan(full).any()
+    np.testing.assert_array_equal(only[:, :4], full[:, :4])
+
+
+@pytest.mark.parametrize("hw", [(6, 9), (9, 6)])
+def test_planes_below_the_window_raise(hip_ops, hw):
+    t = torch.zeros(1, 2, *hw, device="cuda")
+    with pytest.raises(ValueError):
+        hip_ops.valmetrics(t, t + 1)
+    assert torch.isfinite(hip_ops.valmetrics(t + 1, t, ssim=False)[:, :4]).all()      # no SSIM: no window
+
+
+def test_tables_are_bitwise_reproducible(hip_ops):
+    t, p = (torch.from_numpy(a).cuda() for a in _data((1, 1, 155, 240, 240), "ct", seed=3))
+    a = hip_ops.valmetrics(t, p).cpu()
+    b = hip_ops.valmetrics(t, p).cpu()
+    assert torch.equal(a.view(torch.int64), b.view(torch.int64))
+
+
+def test_gpu_validation_reports_every_metric_and_cycle_ssim(hip_ops, tmp_path):
+    """Validator on the device (validator_tester.py:62-112): the seven metrics and cycle_SSIM per sample, means equal to
+    the restatement of the recorded predictions and reconstructions; then the Tester on the run's checkpoint"""
+    from ganslate_amd.engines import init_engine
+    args = [f"config={CONFIGS / 'cyclegan3d_val_synthetic.yaml'}", f"train.output_dir={tmp_path}",
+            f"val.output_dir={tmp_path}", "train.seed=7", "train.checkpointing.freq=2", "val.metrics.ssim=true",
+            "val.metrics.nmi=true", "val.metrics.histogram_chi2=true"]
+    tr = init_engine("train", args)
+    tr.run()
+    keys = set(ref.COLUMNS) | {"cycle_SSIM"}
+    assert [h[0] for h in tr.validator.history] == [2, 4]
+    assert all(set(m) == keys for _, _, m in tr.validator.history)
+    v = tr.validator
+    seen = []
+    infer = v.infer
+    v.infer = lambda x, *a, **k: (lambda y: (seen.append((k.get("direction", "AB"), x.float().cpu(), y.float().cpu())),
+                                             y)[1])(infer(x, *a, **k))
+    v.run(current_idx=5)
+    _, _, mean = v.history[-1]
+    loader = next(iter(v.data_loaders.values()))
+    fwd = [s for s in seen if s[0] == "AB"]
+    bwd = [s for s in seen if s[0] == "BA"]
+    rows = []
+    for (_, real_A, fake_B), (_, fake_B2, rec_A), data in zip(fwd, bwd, loader):
+        assert torch.equal(fake_B, fake_B2)
+        for i in range(real_A.shape[0]):
+            row = ref.metrics(data["B"][i].float().numpy(), fake_B[i].numpy())
+            row["cycle_SSIM"] = ref.ssim(real_A[i].numpy(), rec_A[i].numpy())
+            rows.append(row)
+    assert len(rows) == 2
+    for k in keys:
+        assert mean[k] == pytest.approx(float(np.mean([r[k] for r in rows])), rel=1e-6), k
+
+    elsewhere = tmp_path / "elsewhere"
+    te = init_engine("test", [f"config={CONFIGS / 'cyclegan3d_test_synthetic.yaml'}", f"train.output_dir={elsewhere}",
+                              f"test.output_dir={tmp_path}", "test.checkpointing.load_iter=2"])
+    assert te.on_device
+    te.run()
+    assert not elsewhere.exists()
+    with open(tmp_path / "test" / "metrics.csv", newline="") as f:
+        got = list(csv.DictReader(f))
+    assert len(got) == 3
+    assert set(got[0]) == {"sample", "ssim", "mse", "nmse", "psnr", "mae"}       # TestMetricsConfig defaults
+    assert all(np.isfinite(float(r[k])) for r in got for k in r)
