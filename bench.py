@@ -6,10 +6,16 @@ horse2zebra hyper-parameters, batch 8 per GPU) on N MI355X of one node.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N          # no WORLD_SIZE in the environment: starts the N ranks itself (child process)
+    python bench.py --full            # + the measurements attached to the line (see below)
 
 A "step" = set_input + optimize_parameters of ganslate_amd.nn.gans.unpaired.CycleGAN (what the reference's
 `t_comp` brackets, engines/trainer.py:56-60) on a synthetic batch already resident in HBM. One process per GPU;
 gradients are averaged over RCCL inside the step. Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline figure needs: set up, warm up, time the steps, write --dump-outputs,
+print. `--full` adds what takes runs of its own behind the timed region: the per-kernel HIP-event timings and the
+`roofline` block (`residual_conv_kernels`), the short timed runs of the other BASELINE configurations (`secondary`) and the
+stock-torch CPU baseline (`cpu_baseline`); --no-kernel-timing / --no-secondary / --no-cpu-baseline leave single ones out.
 """
 import argparse
 import json
@@ -225,8 +231,8 @@ def cpu_baseline(size=256, steps=5):
                       f"{steps} timed steps, {threads} threads of {cores} host cpus ({cpu})"}
 
 
-# BASELINE configs[2..4] (per-GPU shapes, SURVEY.md §8 GFLOP per unit): timed for a few steps behind the headline so that the
-# driver's line shows them too
+# BASELINE configs[2..4] (per-GPU shapes, SURVEY.md §8 GFLOP per unit): timed for a few steps behind the headline of a --full
+# run so that its line shows them too
 SECONDARY = {
     "pix2pix": {"config": "cityscapes pix2pix (BASELINE configs[2]): U-Net(7,128) + PatchGAN-4, 256x512, batch 1",
                 "unit": "img/s", "gflop_per_unit": 371.5},
@@ -346,7 +352,7 @@ def _run_secondary_one(dev, name, meta, steps, warmup):
     return out[name]
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -358,17 +364,28 @@ def main():
                          "cut = configs[3] (PatchNCE, batch 8, 256x256); "
                          "cyclegan3d = 3-D CycleGAN on 128^3 volumes with Resnet3D (configs[4] shape, batch 1); "
                          "brats = configs[4] with the brats yaml's own networks (Vnet3D + PatchGAN3D-2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the attached measurements: per-kernel HIP-event timings + "
+                         "`roofline`, `secondary` (the other BASELINE configs) and `cpu_baseline`; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: leave out the kernel timings and `roofline`")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short timed runs of the other BASELINE configs attached to the headline line as `secondary`")
+                    help="with --full: skip the short timed runs of the other BASELINE configs attached to the headline "
+                         "line as `secondary`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (visuals, losses, metrics) as "
                          "DIR/<kind>_<name>.npy, at most 64 MB in all (see dump_outputs); inputs and weights are seeded, "
                          "so two builds run with the same arguments can be compared output for output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_secondary = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # a timed kernel must never be one that was told to skip work: the ablation switches of round 1 are compiled out
     # of the library; refuse to run if somebody still sets them, or any other kernel "variant" selector
