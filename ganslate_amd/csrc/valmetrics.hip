@@ -10,6 +10,8 @@
 //                  LDS-private uint32 counts, then one integer add per non-empty bin per workgroup
 //   4. finalize  : one workgroup per sample reduces the slabs in a fixed order and writes the row
 // No float atomics anywhere: the table is bitwise identical from run to run.
+// gs_valmetrics_masked (further down) scores the same columns inside region masks, sharing the SSIM tile body and the
+// histogram scores with the passes above.
 // Inputs are expected to be finite. numpy's np.histogram raises ValueError on a non-finite range; here inf / NaN values
 // are binned without an error (the bin search settles on some bin) and the other metrics turn inf / NaN.
 #include "common.hpp"
@@ -166,31 +168,25 @@ __device__ __forceinline__ void vm_row7(const float (*st)[VM_TW + 6], const floa
   }
 }
 
-__global__ __launch_bounds__(VM_THREADS) void vm_ssim_kernel(const float* t, const float* p, int P, int H, int W,
-                                                             int tiles_w, int tiles_h, int nb_mom, const double* mom,
-                                                             double* partial) {
-  __shared__ float st[VM_TH + 6][VM_TW + 6];
-  __shared__ float sp[VM_TH + 6][VM_TW + 6];
-  __shared__ double sh[VM_THREADS];
-  int q = blockIdx.x;
-  const int tw = q % tiles_w; q /= tiles_w;
-  const int th = q % tiles_h; const int plane = q / tiles_h;
-  const int n = plane / P;
-  float rg[4];
-  vm_sample_range(mom + (size_t)n * nb_mom * VM_MOM, nb_mom, rg, sh);
+// the tile body shared by the unmasked and the masked kernel: stages the (32+6) x (64+6) patch at (y0, x0) of one plane
+// (MASKED: an element whose bit `label` of `bits` is clear is staged as 0, so t*m and p*m exist in LDS only) and returns
+// the workgroup's sum of the SSIM map over the tile's interior pixels (in every thread)
+template <bool MASKED>
+__device__ __forceinline__ double vm_ssim_tile(const float* tp, const float* pp, const uint8_t* bits, int label, int H,
+                                               int W, int y0, int x0, double R, float (*st)[VM_TW + 6],
+                                               float (*sp)[VM_TW + 6], double* sh) {
   const int Ho = H - 6, Wo = W - 6;
-  const int y0 = th * VM_TH, x0 = tw * VM_TW;
-  const float* tp = t + (size_t)plane * H * W;
-  const float* pp = p + (size_t)plane * H * W;
   for (int e = threadIdx.x; e < (VM_TH + 6) * (VM_TW + 6); e += VM_THREADS) {
     const int r = e / (VM_TW + 6), c = e % (VM_TW + 6);
     const int y = y0 + r, x = x0 + c;
     float a = 0.f, b = 0.f;
-    if (y < H && x < W) { a = tp[(size_t)y * W + x]; b = pp[(size_t)y * W + x]; }
+    if (y < H && x < W) {
+      a = tp[(size_t)y * W + x]; b = pp[(size_t)y * W + x];
+      if (MASKED && !((bits[(size_t)y * W + x] >> label) & 1)) { a = 0.f; b = 0.f; }
+    }
     st[r][c] = a; sp[r][c] = b;
   }
   __syncthreads();
-  const double R = (double)rg[1];
   const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
   const double inv = 1.0 / 49.0, cov = 49.0 / 48.0;
   const int c = threadIdx.x % VM_TW, g = threadIdx.x / VM_TW;
@@ -220,7 +216,23 @@ __global__ __launch_bounds__(VM_THREADS) void vm_ssim_kernel(const float* t, con
       }
     }
   }
-  acc = vm_block_sum(acc, sh);
+  return vm_block_sum(acc, sh);
+}
+
+__global__ __launch_bounds__(VM_THREADS) void vm_ssim_kernel(const float* t, const float* p, int P, int H, int W,
+                                                             int tiles_w, int tiles_h, int nb_mom, const double* mom,
+                                                             double* partial) {
+  __shared__ float st[VM_TH + 6][VM_TW + 6];
+  __shared__ float sp[VM_TH + 6][VM_TW + 6];
+  __shared__ double sh[VM_THREADS];
+  int q = blockIdx.x;
+  const int tw = q % tiles_w; q /= tiles_w;
+  const int th = q % tiles_h; const int plane = q / tiles_h;
+  const int n = plane / P;
+  float rg[4];
+  vm_sample_range(mom + (size_t)n * nb_mom * VM_MOM, nb_mom, rg, sh);
+  const double acc = vm_ssim_tile<false>(t + (size_t)plane * H * W, p + (size_t)plane * H * W, nullptr, 0, H, W,
+                                         th * VM_TH, tw * VM_TW, (double)rg[1], st, sp, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -258,12 +270,61 @@ __global__ __launch_bounds__(VM_THREADS) void vm_hist_kernel(const float* t, con
 // ---- pass 4: finalize -----------------------------------------------------------------------------------------------
 __device__ double vm_entr(double x) { return x > 0.0 ? -x * log(x) : 0.0; }
 
+// nmi and histogram_chi2 of one count table c ([t bins][p bins][joint]) of S elements whose histogram ranges are
+// rg = {min t, max t, min p, max p}; shared by the unmasked and the masked finalize (every thread gets both values)
+struct VmHistShared {
+  double rowsum[VM_BINS], colsum[VM_BINS];
+  float wt[VM_BINS], wp[VM_BINS];
+};
+__device__ __forceinline__ void vm_hist_scores(const unsigned* c, int64_t S, const float* rg, VmHistShared& hs,
+                                               double* sh, double& nmi, double& chi2) {
+  double* rowsum = hs.rowsum; double* colsum = hs.colsum;
+  float* wt = hs.wt; float* wp = hs.wp;
+  // histogram_chi2: each histogram normalised to sum 1 (the sum is S), 0/0 bins dropped
+  double chi = 0.0;
+  if (threadIdx.x < VM_BINS) {
+    const double g = (double)c[threadIdx.x] / (double)S, q = (double)c[VM_BINS + threadIdx.x] / (double)S;
+    if (g + q != 0.0) chi = (q - g) * (q - g) / (q + g);
+  }
+  chi2 = vm_block_sum(chi, sh);
+  // nmi: np.histogramdd([t, p], bins=100, density=True) = ((count / wt[i]) / wp[j]) / S with float32 widths
+  float ft, lt, fp, lp;
+  vm_outer_edges(rg[0], rg[1], ft, lt);
+  vm_outer_edges(rg[2], rg[3], fp, lp);
+  if (threadIdx.x < VM_BINS) {
+    wt[threadIdx.x] = __fsub_rn(vm_edge(ft, lt, threadIdx.x + 1), vm_edge(ft, lt, threadIdx.x));
+    wp[threadIdx.x] = __fsub_rn(vm_edge(fp, lp, threadIdx.x + 1), vm_edge(fp, lp, threadIdx.x));
+  }
+  __syncthreads();
+  const unsigned* cj = c + 2 * VM_BINS;
+  auto dens = [&](int i, int j) { return (((double)cj[i * VM_BINS + j] / (double)wt[i]) / (double)wp[j]) / (double)S; };
+  if (threadIdx.x < VM_BINS) {
+    double a = 0.0;
+    for (int j = 0; j < VM_BINS; ++j) a += dens(threadIdx.x, j);
+    rowsum[threadIdx.x] = a;
+  } else if (threadIdx.x >= 128 && threadIdx.x < 128 + VM_BINS) {
+    const int j = threadIdx.x - 128;
+    double a = 0.0;
+    for (int i = 0; i < VM_BINS; ++i) a += dens(i, j);
+    colsum[j] = a;
+  }
+  __syncthreads();
+  double tr = 0.0, tc = 0.0, tj = 0.0;
+  if (threadIdx.x < VM_BINS) { tr = rowsum[threadIdx.x]; tc = colsum[threadIdx.x]; }
+  for (int e = threadIdx.x; e < VM_BINS * VM_BINS; e += VM_THREADS) tj += dens(e / VM_BINS, e % VM_BINS);
+  const double Tr = vm_block_sum(tr, sh), Tc = vm_block_sum(tc, sh), Tj = vm_block_sum(tj, sh);
+  double er = 0.0, ec = 0.0, ej = 0.0;
+  if (threadIdx.x < VM_BINS) { er = vm_entr(rowsum[threadIdx.x] / Tr); ec = vm_entr(colsum[threadIdx.x] / Tc); }
+  for (int e = threadIdx.x; e < VM_BINS * VM_BINS; e += VM_THREADS) ej += vm_entr(dens(e / VM_BINS, e % VM_BINS) / Tj);
+  const double H0 = vm_block_sum(ec, sh), H1 = vm_block_sum(er, sh), H01 = vm_block_sum(ej, sh);
+  nmi = (H0 + H1) / H01;
+}
+
 __global__ __launch_bounds__(VM_THREADS) void vm_final_kernel(int64_t S, int P, int H, int W, int nb_mom,
                                                               const double* mom, int ssim_blocks, const double* ssim_part,
                                                               const unsigned* counts, double* table) {
   __shared__ double sh[VM_THREADS];
-  __shared__ double rowsum[VM_BINS], colsum[VM_BINS];
-  __shared__ float wt[VM_BINS], wp[VM_BINS];
+  __shared__ VmHistShared hs;
   const int n = blockIdx.x;
   const double* m = mom + (size_t)n * nb_mom * VM_MOM;
   double s[3] = {0.0, 0.0, 0.0};
@@ -287,48 +348,253 @@ __global__ __launch_bounds__(VM_THREADS) void vm_final_kernel(int64_t S, int P, 
     a = vm_block_sum(a, sh);
     row[4] = a / ((double)P * (double)(H - 6) * (double)(W - 6));
   }
-  if (counts) {
-    const unsigned* c = counts + (size_t)n * VM_HIST_WORDS;
-    // histogram_chi2: each histogram normalised to sum 1 (the sum is S), 0/0 bins dropped
-    double chi = 0.0;
-    if (threadIdx.x < VM_BINS) {
-      const double g = (double)c[threadIdx.x] / (double)S, q = (double)c[VM_BINS + threadIdx.x] / (double)S;
-      if (g + q != 0.0) chi = (q - g) * (q - g) / (q + g);
-    }
-    row[6] = vm_block_sum(chi, sh);
-    // nmi: np.histogramdd([t, p], bins=100, density=True) = ((count / wt[i]) / wp[j]) / S with float32 widths
-    float ft, lt, fp, lp;
-    vm_outer_edges(rg[0], rg[1], ft, lt);
-    vm_outer_edges(rg[2], rg[3], fp, lp);
-    if (threadIdx.x < VM_BINS) {
-      wt[threadIdx.x] = __fsub_rn(vm_edge(ft, lt, threadIdx.x + 1), vm_edge(ft, lt, threadIdx.x));
-      wp[threadIdx.x] = __fsub_rn(vm_edge(fp, lp, threadIdx.x + 1), vm_edge(fp, lp, threadIdx.x));
-    }
-    __syncthreads();
-    const unsigned* cj = c + 2 * VM_BINS;
-    auto dens = [&](int i, int j) { return (((double)cj[i * VM_BINS + j] / (double)wt[i]) / (double)wp[j]) / (double)S; };
-    if (threadIdx.x < VM_BINS) {
-      double a = 0.0;
-      for (int j = 0; j < VM_BINS; ++j) a += dens(threadIdx.x, j);
-      rowsum[threadIdx.x] = a;
-    } else if (threadIdx.x >= 128 && threadIdx.x < 128 + VM_BINS) {
-      const int j = threadIdx.x - 128;
-      double a = 0.0;
-      for (int i = 0; i < VM_BINS; ++i) a += dens(i, j);
-      colsum[j] = a;
-    }
-    __syncthreads();
-    double tr = 0.0, tc = 0.0, tj = 0.0;
-    if (threadIdx.x < VM_BINS) { tr = rowsum[threadIdx.x]; tc = colsum[threadIdx.x]; }
-    for (int e = threadIdx.x; e < VM_BINS * VM_BINS; e += VM_THREADS) tj += dens(e / VM_BINS, e % VM_BINS);
-    const double Tr = vm_block_sum(tr, sh), Tc = vm_block_sum(tc, sh), Tj = vm_block_sum(tj, sh);
-    double er = 0.0, ec = 0.0, ej = 0.0;
-    if (threadIdx.x < VM_BINS) { er = vm_entr(rowsum[threadIdx.x] / Tr); ec = vm_entr(colsum[threadIdx.x] / Tc); }
-    for (int e = threadIdx.x; e < VM_BINS * VM_BINS; e += VM_THREADS) ej += vm_entr(dens(e / VM_BINS, e % VM_BINS) / Tj);
-    const double H0 = vm_block_sum(ec, sh), H1 = vm_block_sum(er, sh), H01 = vm_block_sum(ej, sh);
-    row[5] = (H0 + H1) / H01;
-  }
+  if (counts) vm_hist_scores(counts + (size_t)n * VM_HIST_WORDS, S, rg, hs, sh, row[5], row[6]);
   if (threadIdx.x < 7) table[(size_t)n * 7 + threadIdx.x] = row[threadIdx.x];
+}
+
+// ---- masked scoring (validator_tester.py:78-98, val_test_metrics.py:19-29,141-149) --------------------------------------
+// One call scores every sample inside L <= VM_MAX_LABELS region masks. What the reference's masked arrays make of each
+// metric is stated at gs_valmetrics_masked in ganslate_hip.h. tm = t*m and pm = p*m exist nowhere in memory: the masks
+// are packed once into one byte per element (bit l = label l, vmm_pack_kernel) and applied where t and p are loaded.
+// Launches (at most five, whatever L is):
+//   0. pack      : L byte masks -> one bit per label
+//   1. moments   : reads t, p and the bits once and keeps, for every label, sum_m |t-p|, sum_m (t-p)^2, sum_m t^2, n,
+//                  Rm = max of t inside the mask, and min / max of tm and pm (the histogram ranges); zeroes the counts
+//   2. ssim      : the unmasked tile body on tm / pm, one workgroup per (tile, label), label fastest, data range Rm
+//   3. histograms: one workgroup per (chunk, label), label fastest. A workgroup's LDS-private joint table is 40 KB, so L
+//                  of them would leave one workgroup per CU at L = 3 and do not fit the CU's 160 KB from L = 4 on; with
+//                  one label per workgroup three workgroups share a CU whatever L is, and the L workgroups of a chunk
+//                  run side by side and share its lines in L2. Masked-out elements all fall into the bin of 0: they are
+//                  counted in a register and added once, not by same-address LDS atomics.
+//   4. finalize  : one workgroup per (sample, label)
+// The wave reductions below use a fixed xor pattern and a fixed order across the four waves: bitwise reproducible.
+#define VM_MAX_LABELS GS_VM_MAX_LABELS
+#define VMM_MOM 10              // slab row per (moments workgroup, label): sum|d|, sum d^2, sum t^2, n, Rm, min tm, max tm,
+                                // min pm, max pm, -
+
+struct VmMaskPtrs { const uint8_t* m[VM_MAX_LABELS]; };
+
+// bit l of out[i] = (masks[l][i] != 0). words = the number of leading 4-byte groups handled a word at a time (0 when a
+// mask is not 4-byte aligned); the bytes after them go one by one.
+__global__ __launch_bounds__(VM_THREADS) void vmm_pack_kernel(VmMaskPtrs mk, int L, int64_t words, int64_t total,
+                                                              uint8_t* out) {
+  const int64_t stride = (int64_t)gridDim.x * VM_THREADS;
+  const int64_t i0 = (int64_t)blockIdx.x * VM_THREADS + threadIdx.x;
+  for (int64_t i = i0; i < words; i += stride) {
+    unsigned r = 0u;
+    for (int l = 0; l < L; ++l) {
+      const unsigned w = reinterpret_cast<const unsigned*>(mk.m[l])[i];
+      r |= (((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u) << l;      // 1 in every non-zero byte
+    }
+    reinterpret_cast<unsigned*>(out)[i] = r;
+  }
+  for (int64_t i = words * 4 + i0; i < total; i += stride) {
+    unsigned r = 0u;
+    for (int l = 0; l < L; ++l) r |= (mk.m[l][i] != 0 ? 1u : 0u) << l;
+    out[i] = (uint8_t)r;
+  }
+}
+
+template <class F>
+__device__ __forceinline__ void vmm_for_chunk(const float* t, const float* p, const uint8_t* m, int64_t b0, int64_t b1,
+                                              bool vec, F&& f) {
+  int64_t i = b0;
+  if (vec) {
+    const int64_t n4 = (b1 - b0) / 4;
+    const float4* t4 = reinterpret_cast<const float4*>(t + b0);
+    const float4* p4 = reinterpret_cast<const float4*>(p + b0);
+    const unsigned* m4 = reinterpret_cast<const unsigned*>(m + b0);
+    for (int64_t k = threadIdx.x; k < n4; k += VM_THREADS) {
+      const float4 a = t4[k], b = p4[k];
+      const unsigned w = m4[k];
+      f(a.x, b.x, w & 255u); f(a.y, b.y, (w >> 8) & 255u); f(a.z, b.z, (w >> 16) & 255u); f(a.w, b.w, w >> 24);
+    }
+    i = b0 + n4 * 4;
+  }
+  for (int64_t k = i + threadIdx.x; k < b1; k += VM_THREADS) f(t[k], p[k], (unsigned)m[k]);
+}
+
+// workgroup reduction of K values at once; bit k of maxbits / minbits makes v[k] a max / a min, otherwise a sum. Xor
+// butterflies inside each wave, then the four waves in index order: the same order every run. Result in every thread.
+template <int K>
+__device__ __forceinline__ void vmm_block_reduce(double (&v)[K], unsigned minbits, unsigned maxbits, double* sh) {
+  auto op = [&](int k, double a, double b) {
+    return ((maxbits >> k) & 1) ? fmax(a, b) : ((minbits >> k) & 1) ? fmin(a, b) : a + b;
+  };
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int o = 32; o > 0; o >>= 1) v[k] = op(k, v[k], __shfl_xor(v[k], o, 64));
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[wave * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = op(k, op(k, op(k, sh[k], sh[K + k]), sh[2 * K + k]), sh[3 * K + k]);
+  __syncthreads();
+}
+
+// {Rm, min tm, max tm, min pm, max pm} of (sample, label) from the masked moment slab `mom` of that sample
+__device__ void vmm_sample_range(const double* mom, int nb, int L, int label, float* out5, double* sh) {
+  double v[5] = {-INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
+  for (int b = threadIdx.x; b < nb; b += VM_THREADS) {
+    const double* r = mom + ((size_t)b * L + label) * VMM_MOM;
+    v[0] = fmax(v[0], r[4]); v[1] = fmin(v[1], r[5]); v[2] = fmax(v[2], r[6]); v[3] = fmin(v[3], r[7]);
+    v[4] = fmax(v[4], r[8]);
+  }
+  vmm_block_reduce<5>(v, 0x0au, 0x15u, sh);
+  for (int q = 0; q < 5; ++q) out5[q] = (float)v[q];
+}
+
+__global__ __launch_bounds__(VM_THREADS) void vmm_moments_kernel(const float* t, const float* p, const uint8_t* bits,
+                                                                 int L, int64_t S, int nb, bool vec, double* mom,
+                                                                 unsigned* counts) {
+  __shared__ double sh[VM_THREADS];
+  const int n = blockIdx.x / nb, b = blockIdx.x % nb;
+  if (counts) {
+    unsigned* c = counts + (size_t)n * L * VM_HIST_WORDS;
+    for (int i = b * VM_THREADS + threadIdx.x; i < L * VM_HIST_WORDS; i += nb * VM_THREADS) c[i] = 0u;
+  }
+  int64_t b0, b1;
+  vm_chunk(S, b, nb, b0, b1);
+  double sad[VM_MAX_LABELS], ssd[VM_MAX_LABELS], stt[VM_MAX_LABELS];
+  unsigned cnt[VM_MAX_LABELS];
+  float rm[VM_MAX_LABELS], tmin[VM_MAX_LABELS], tmax[VM_MAX_LABELS], pmin[VM_MAX_LABELS], pmax[VM_MAX_LABELS];
+#pragma unroll
+  for (int l = 0; l < VM_MAX_LABELS; ++l) {
+    sad[l] = ssd[l] = stt[l] = 0.0; cnt[l] = 0u;
+    rm[l] = -INFINITY; tmin[l] = pmin[l] = INFINITY; tmax[l] = pmax[l] = -INFINITY;
+  }
+  vmm_for_chunk(t + (size_t)n * S, p + (size_t)n * S, bits + (size_t)n * S, b0, b1, vec,
+                [&](float a, float c, unsigned w) {
+    const double d = (double)a - (double)c;
+    const double ad = fabs(d), dd = d * d, aa = (double)a * (double)a;
+#pragma unroll
+    for (int l = 0; l < VM_MAX_LABELS; ++l) {
+      if (l < L) {
+        const bool in = (w >> l) & 1u;
+        sad[l] += in ? ad : 0.0; ssd[l] += in ? dd : 0.0; stt[l] += in ? aa : 0.0;
+        cnt[l] += in ? 1u : 0u;
+        rm[l] = in ? fmaxf(rm[l], a) : rm[l];
+        const float ta = in ? a : 0.f, pa = in ? c : 0.f;
+        tmin[l] = fminf(tmin[l], ta); tmax[l] = fmaxf(tmax[l], ta);
+        pmin[l] = fminf(pmin[l], pa); pmax[l] = fmaxf(pmax[l], pa);
+      }
+    }
+  });
+#pragma unroll
+  for (int l = 0; l < VM_MAX_LABELS; ++l) {
+    if (l < L) {
+      double v[9] = {sad[l], ssd[l], stt[l], (double)cnt[l], (double)rm[l], (double)tmin[l], (double)tmax[l],
+                     (double)pmin[l], (double)pmax[l]};
+      vmm_block_reduce<9>(v, 0x0a0u, 0x150u, sh);
+      if (threadIdx.x == 0) {
+        double* r = mom + ((size_t)blockIdx.x * L + l) * VMM_MOM;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r[k] = v[k];
+        r[9] = 0.0;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(VM_THREADS) void vmm_ssim_kernel(const float* t, const float* p, const uint8_t* bits, int L,
+                                                              int P, int H, int W, int tiles_w, int tiles_h, int nb_mom,
+                                                              const double* mom, double* partial) {
+  __shared__ float st[VM_TH + 6][VM_TW + 6];
+  __shared__ float sp[VM_TH + 6][VM_TW + 6];
+  __shared__ double sh[VM_THREADS];
+  int q = blockIdx.x;
+  const int label = q % L; q /= L;
+  const int tw = q % tiles_w; q /= tiles_w;
+  const int th = q % tiles_h; const int plane = q / tiles_h;
+  const int n = plane / P;
+  float rg[5];
+  vmm_sample_range(mom + (size_t)n * nb_mom * L * VMM_MOM, nb_mom, L, label, rg, sh);
+  const size_t off = (size_t)plane * H * W;
+  const double acc = vm_ssim_tile<true>(t + off, p + off, bits + off, label, H, W, th * VM_TH, tw * VM_TW, (double)rg[0],
+                                        st, sp, sh);
+  // partial[(n, label)][plane of n][tile]: the finalize sums a (sample, label) run in the unmasked order
+  if (threadIdx.x == 0) {
+    const int per = P * tiles_h * tiles_w;
+    partial[((size_t)n * L + label) * per + ((size_t)(plane - n * P) * tiles_h + th) * tiles_w + tw] = acc;
+  }
+}
+
+__global__ __launch_bounds__(VM_THREADS) void vmm_hist_kernel(const float* t, const float* p, const uint8_t* bits, int L,
+                                                              int64_t S, int nb, bool vec, int nb_mom, const double* mom,
+                                                              unsigned* counts) {
+  __shared__ unsigned h[VM_HIST_WORDS];       // [tm bins][pm bins][tm bin * 100 + pm bin]
+  __shared__ float et[VM_BINS + 1], ep[VM_BINS + 1];
+  __shared__ double sh[VM_THREADS];
+  int q = blockIdx.x;
+  const int label = q % L; q /= L;
+  const int n = q / nb, b = q % nb;
+  float rg[5];
+  vmm_sample_range(mom + (size_t)n * nb_mom * L * VMM_MOM, nb_mom, L, label, rg, sh);
+  float ft, lt, fp, lp;
+  vm_outer_edges(rg[1], rg[2], ft, lt);
+  vm_outer_edges(rg[3], rg[4], fp, lp);
+  for (int i = threadIdx.x; i < VM_HIST_WORDS; i += VM_THREADS) h[i] = 0u;
+  if (threadIdx.x <= VM_BINS) { et[threadIdx.x] = vm_edge(ft, lt, threadIdx.x); ep[threadIdx.x] = vm_edge(fp, lp, threadIdx.x); }
+  __syncthreads();
+  const float scale_t = (float)VM_BINS / (lt - ft), scale_p = (float)VM_BINS / (lp - fp);
+  int64_t b0, b1;
+  vm_chunk(S, b, nb, b0, b1);
+  unsigned outside = 0u;
+  vmm_for_chunk(t + (size_t)n * S, p + (size_t)n * S, bits + (size_t)n * S, b0, b1, vec,
+                [&](float a, float c, unsigned w) {
+    if (!((w >> label) & 1u)) { ++outside; return; }
+    const int i = vm_bin(a, et, ft, scale_t), j = vm_bin(c, ep, fp, scale_p);
+    atomicAdd(&h[i], 1u);
+    atomicAdd(&h[VM_BINS + j], 1u);
+    atomicAdd(&h[2 * VM_BINS + i * VM_BINS + j], 1u);
+  });
+  if (outside) {          // tm = pm = 0 there (0 lies inside both ranges, since a masked-out element took part in them)
+    const int i = vm_bin(0.f, et, ft, scale_t), j = vm_bin(0.f, ep, fp, scale_p);
+    atomicAdd(&h[i], outside);
+    atomicAdd(&h[VM_BINS + j], outside);
+    atomicAdd(&h[2 * VM_BINS + i * VM_BINS + j], outside);
+  }
+  __syncthreads();
+  unsigned* out = counts + ((size_t)n * L + label) * VM_HIST_WORDS;
+  for (int i = threadIdx.x; i < VM_HIST_WORDS; i += VM_THREADS)
+    if (h[i]) atomicAdd(&out[i], h[i]);
+}
+
+__global__ __launch_bounds__(VM_THREADS) void vmm_final_kernel(int64_t S, int L, int P, int H, int W, int nb_mom,
+                                                               const double* mom, int ssim_blocks,
+                                                               const double* ssim_part, const unsigned* counts,
+                                                               double* table) {
+  __shared__ double sh[VM_THREADS];
+  __shared__ VmHistShared hs;
+  const int n = blockIdx.x / L, label = blockIdx.x % L;
+  const double* m = mom + (size_t)n * nb_mom * L * VMM_MOM;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nb_mom; b += VM_THREADS)
+    for (int k = 0; k < 4; ++k) s[k] += m[((size_t)b * L + label) * VMM_MOM + k];
+  vmm_block_reduce<4>(s, 0u, 0u, sh);
+  float rg[5];
+  vmm_sample_range(m, nb_mom, L, label, rg, sh);
+  const double nan = __builtin_nan("");
+  double row[7] = {nan, nan, nan, nan, nan, nan, nan};
+  const double sad = s[0], ssd = s[1], stt = s[2], cnt = s[3];       // cnt: a sum of integers below 2^32, exact
+  row[0] = sad / cnt;
+  row[1] = ssd / cnt;
+  row[2] = ssd / stt;
+  const double R = (double)rg[0];
+  row[3] = 10.0 * log10((R * R) / (ssd / (double)S));                // skimage averages over all S elements
+  if (ssim_part) {
+    const double* sp = ssim_part + (size_t)blockIdx.x * ssim_blocks;
+    double a = 0.0;
+    for (int b = threadIdx.x; b < ssim_blocks; b += VM_THREADS) a += sp[b];
+    a = vm_block_sum(a, sh);
+    row[4] = a / ((double)P * (double)(H - 6) * (double)(W - 6));
+  }
+  if (counts) vm_hist_scores(counts + (size_t)blockIdx.x * VM_HIST_WORDS, S, rg + 1, hs, sh, row[5], row[6]);
+  if (threadIdx.x < 7) table[(size_t)blockIdx.x * 7 + threadIdx.x] = cnt > 0.0 ? row[threadIdx.x] : nan;   // empty mask
 }
 
 struct VmPlan {
@@ -378,6 +644,75 @@ extern "C" int gs_valmetrics(const float* t, const float* p, int32_t N, int32_t 
     hipLaunchKernelGGL(vm_hist_kernel, dim3(N * q.nb_hist), dim3(VM_THREADS), 0, st, t, p, q.S, q.nb_hist, vec,
                        q.nb_mom, mom, cnt);
   hipLaunchKernelGGL(vm_final_kernel, dim3(N), dim3(VM_THREADS), 0, st, q.S, P, H, W, q.nb_mom, mom, ssim_blocks,
+                     (flags & GS_VM_SSIM) ? ssim_part : nullptr, cnt, table);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// scratch of the masked call: [masked moment slab][ssim partials][packed mask bits, one byte per element]
+struct VmmPlan {
+  VmPlan q;
+  size_t mom_doubles, ssim_doubles, bit_bytes;
+};
+static VmmPlan vmm_plan(int32_t N, int32_t L, int32_t P, int32_t H, int32_t W) {
+  VmmPlan m;
+  m.q = vm_plan(N, P, H, W);
+  m.mom_doubles = (size_t)N * m.q.nb_mom * L * VMM_MOM;
+  m.ssim_doubles = m.q.ssim_doubles * L;
+  m.bit_bytes = ((size_t)N * m.q.S + 15) / 16 * 16;
+  return m;
+}
+
+extern "C" int64_t gs_valmetric_masked_scratch_bytes(int32_t N, int32_t L, int32_t P, int32_t H, int32_t W) {
+  if (N <= 0 || L <= 0 || L > VM_MAX_LABELS || P <= 0 || H <= 0 || W <= 0) return 0;
+  const VmmPlan m = vmm_plan(N, L, P, H, W);
+  return (int64_t)((m.mom_doubles + m.ssim_doubles) * sizeof(double) + m.bit_bytes);
+}
+
+extern "C" int gs_valmetrics_masked(const float* t, const float* p, const uint8_t* const* masks, int32_t L, int32_t N,
+                                    int32_t P, int32_t H, int32_t W, int32_t flags, double* table, uint32_t* counts,
+                                    void* scratch, void* stream) {
+  GS_REQUIRE(t && p && masks && table && scratch && N > 0 && P > 0 && H > 0 && W > 0 &&
+             (flags & ~(GS_VM_SSIM | GS_VM_HIST)) == 0, "gs_valmetrics_masked: bad argument");
+  GS_REQUIRE(L >= 1 && L <= VM_MAX_LABELS, "gs_valmetrics_masked: between 1 and GS_VM_MAX_LABELS masks per call");
+  GS_REQUIRE(!(flags & GS_VM_SSIM) || (H >= 7 && W >= 7),
+             "gs_valmetrics_masked: SSIM needs H >= 7 and W >= 7 (7x7 window)");
+  GS_REQUIRE(!(flags & GS_VM_HIST) || counts, "gs_valmetrics_masked: histograms need the counts table");
+  const VmmPlan m = vmm_plan(N, L, P, H, W);
+  const VmPlan& q = m.q;
+  GS_REQUIRE(q.S < ((int64_t)1 << 32),
+             "gs_valmetrics_masked: a sample must hold fewer than 2^32 elements (uint32 counts)");
+  VmMaskPtrs mk = {};
+  bool words = true;
+  for (int l = 0; l < L; ++l) {
+    GS_REQUIRE(masks[l], "gs_valmetrics_masked: null mask");
+    mk.m[l] = masks[l];
+    words = words && (reinterpret_cast<uintptr_t>(masks[l]) & 3) == 0;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* mom = static_cast<double*>(scratch);
+  double* ssim_part = mom + m.mom_doubles;
+  uint8_t* bits = reinterpret_cast<uint8_t*>(ssim_part + m.ssim_doubles);
+  unsigned* cnt = (flags & GS_VM_HIST) ? counts : nullptr;
+  const int64_t total = (int64_t)N * q.S;
+  const int64_t nwords = words ? total / 4 : 0;
+  const int64_t pack_items = nwords > 0 ? nwords : total;
+  const int pack_blocks = (int)((pack_items + 4 * VM_THREADS - 1) / (4 * VM_THREADS) < 2048
+                                    ? (pack_items + 4 * VM_THREADS - 1) / (4 * VM_THREADS) : 2048);
+  hipLaunchKernelGGL(vmm_pack_kernel, dim3(pack_blocks), dim3(VM_THREADS), 0, st, mk, L, nwords, total, bits);
+  // the bits of sample n start at n * S: word loads need S % 4 == 0 as the float4 loads do (the base is 8-byte aligned)
+  const bool vec = ((reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(p)) & 15) == 0 && q.S % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(bits) & 3) == 0;
+  hipLaunchKernelGGL(vmm_moments_kernel, dim3(N * q.nb_mom), dim3(VM_THREADS), 0, st, t, p, bits, L, q.S, q.nb_mom, vec,
+                     mom, cnt);
+  const int ssim_blocks = P * q.tiles_w * q.tiles_h;
+  if (flags & GS_VM_SSIM)
+    hipLaunchKernelGGL(vmm_ssim_kernel, dim3(N * ssim_blocks * L), dim3(VM_THREADS), 0, st, t, p, bits, L, P, H, W,
+                       q.tiles_w, q.tiles_h, q.nb_mom, mom, ssim_part);
+  if (flags & GS_VM_HIST)
+    hipLaunchKernelGGL(vmm_hist_kernel, dim3(N * q.nb_hist * L), dim3(VM_THREADS), 0, st, t, p, bits, L, q.S, q.nb_hist,
+                       vec, q.nb_mom, mom, cnt);
+  hipLaunchKernelGGL(vmm_final_kernel, dim3(N * L), dim3(VM_THREADS), 0, st, q.S, L, P, H, W, q.nb_mom, mom, ssim_blocks,
                      (flags & GS_VM_SSIM) ? ssim_part : nullptr, cnt, table);
   GS_CHECK_HIP(hipGetLastError());
   return 0;

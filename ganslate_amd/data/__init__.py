@@ -1,4 +1,5 @@
 from .image_datasets import (PairedImageDataset, PairedImageDatasetConfig, UnpairedImageDataset,  # noqa: F401
                              UnpairedImageDatasetConfig)
-from .synthetic import SyntheticImageDataset, SyntheticImageDatasetConfig  # noqa: F401
+from .synthetic import (SyntheticImageDataset, SyntheticImageDatasetConfig,  # noqa: F401
+                        SyntheticMaskedImageDataset, SyntheticMaskedImageDatasetConfig)
 from .volume_datasets import UnpairedVolumeDataset, UnpairedVolumeDatasetConfig  # noqa: F401

@@ -11,7 +11,10 @@ utils/metrics/val_test_metrics.py that `<mode>.metrics` enables.
 - Model on the CPU (the oracle backend of the test-suite): the host path of mae, mse, nmse and psnr below; ssim, nmi and
   histogram_chi2 are skipped there with a log line.
 
-Batches that carry `masks` are scored without them (masked metrics are out of scope). The Tester writes
+Batches that carry `masks` ({label: tensor of the batch's shape}, as the medical datasets return BODY, GTV, ...) get every
+enabled metric once more per label on the device path, as `<metric>_<label>` (and `Original_<metric>_<label>` with
+`compute_over_input`), between the standard keys and `cycle_SSIM` as validator_tester.py:78-98 orders them. The masks are
+not denormalised; all labels of a batch go through one masked call. The host path ignores masks. The Tester writes
 `<test.output_dir>/test/metrics.csv` when `test.metrics.save_to_csv` is set: one row per sample, one column per metric,
 plus a `dataset` column with `multi_dataset`. Saving generated tensors and the W&B / TensorBoard trackers stay out of
 scope."""
@@ -115,7 +118,8 @@ class BaseValTestEngine(BaseEngineWithInference):
 
     def _log_masks(self, data):
         if "masks" in data and not self._masks_logged:
-            self.logger.info("batches carry `masks`: masked metrics are out of scope, the masks are ignored")
+            self.logger.info("batches carry `masks`: masked metrics are computed on the device path only; the host "
+                             "path ignores the masks")
             self._masks_logged = True
 
     def _host_rows(self, loader, denormalize, over_input):
@@ -144,8 +148,8 @@ class BaseValTestEngine(BaseEngineWithInference):
         """per-batch device tables, one host copy per dataset (validator_tester.py:62-112)"""
         m = self.metricizer
         tables, originals, cycles = [], [], []
+        labels, masked, masked_originals = None, [], []
         for data in loader:
-            self._log_masks(data)
             real_A = data["A"].to(self.model.device)
             with torch.no_grad():
                 fake_B = self.infer(real_A)
@@ -158,6 +162,18 @@ class BaseValTestEngine(BaseEngineWithInference):
                 tables.append(m.table(pred, target))
                 if over_input:
                     originals.append(m.table(original, target))
+                if "masks" in data:
+                    if labels is None:
+                        labels = list(data["masks"])
+                    if list(data["masks"]) != labels or len(masked) != len(tables) - 1:
+                        raise ValueError(f"every batch of a dataset must carry the same mask labels; got "
+                                         f"{list(data['masks'])} after {labels}")
+                    masks = [data["masks"][k].to(self.model.device) for k in labels]
+                    masked.append(m.masked_table(pred, target, masks))
+                    if over_input:
+                        masked_originals.append(m.masked_table(original, target, masks))
+                elif labels is not None:
+                    raise ValueError(f"every batch of a dataset must carry the same mask labels; got none after {labels}")
                 if self.cycle:
                     rec_A = self.infer(fake_B, direction="BA")
                     cycles.append(m.cycle_table(rec_A, real_A))
@@ -166,6 +182,14 @@ class BaseValTestEngine(BaseEngineWithInference):
         cols = m.to_lists(torch.cat(tables))
         if over_input:
             cols.update(m.to_lists(torch.cat(originals), prefix="Original_"))
+        if labels:
+            # one copy of the [samples, L, 7] table(s); per label the masked keys, then the Original_ ones (:84-95)
+            by_label = torch.cat(masked).cpu().transpose(0, 1)
+            by_label_original = torch.cat(masked_originals).cpu().transpose(0, 1) if over_input else None
+            for i, label in enumerate(labels):
+                cols.update({f"{k}_{label}": v for k, v in m.to_lists(by_label[i]).items()})
+                if over_input:
+                    cols.update({f"Original_{k}_{label}": v for k, v in m.to_lists(by_label_original[i]).items()})
         if self.cycle:
             cols["cycle_SSIM"] = torch.cat(cycles).cpu().tolist()
         n = len(next(iter(cols.values()))) if cols else 0

@@ -11,6 +11,7 @@ BORDER = {"zero": 0, "reflect": 1, "replicate": 2}
 ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
 VM_FLAGS = {"ssim": 1, "hist": 2}     # GS_VM_SSIM, GS_VM_HIST
 VM_BINS = 100
+VM_MAX_LABELS = 8                       # GS_VM_MAX_LABELS
 
 
 class GConvDesc(C.Structure):
@@ -224,6 +225,9 @@ _PROTOS = {
     "gs_valmetrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_valmetric_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gs_valmetrics_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_valmetric_masked_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gs_patchnce_param_floats": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_work_bytes": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_forward": (C.c_int, [C.POINTER(PatchNCEDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,

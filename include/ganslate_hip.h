@@ -504,6 +504,36 @@ int gs_valmetrics(const float* t, const float* p, int32_t N, int32_t P, int32_t 
                   double* table, uint32_t* counts, void* scratch, void* stream);
 int64_t gs_valmetric_scratch_bytes(int32_t N, int32_t P, int32_t H, int32_t W);
 
+/* ---- the same metrics inside region masks (ganslate/engines/validator_tester.py:78-98,
+ *      utils/metrics/val_test_metrics.py:19-29 create_masked_array, :141-149 get_metrics(mask=...)) ----
+ * The reference scores np.ma.masked_array(x * m, mask=~m) with m = mask.astype(bool); some of the numpy / scipy /
+ * scikit-image calls behind the seven metrics honour the mask and others strip it (np.asarray). Per sample, with m in
+ * {0, 1}, n = sum(m), S = P*H*W, tm = t*m, pm = p*m and Rm = the maximum of t over the elements with m != 0 (not max(tm):
+ * they differ when every target value inside the mask is negative):
+ *   mae  = sum_m |t-p| / n          mse = sum_m (t-p)^2 / n          nmse = sum_m (t-p)^2 / sum_m t^2
+ *          (np.mean, np.linalg.norm and .max() run over the unmasked elements; checked against numpy)
+ *   psnr = 10 log10(Rm^2 / (sum_m (t-p)^2 / S)): divisor S, not n, because scikit-image converts with np.asarray and
+ *          averages over every element
+ *   ssim = the plane-wise 7x7 SSIM of gs_valmetrics of tm against pm over all planes, data range Rm
+ *          (scipy.ndimage.uniform_filter sees x*m)
+ *   nmi, histogram_chi2 = from the 100-bin histograms of tm and pm over all S elements: masked-out elements count as
+ *          zeros, so the ranges are those of tm / pm (np.histogram and np.histogramdd see x*m; checked against numpy)
+ * The psnr and ssim rows are read from scikit-image's source (_as_floats, mean_squared_error, structural_similarity) and
+ * are not pinned against an installed scikit-image, as the unmasked ssim is not.
+ * Definitions of this library: n == 0 gives NaN in every column of that row (the reference yields numpy's masked
+ * constant); a mask has exactly the shape of the sample batch (the reference raises MaskError otherwise); any non-zero
+ * mask byte means "inside".
+ * masks = host array of L (1..GS_VM_MAX_LABELS) device pointers, each to N*P*H*W bytes laid out like t. table = device
+ * [N][L][7] fp64 in the column order of gs_valmetrics; counts (needed with GS_VM_HIST) = device [N][L][2*100 + 100*100]
+ * uint32, left holding the raw bin counts of tm and pm. t*m and p*m are never written to memory: one launch packs the
+ * masks into a bit per label and the passes apply them on load. At most five launches whatever L is; t and p are read
+ * once for all labels by the moments pass. No float atomics: tables are bitwise reproducible. */
+#define GS_VM_MAX_LABELS 8
+int gs_valmetrics_masked(const float* t, const float* p, const uint8_t* const* masks, int32_t L, int32_t N, int32_t P,
+                         int32_t H, int32_t W, int32_t flags, double* table, uint32_t* counts, void* scratch,
+                         void* stream);
+int64_t gs_valmetric_masked_scratch_bytes(int32_t N, int32_t L, int32_t P, int32_t H, int32_t W);
+
 /* ---- PatchNCE + patch MLP of CUT (ganslate/nn/gans/unpaired/cut.py:229-294, ganslate/nn/losses/cut_losses.py:14-43) ----
  * For every feature level l: sampled patches xq[l], xk[l] are [batch*patches][channels[l]] fp32 (target = query, source =
  * key, row = image * patches + patch); FeaturePatchMLP level l = Linear(C_l, nc) - ReLU - Linear(nc, nc) - x/(||x||+1e-7);

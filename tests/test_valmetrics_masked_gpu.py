@@ -1,0 +1,207 @@
+"""Masked device validation / test metrics (valmetrics.hip through HipOps.valmetrics_masked and utils/val_metrics.py)
+against the float64 restatement of the reference's masked arrays (tests/valmetrics_masked_ref.py), and the GPU
+Validator / Tester reporting `<metric>_<label>` for datasets that yield masks. Tolerances are those of
+tests/test_valmetrics_gpu.py, for its reasons: fp64 accumulation in another order than numpy's (rel 1e-9), SSIM window
+sums of float32 products against cumulative sums (abs 1e-5), bin counts exact."""
+import csv
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from tests import valmetrics_masked_ref as mref
+from tests import valmetrics_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(2, 3, 256, 256), (1, 1, 155, 240, 240), (3, 1, 16, 24, 20), (1, 3, 7, 7), (2, 1, 9, 300)]
+KINDS = ["uniform", "ct", "int", "constant"]
+CONFIGS = Path(__file__).parent / "configs"
+SCALARS = ("mae", "mse", "nmse", "psnr", "nmi", "histogram_chi2")
+
+
+def _data(shape, kind, seed=0):
+    rng = np.random.default_rng(seed)
+    if kind == "uniform":
+        t = rng.uniform(-1, 1, shape)
+        p = np.clip(t + rng.normal(0, 0.2, shape), -1, 1)
+    elif kind == "ct":                  # denormalised CT-like values with a flat region (air / water)
+        t = rng.uniform(-1000, 3000, shape)
+        t[..., : shape[-2] // 2, : shape[-1] // 2] = 40.0
+        p = t + rng.normal(0, 60, shape)
+    elif kind == "int":                 # many values exactly on bin edges
+        t = rng.integers(0, 101, shape)
+        p = np.clip(t + rng.integers(-3, 4, shape), 0, 100)
+    else:                               # one constant target sample: histogram range [c - 0.5, c + 0.5]
+        t = rng.uniform(-1, 1, shape)
+        p = rng.uniform(-1, 1, shape)
+        t[0] = 0.25
+    return t.astype(np.float32), p.astype(np.float32)
+
+
+def _masks(shape, seed=1):
+    """a box over the middle half of every spatial axis (every channel), a random 40 % mask, and all ones"""
+    rng = np.random.default_rng(seed)
+    box = np.zeros(shape, dtype=bool)
+    box[(slice(None), slice(None)) + tuple(slice(s // 4, max(s // 4 + 1, 3 * s // 4)) for s in shape[2:])] = True
+    return [box, rng.random(shape) < 0.4, np.ones(shape, dtype=bool)]
+
+
+def _cuda(*arrays):
+    return [torch.from_numpy(a).cuda() for a in arrays]
+
+
+def _check_row(got_row, want, where):
+    got = dict(zip(ref.COLUMNS, got_row))
+    for k in SCALARS:
+        assert got[k] == pytest.approx(want[k], rel=1e-9, abs=0), (where, k)
+    assert abs(got["ssim"] - want["ssim"]) <= 1e-5, (where, got["ssim"], want["ssim"])
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_masked_device_metrics_match_the_restatement(hip_ops, shape, kind):
+    t, p = _data(shape, kind)
+    masks = _masks(shape)
+    td, pd = _cuda(t, p)
+    table, counts = hip_ops.valmetrics_masked(td, pd, _cuda(*masks), return_counts=True)
+    table = table.cpu().numpy()
+    ht, hp, hj = (c.cpu().numpy() for c in counts)
+    assert table.shape == (shape[0], 3, 7)
+    for i in range(shape[0]):
+        for l, m in enumerate(masks):
+            assert m[i].any()
+            _check_row(table[i, l], mref.metrics(t[i], p[i], m[i]), (i, l))
+            wt, wp, wj = mref.bin_counts(t[i], p[i], m[i])
+            np.testing.assert_array_equal(ht[i, l], wt)
+            np.testing.assert_array_equal(hp[i, l], wp)
+            np.testing.assert_array_equal(hj[i, l], wj)
+    # the all-ones label is the unmasked call
+    plain, (ut, up, uj) = hip_ops.valmetrics(td, pd, return_counts=True)
+    plain = plain.cpu().numpy()
+    for i in range(shape[0]):
+        _check_row(table[i, 2], dict(zip(ref.COLUMNS, plain[i])), (i, "all ones"))
+    np.testing.assert_array_equal(ht[:, 2], ut.cpu().numpy())
+    np.testing.assert_array_equal(hp[:, 2], up.cpu().numpy())
+    np.testing.assert_array_equal(hj[:, 2], uj.cpu().numpy())
+
+
+@pytest.mark.parametrize("dtype", [torch.bool, torch.uint8, torch.float32])
+def test_mask_dtypes_and_negative_targets_inside(hip_ops, dtype):
+    """bool, uint8 and float masks mean the same (non-zero = inside; 0.5 and 255 count as inside), and a mask whose
+    inside holds only negative targets uses Rm < 0, not max(t * m) = 0"""
+    shape = (2, 1, 9, 300)
+    t, p = _data(shape, "uniform", seed=4)
+    box = _masks(shape)[0]
+    t[box] = -np.abs(t[box]) - 0.5
+    mask = torch.from_numpy(box).cuda()
+    mask = mask if dtype is torch.bool else mask.to(dtype) * (255 if dtype is torch.uint8 else 0.5)
+    table = hip_ops.valmetrics_masked(*_cuda(t, p), [mask]).cpu().numpy()
+    for i in range(shape[0]):
+        assert mref.masked_max(t[i], box[i]) < 0
+        _check_row(table[i, 0], mref.metrics(t[i], p[i], box[i]), i)
+
+
+def test_an_empty_mask_gives_a_nan_row_and_leaves_the_others(hip_ops):
+    shape = (2, 3, 256, 256)
+    t, p = _data(shape, "ct", seed=2)
+    box, rnd, _ = _masks(shape)
+    empty = np.zeros(shape, dtype=bool)
+    empty[1, 0, 3, 5] = True                        # empty for sample 0 only
+    td, pd = _cuda(t, p)
+    got = hip_ops.valmetrics_masked(td, pd, _cuda(box, empty, rnd)).cpu()
+    alone = hip_ops.valmetrics_masked(td, pd, _cuda(box, rnd)).cpu()
+    assert torch.isnan(got[0, 1]).all()
+    assert torch.equal(got[:, [0, 2]].contiguous().view(torch.int64), alone.view(torch.int64))
+    got = got.numpy()
+    # sample 1 of that label holds one element: mae, mse, nmse of it; one 7x7 window is not all of them
+    want = mref.metrics(t[1], p[1], empty[1])
+    for k in ("mae", "mse", "nmse", "psnr"):
+        assert dict(zip(ref.COLUMNS, got[1, 1]))[k] == pytest.approx(want[k], rel=1e-9, abs=0), k
+
+
+def test_masked_tables_are_bitwise_reproducible_and_flags_launch_only_what_is_asked(hip_ops):
+    shape = (1, 1, 155, 240, 240)
+    t, p = _cuda(*_data(shape, "ct", seed=3))
+    masks = _cuda(*_masks(shape))
+    a = hip_ops.valmetrics_masked(t, p, masks).cpu()
+    b = hip_ops.valmetrics_masked(t, p, masks).cpu()
+    assert torch.equal(a.view(torch.int64), b.view(torch.int64))
+    assert not torch.isnan(a).any()
+    only = hip_ops.valmetrics_masked(t, p, masks, ssim=False, hist=False).cpu()
+    assert torch.isnan(only[..., 4:]).all()
+    assert torch.equal(only[..., :4].contiguous().view(torch.int64), a[..., :4].contiguous().view(torch.int64))
+
+
+def test_a_mask_of_another_shape_raises(hip_ops):
+    t = torch.zeros(2, 1, 9, 30, device="cuda")
+    for bad in (torch.ones(1, 1, 9, 30), torch.ones(2, 1, 9, 1), torch.ones(2, 9, 30), torch.ones(2, 1, 30, 9)):
+        with pytest.raises(ValueError):
+            hip_ops.valmetrics_masked(t + 1, t, [torch.ones(2, 1, 9, 30).cuda(), bad.cuda()])
+    with pytest.raises(ValueError):
+        hip_ops.valmetrics_masked(t + 1, t, [])
+    with pytest.raises(ValueError):
+        hip_ops.valmetrics_masked(t + 1, t, [torch.ones_like(t)] * 9)
+
+
+def test_gpu_validation_and_test_report_every_metric_per_mask_label(hip_ops, tmp_path):
+    """Validator on the device with a dataset that yields masks (validator_tester.py:78-98): `<metric>_<label>` for every
+    enabled metric and label, equal to the mean of valmetrics_masked over the recorded predictions; the unmasked keys are
+    those of the same model on SyntheticImageDataset with the same seed. Then the Tester's metrics.csv columns."""
+    from ganslate_amd.engines import init_engine
+    from ganslate_amd.engines.validator import Validator
+    from ganslate_amd.utils.builders import build_conf
+    config = CONFIGS / "cyclegan3d_masked_synthetic.yaml"
+    tr = init_engine("train", [f"config={config}", f"train.output_dir={tmp_path}", f"val.output_dir={tmp_path}",
+                               "train.seed=7", "train.checkpointing.freq=2"])
+    tr.run()
+    labels = ["BODY", "GTV"]
+    order = ["ssim", "mse", "nmse", "psnr", "mae", "nmi", "histogram_chi2"]
+    keys = order + [f"{k}_{label}" for label in labels for k in order] + ["cycle_SSIM"]
+    assert [h[0] for h in tr.validator.history] == [2, 4]
+    assert all(list(m) == keys for _, _, m in tr.validator.history)
+
+    v = tr.validator
+    seen = []
+    infer = v.infer
+    v.infer = lambda x, *a, **k: (lambda y: (seen.append((k.get("direction", "AB"), y.float())), y)[1])(infer(x, *a, **k))
+    v.run(current_idx=5)
+    v.infer = infer
+    _, _, mean = v.history[-1]
+    loader = next(iter(v.data_loaders.values()))
+    rows = []
+    for (_, fake_B), data in zip([s for s in seen if s[0] == "AB"], loader):
+        masks = [data["masks"][k].cuda() for k in labels]
+        rows.append(hip_ops.valmetrics_masked(data["B"].cuda().float(), fake_B, masks).cpu())
+    rows = torch.cat(rows).numpy()
+    assert rows.shape == (3, 2, 7) and np.isfinite(rows).all()
+    for l, label in enumerate(labels):
+        for c, k in enumerate(ref.COLUMNS):
+            assert mean[f"{k}_{label}"] == pytest.approx(float(np.mean(rows[:, l, c])), rel=1e-12, abs=0), (k, label)
+            assert mean[f"{k}_{label}"] != mean[k]
+
+    plain = build_conf([f"config={CONFIGS / 'cyclegan3d_val_synthetic.yaml'}", f"train.output_dir={tmp_path}",
+                        f"val.output_dir={tmp_path}", "val.batch_size=2", "val.dataset.length=3", "val.metrics.ssim=true",
+                        "val.metrics.nmi=true", "val.metrics.histogram_chi2=true"])
+    pv = Validator(plain, tr.model)
+    pv.run(current_idx=5)
+    _, _, plain_mean = pv.history[-1]
+    assert list(plain_mean) == order + ["cycle_SSIM"]
+    assert plain_mean == {k: mean[k] for k in plain_mean}
+
+    te = init_engine("test", [f"config={config}", f"train.output_dir={tmp_path / 'elsewhere'}",
+                              f"test.output_dir={tmp_path}", "test.checkpointing.load_iter=2",
+                              "test.metrics.compute_over_input=true"])
+    assert te.on_device
+    te.run()
+    with open(tmp_path / "test" / "metrics.csv", newline="") as f:
+        got = list(csv.DictReader(f))
+    assert len(got) == 3
+    names = ["ssim", "mse", "nmse", "psnr", "mae"]                                  # TestMetricsConfig defaults
+    want = names + [f"Original_{k}" for k in names]
+    for label in labels:
+        want += [f"{k}_{label}" for k in names] + [f"Original_{k}_{label}" for k in names]
+    assert list(got[0]) == ["sample"] + want
+    assert all(np.isfinite(float(r[k])) for r in got for k in r)
+    assert all(r[f"mae_{label}"] != r["mae"] for r in got for label in labels)
