@@ -46,47 +46,10 @@ float* gs_reduce_workspace(void* stream) {
 
 namespace {
 struct OptDef { const char* name; int value; };
-OptDef g_opts[GS_OPT_COUNT] = {
-    {"splitk", 1},              // split-K for launches with few output tiles and a long K loop (gconv.hip)
-    {"splitk_max_blocks", 128}, // ... only below this many output tiles
-    {"splitk_target", 256},     // ... aiming at this many workgroups
-    {"hconv", 1},               // halo-resident forward kernel for narrow stride-1 layers (hconv.hip)
-    {"hconv_wide", 1},          // halo-resident forward kernel for the wide 3x3 layers (hconvw.hip)
-    {"hwgrad", 1},              // halo-resident weight-gradient kernels (hwgrad.hip)
-    {"hwgrad_wide", 1},         // ... the wide 3x3 form
-    {"hwgrad_planes", 1},       // ... 3x3x3 layers as three depth planes of it
-    {"norm_bwd_ppb", 0},        // pixels per workgroup of the norm-backward reduction (0 = heuristic; tuning aid)
-    {"norm_apply_unroll", 4},   // elements per thread of the norm-backward apply pass (tuning aid)
-    {"gconv_tile288", 1},       // 288-pixel im2col tiles where they make exactly one round of workgroups (else 320)
-    {"gconv_multi", 1},         // the parity classes of a stride-2 transposed conv / data gradient as one launch
-    {"hconvw_ring", 1},         // fused data gradient of the reflect-padded wide 3x3 layers on the unpadded domain (hconvw.hip RING)
-    {"hconvt", 192},            // halo-resident kernel for the four parity classes of a stride-2 layer in one pass (hconvt.hip):
-                                // smallest grid (boxes x channel tiles x batch) it takes, 0 = off
-    {"hstrip", 1024},           // halo-resident kernel for the W-folded k7 boundary convs (hstrip.hip): smallest grid, 0 = off
-    {"wfold_rows", 1},          // row-staged forms of the four W-fold boundary transforms (wfold.hip) instead of one thread per pixel
-    {"hwgrad_ft", 1},           // halo-resident weight gradient of narrow layers with few taps (hwgrad.hip: the 2-D k7 boundary convs)
-    {"gconv_big", 192},         // smallest number of 256 x 128 im2col tiles that selects them (one workgroup per CU) over 128 x 128 (two)
-    {"hconv_box8", 1},          // hconv.hip: 8 x 8 x 8 boxes on 8 waves for volumes (4 x 8 x 8 on 4 waves otherwise)
-    {"hconvw_persist", 1},      // hconvw.hip: launches with more tiles than CUs run ceil(tiles / CUs) tiles per workgroup (0: one each)
-    {"hstrip_regs", 1},         // hstrip.hip: persistent form with the weights in registers for the k7 boundary convs (0: one tile per workgroup)
-    {"gconv_twin", 1},          // gconv.hip: twin batches on the im2col kernel as one launch (0: the two halves as two launches)
-    {"wgrad_twin", 1},          // wgrad.hip: twin batches on the im2col weight-gradient kernel as one launch (0: two launches)
-    {"gconv_persist", 16},      // pconv.hip: 256 x 128 im2col launches with more tiles than CUs and at most this many K-steps run as
-                                // persistent workgroups (the K-step stream continues across tiles); 0 = off
-    {"hconvt_persist", 1},      // hconvt.hip: launches with more tiles than CUs run as persistent workgroups (0: one tile each)
-    {"wgrad_rows", 1},          // wgrad.hip: the im2col weight gradient stores whole tile rows through LDS; one split adds without atomics
-    {"splitk_multi", 1},        // gconv.hip: split-K over the merged parity classes of a small stride-2 layer (one launch + one finalize)
-    {"splitk_ring", 1},         // gconv.hip: split-K launches of the 128 x 128 tile run a 4-stage ring (three K-steps of cold weights in flight)
-    {"gconv_ring4", 16},        // gconv.hip: 128-pixel im2col tiles in a grid of <= 2 workgroups per CU with at least this many K-steps run a 4-stage ring; 0 = off
-    {"hconv5", 64},             // hconv5.hip: register-resident-weights kernel for the 16 -> 16 channel k5 volume convs; smallest volume
-                                // (batch x voxels / 2048) it takes (0 = off)
-    {"hconv5_seg", 0},          // ... z segments per column (0 = as many as fill the chip; tests force long segments with 1 / 2)
-    {"hwgrad2", 2},             // hwgrad.hip: double-buffered, decode-once form of the narrow volume weight gradient with 65..128 taps
-                                // (>= 2: also for layers wide on both sides, 33..64 x 17..64 channels, instead of the im2col kernel)
-    {"hconv2", 4},              // hconv.hip: persistent double-buffered form of the narrow volume forward / data-gradient kernel (17..64 output channels;
-                                // >= 2: also 64 -> 64 channels — wide on both sides — instead of the split-K im2col launch + its finalize;
-                                // >= 3: 32-channel layers on <= 128 boxes as two 16-channel groups per box; >= 4: 64-channel layers on <= 64 boxes as four)
-    {"pwise", 8},               // pwise.hip: register-operand kernels for one-tap layers with <= 8 channels on one side (smallest volume in 2048-voxel units, 0 = off)
+OptDef g_opts[GS_OPT_COUNT] = {       // one entry per row of GS_OPTIONS (common.hpp), in the enum's order by construction
+#define GS_OPT_DEF(id, name, def) {name, def},
+    GS_OPTIONS(GS_OPT_DEF)
+#undef GS_OPT_DEF
 };
 }  // namespace
 int gs_opt(int id) { return g_opts[id].value; }

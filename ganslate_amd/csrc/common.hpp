@@ -191,11 +191,55 @@ __device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v,
 }
 
 
-// kernel-selection switches (api.hip; set through gs_set_option, never read from the environment by the library)
+// kernel-selection switches (set through gs_set_option, never read from the environment by the library).
+// THE list: X(id suffix, option name, default), one row per option. enum GsOpt below and g_opts[] in api.hip are both
+// generated from it, so an id and its name / default cannot drift apart; ganslate_amd/switches.py holds the same names
+// with the environment variable that drives each (tests/test_abi_cpu.py compares the two sets).
+#define GS_OPTIONS(X) \
+  X(SPLITK, "splitk", 1)                       /* split-K for launches with few output tiles and a long K loop (gconv.hip) */ \
+  X(SPLITK_MAX_BLOCKS, "splitk_max_blocks", 128) /* ... only below this many output tiles */ \
+  X(SPLITK_TARGET, "splitk_target", 256)       /* ... aiming at this many workgroups */ \
+  X(HCONV, "hconv", 1)                         /* halo-resident forward kernel for narrow stride-1 layers (hconv.hip) */ \
+  X(HCONV_WIDE, "hconv_wide", 1)               /* halo-resident forward kernel for the wide 3x3 layers (hconvw.hip) */ \
+  X(HWGRAD, "hwgrad", 1)                       /* halo-resident weight-gradient kernels (hwgrad.hip) */ \
+  X(HWGRAD_WIDE, "hwgrad_wide", 1)             /* ... the wide 3x3 form */ \
+  X(HWGRAD_PLANES, "hwgrad_planes", 1)         /* ... 3x3x3 layers as three depth planes of it */ \
+  X(NORM_BWD_PPB, "norm_bwd_ppb", 0)           /* pixels per workgroup of the norm-backward reduction (0 = heuristic; tuning aid) */ \
+  X(NORM_APPLY_UNROLL, "norm_apply_unroll", 4) /* elements per thread of the norm-backward apply pass (tuning aid) */ \
+  X(GCONV_TILE288, "gconv_tile288", 1)         /* 288-pixel im2col tiles where they make exactly one round of workgroups (else 320) */ \
+  X(GCONV_MULTI, "gconv_multi", 1)             /* the parity classes of a stride-2 transposed conv / data gradient as one launch */ \
+  X(HCONVW_RING, "hconvw_ring", 1)             /* fused data gradient of the reflect-padded wide 3x3 layers on the unpadded domain (hconvw.hip RING) */ \
+  X(HCONVT, "hconvt", 192)                     /* halo-resident kernel for the four parity classes of a stride-2 layer in one pass (hconvt.hip): */ \
+                                               /* smallest grid (boxes x channel tiles x batch) it takes, 0 = off */ \
+  X(HSTRIP, "hstrip", 1024)                    /* halo-resident kernel for the W-folded k7 boundary convs (hstrip.hip): smallest grid, 0 = off */ \
+  X(WFOLD_ROWS, "wfold_rows", 1)               /* row-staged forms of the four W-fold boundary transforms (wfold.hip) instead of one thread per pixel */ \
+  X(HWGRAD_FT, "hwgrad_ft", 1)                 /* halo-resident weight gradient of narrow layers with few taps (hwgrad.hip: the 2-D k7 boundary convs) */ \
+  X(GCONV_BIG, "gconv_big", 192)               /* smallest number of 256 x 128 im2col tiles that selects them (one workgroup per CU) over 128 x 128 (two) */ \
+  X(HCONV_BOX8, "hconv_box8", 1)               /* hconv.hip: 8 x 8 x 8 boxes on 8 waves for volumes (4 x 8 x 8 on 4 waves otherwise) */ \
+  X(HCONVW_PERSIST, "hconvw_persist", 1)       /* hconvw.hip: launches with more tiles than CUs run ceil(tiles / CUs) tiles per workgroup (0: one each) */ \
+  X(HSTRIP_REGS, "hstrip_regs", 1)             /* hstrip.hip: persistent form with the weights in registers for the k7 boundary convs (0: one tile per workgroup) */ \
+  X(GCONV_TWIN, "gconv_twin", 1)               /* gconv.hip: twin batches on the im2col kernel as one launch (0: the two halves as two launches) */ \
+  X(WGRAD_TWIN, "wgrad_twin", 1)               /* wgrad.hip: twin batches on the im2col weight-gradient kernel as one launch (0: two launches) */ \
+  X(GCONV_PERSIST, "gconv_persist", 16)        /* pconv.hip: 256 x 128 im2col launches with more tiles than CUs and at most this many K-steps run as */ \
+                                               /* persistent workgroups (the K-step stream continues across tiles); 0 = off */ \
+  X(HCONVT_PERSIST, "hconvt_persist", 1)       /* hconvt.hip: launches with more tiles than CUs run as persistent workgroups (0: one tile each) */ \
+  X(WGRAD_ROWS, "wgrad_rows", 1)               /* wgrad.hip: the im2col weight gradient stores whole tile rows through LDS; one split adds without atomics */ \
+  X(SPLITK_MULTI, "splitk_multi", 1)           /* gconv.hip: split-K over the merged parity classes of a small stride-2 layer (one launch + one finalize) */ \
+  X(SPLITK_RING, "splitk_ring", 1)             /* gconv.hip: split-K launches of the 128 x 128 tile run a 4-stage ring (three K-steps of cold weights in flight) */ \
+  X(GCONV_RING4, "gconv_ring4", 16)            /* gconv.hip: 128-pixel im2col tiles in a grid of <= 2 workgroups per CU with at least this many K-steps run a 4-stage ring; 0 = off */ \
+  X(HCONV5, "hconv5", 64)                      /* hconv5.hip: register-resident-weights kernel for the 16 -> 16 channel k5 volume convs; smallest volume */ \
+                                               /* (batch x voxels / 2048) it takes (0 = off) */ \
+  X(HCONV5_SEG, "hconv5_seg", 0)               /* ... z segments per column (0 = as many as fill the chip; tests force long segments with 1 / 2) */ \
+  X(HWGRAD2, "hwgrad2", 2)                     /* hwgrad.hip: double-buffered, decode-once form of the narrow volume weight gradient with 65..128 taps */ \
+                                               /* (>= 2: also for layers wide on both sides, 33..64 x 17..64 channels, instead of the im2col kernel) */ \
+  X(HCONV2, "hconv2", 4)                       /* hconv.hip: persistent double-buffered form of the narrow volume forward / data-gradient kernel (17..64 output channels; */ \
+                                               /* >= 2: also 64 -> 64 channels — wide on both sides — instead of the split-K im2col launch + its finalize; */ \
+                                               /* >= 3: 32-channel layers on <= 128 boxes as two 16-channel groups per box; >= 4: 64-channel layers on <= 64 boxes as four) */ \
+  X(PWISE, "pwise", 8)                         /* pwise.hip: register-operand kernels for one-tap layers with <= 8 channels on one side (smallest volume in 2048-voxel units, 0 = off) */
 enum GsOpt {
-  GS_OPT_SPLITK, GS_OPT_SPLITK_MAX_BLOCKS, GS_OPT_SPLITK_TARGET, GS_OPT_HCONV, GS_OPT_HCONV_WIDE,
-  GS_OPT_HWGRAD, GS_OPT_HWGRAD_WIDE, GS_OPT_HWGRAD_PLANES, GS_OPT_NORM_BWD_PPB, GS_OPT_NORM_APPLY_UNROLL,
-  GS_OPT_GCONV_TILE288, GS_OPT_GCONV_MULTI, GS_OPT_HCONVW_RING, GS_OPT_HCONVT, GS_OPT_HSTRIP, GS_OPT_WFOLD_ROWS, GS_OPT_HWGRAD_FT, GS_OPT_GCONV_BIG, GS_OPT_HCONV_BOX8, GS_OPT_HCONVW_PERSIST, GS_OPT_HSTRIP_REGS, GS_OPT_GCONV_TWIN, GS_OPT_WGRAD_TWIN, GS_OPT_GCONV_PERSIST, GS_OPT_HCONVT_PERSIST, GS_OPT_WGRAD_ROWS, GS_OPT_SPLITK_MULTI, GS_OPT_SPLITK_RING, GS_OPT_GCONV_RING4, GS_OPT_HCONV5, GS_OPT_HCONV5_SEG, GS_OPT_HWGRAD2, GS_OPT_HCONV2, GS_OPT_PWISE,
+#define GS_OPT_ENUM(id, name, def) GS_OPT_##id,
+  GS_OPTIONS(GS_OPT_ENUM)
+#undef GS_OPT_ENUM
   GS_OPT_COUNT
 };
 int gs_opt(int id);

@@ -1,13 +1,14 @@
 """Tensor-level wrappers over the C ABI (include/ganslate_hip.h). Every call enqueues on torch's current
 stream; tensors are device tensors owned by the caller. No fallback: a missing library raises in lib.load()."""
 import ctypes as C
-import os
+import contextlib
 
 import torch
 
 import functools
 
 from . import lib as L
+from .. import switches
 from ..nn.native.spec import GConv, WGrad
 from ..nn.native.twin import Twin, TwinSplit, is_twin
 
@@ -45,15 +46,8 @@ class HipOps(TwinSplit):
 
     # ---- kernel-selection switches ------------------------------------------------------------------------
     # The library reads no environment variable (gs_set_option, include/ganslate_hip.h); the GS_* variables of the
-    # host side are mapped onto its options here, when the backend is created and whenever a model is built.
-    ENV_OPTIONS = {"GS_SPLITK": "splitk", "GS_SPLITK_MAXB": "splitk_max_blocks", "GS_SPLITK_TARGET": "splitk_target",
-                   "GS_HCONV": "hconv", "GS_HCONV_WIDE": "hconv_wide", "GS_HCONVW_PERSIST": "hconvw_persist", "GS_HSTRIP_REGS": "hstrip_regs", "GS_GCONV_TWIN": "gconv_twin", "GS_GCONV_PERSIST": "gconv_persist", "GS_HCONVT_PERSIST": "hconvt_persist", "GS_WGRAD_ROWS": "wgrad_rows", "GS_SPLITK_MULTI": "splitk_multi", "GS_SPLITK_RING": "splitk_ring", "GS_GCONV_RING4": "gconv_ring4", "GS_WGRAD_TWIN": "wgrad_twin",
-                   "GS_HWGRAD": "hwgrad", "GS_HWGRAD_WIDE": "hwgrad_wide", "GS_HWGRAD_PLANES": "hwgrad_planes",
-                   "GS_BWD_PPB": "norm_bwd_ppb", "GS_APPLY_U": "norm_apply_unroll", "GS_GCONV_TILE288": "gconv_tile288", "GS_GCONV_MULTI": "gconv_multi",
-                   "GS_HCONVW_RING": "hconvw_ring", "GS_HCONVT": "hconvt", "GS_HSTRIP": "hstrip",
-                   "GS_WFOLD_ROWS": "wfold_rows", "GS_HWGRAD_FT": "hwgrad_ft", "GS_GCONV_BIG": "gconv_big", "GS_HCONV_BOX8": "hconv_box8",
-                   "GS_HCONV5": "hconv5", "GS_HWGRAD2": "hwgrad2", "GS_HCONV2": "hconv2", "GS_PWISE": "pwise"}
-
+    # host side are mapped onto its options here (switches.LIBRARY_OPTIONS), when the backend is created and whenever a
+    # model is built.
     def set_option(self, name, value):
         L.check(self.lib.gs_set_option(name.encode(), int(value)), "gs_set_option")
         self._plans.clear()
@@ -63,18 +57,33 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_get_option(name.encode(), C.byref(v)), "gs_get_option")
         return v.value
 
+    @contextlib.contextmanager
+    def options(self, **values):
+        """`with ops.options(hconv=0, hstrip=0): ...` runs the block with these option values and puts the previous ones back,
+        whatever the block raises"""
+        before = {name: self.get_option(name) for name in values}
+        try:
+            for name, value in values.items():
+                self.set_option(name, value)
+            yield self
+        finally:
+            for name, value in before.items():
+                self.set_option(name, value)
+
     def sync_options(self):
+        """every option follows its environment variable, or returns to the library's default where the variable is unset or
+        the option has none"""
         if not hasattr(self, "_option_defaults"):
             self._option_defaults = {}
-            for opt in self.ENV_OPTIONS.values():      # (an older build of the library — GANSLATE_HIP_LIB in an A/B — may not know
+            for opt in switches.LIBRARY_OPTIONS:       # (an older build of the library — GANSLATE_HIP_LIB in an A/B — may not know
                 try:                                   # the newest switches: those are skipped)
                     self._option_defaults[opt] = self.get_option(opt)
                 except L.HipError:
                     pass
-        for env, opt in self.ENV_OPTIONS.items():
-            if opt not in self._option_defaults:
-                continue
-            want = int(os.environ[env]) if env in os.environ else self._option_defaults[opt]
+        for opt, default in self._option_defaults.items():
+            want = switches.library_value(opt)
+            if want is None:
+                want = default
             if want != self.get_option(opt):
                 self.set_option(opt, want)
 
@@ -140,8 +149,8 @@ class HipOps(TwinSplit):
         return n
 
     def _cout1(self, d) -> bool:
-        """the dot-product kernels of the one-output-channel layer take this launch (GS_COUT1=0: A/B switch)"""
-        if os.environ.get("GS_COUT1", "1") == "0":
+        """the dot-product kernels of the one-output-channel layer take this launch"""
+        if not switches.on("GS_COUT1"):
             return False
         key = ("cout1", id(d))
         v = self._plans.get(key)
@@ -161,7 +170,7 @@ class HipOps(TwinSplit):
     # launches that will actually run, while their buffers are sized for all N images.
     def twin_native(self, g: GConv, N: int, ring: bool = False, fused: bool = False) -> bool:
         """ring: the fused data gradient on the unpadded domain (hconvw RING); fused: the padded-domain fused launch"""
-        if os.environ.get("GS_TWIN_NATIVE", "1") == "0":
+        if not switches.on("GS_TWIN_NATIVE"):
             return False
         d = self._gdesc(g, N, g.Ci, 0, g.Co, 0, "none", 0.0, 0, 0)
         if ring:
@@ -169,7 +178,7 @@ class HipOps(TwinSplit):
         if not fused and getattr(g, "co_real", 0) == 1 and self._cout1(d):
             return True
         if fused:
-            if os.environ.get("GS_TWIN_FUSED", "1") == "0":
+            if not switches.on("GS_TWIN_FUSED"):
                 return False
             f = L.GConvFuse()           # (fold 0 on a padded output domain: not the ring form)
             return bool(self.lib.gs_gconv_twin_native(C.byref(d), C.byref(f)))
@@ -178,9 +187,9 @@ class HipOps(TwinSplit):
     def fused_norm_plan(self, g: GConv, N: int, C_: int, force: bool = False, twin: bool = False):
         """(slots, scratch) for fusing the reduction pass of the consumer's InstanceNorm backward into the data-gradient
         launch of class g, or None when this backend / layer shape does not fuse (narrow layers run on the halo kernel)"""
-        if g.so != 1 or g.si not in (1, 2) or g.Co <= 64 or g.Co != C_ or os.environ.get("GS_FUSE_NORM", "1") == "0":
+        if g.so != 1 or g.si not in (1, 2) or g.Co <= 64 or g.Co != C_ or not switches.on("GS_FUSE_NORM"):
             return None
-        if g.si == 2 and os.environ.get("GS_FUSE_SI2", "1") == "0":     # (A/B switch: data gradients of transposed convs)
+        if g.si == 2 and not switches.on("GS_FUSE_SI2"):
             return None
         Nl = N // 2 if (twin and not self.twin_native(g, N, fused=True)) else N        # the batch of the launch(es)
         d = self._gdesc(g, Nl, g.Ci, 0, g.Co, 0, "none", 0.0, 0, 0)
@@ -214,10 +223,8 @@ class HipOps(TwinSplit):
     def fused_multi_plan(self, classes, N: int, C_: int, twin: bool = False):
         """(slots, scratch) when the output-parity classes of a stride-2 conv's data gradient run as ONE halo-resident launch
         that can carry the reduction pass of the consumer's InstanceNorm backward in its epilogue (hconvt.hip), else None"""
-        # (GS_FUSE_MULTI=0: A/B switch. Worth 0.3 % once the fused instantiation stopped spilling, DESIGN.md §4.11)
         g = classes[0]
-        if len(classes) != 4 or g.Co != C_ or os.environ.get("GS_FUSE_NORM", "1") == "0" or \
-                os.environ.get("GS_FUSE_MULTI", "1") == "0":
+        if len(classes) != 4 or g.Co != C_ or not switches.on("GS_FUSE_NORM") or not switches.on("GS_FUSE_MULTI"):
             return None
         Nl = N // 2 if (twin and not self.multi_twin_native(classes, N)) else N      # the batch of the launch(es)
         arr, _ = self._multi_descs(classes, Nl, g.Ci, g.Co)
@@ -229,7 +236,7 @@ class HipOps(TwinSplit):
     def fused_ring_plan(self, g: GConv, N: int, C_: int, twin: bool = False):
         """(slots, scratch) when the fused data gradient of a reflect-padded 3x3 layer can run on the unpadded domain
         (class g = Lowered.dgrad_ring; the launch folds the ring itself, hconvw.hip RING), else None"""
-        if g is None or g.Co != C_ or os.environ.get("GS_FUSE_NORM", "1") == "0":
+        if g is None or g.Co != C_ or not switches.on("GS_FUSE_NORM"):
             return None
         Nl = N // 2 if (twin and not self.twin_native(g, N, ring=True)) else N
         slots = self.lib.gs_gconv_ring_slots(C.byref(self._gdesc(g, Nl, g.Ci, 0, g.Co, 0, "none", 0.0, 0, 0)))
@@ -240,7 +247,7 @@ class HipOps(TwinSplit):
     def multi_twin_native(self, classes, N: int) -> bool:
         """a twin batch of N images over the output-parity classes of one layer runs as ONE launch (the halo-resident class
         kernel picks the packs per box, gs_gconv_multi_twin_native) — else as two launches of N / 2"""
-        if os.environ.get("GS_TWIN_NATIVE", "1") == "0" or os.environ.get("GS_TWIN_MULTI", "1") == "0" or N % 2:
+        if not switches.on("GS_TWIN_NATIVE") or not switches.on("GS_TWIN_MULTI") or N % 2:
             return False
         g = classes[0]
         key = ("multi_twin", tuple(id(c) for c in classes), N)
@@ -415,12 +422,12 @@ class HipOps(TwinSplit):
     @staticmethod
     def can_merge_wgrad(w: WGrad) -> bool:
         """two backward passes of this layer can share one launch (the wide halo kernel's eligibility, hwgrad.hip)"""
-        if w.si != 1 or w.P % 64 or w.Q % 64 or os.environ.get("GS_WGRAD_PAIR", "1") == "0":
+        if w.si != 1 or w.P % 64 or w.Q % 64 or not switches.on("GS_WGRAD_PAIR"):
             return False
         if w.T == 9 and w.Da == 1:
             return True
         # 3x3x3 layers of volumes run as three depth planes of the same kernel (hwgrad.hip)
-        return (w.T == 27 and w.Da > 1 and os.environ.get("GS_HWGRAD_PLANES", "1") != "0"
+        return (w.T == 27 and w.Da > 1 and switches.on("GS_HWGRAD_PLANES")
                 and all(w.dd[9 * k + t] == w.dd[9 * k] and w.dh[9 * k + t] == w.dh[t] and w.dw[9 * k + t] == w.dw[t]
                         for k in range(3) for t in range(9)))
 
@@ -471,9 +478,9 @@ class HipOps(TwinSplit):
         """dw += the weight gradient. fresh: the caller guarantees that dw holds zeros (the layer's first weight gradient since
         the optimiser cleared the buffer, NativeNet.wgrad_fresh) — a hint (gs_wgrad_desc.dw_fresh), never a requirement"""
         twin = is_twin(dw)
-        fresh = bool(fresh) and not twin and pair is None and os.environ.get("GS_WGRAD_FRESH", "1") != "0"     # (A/B switch)
-        if twin and (os.environ.get("GS_WGRAD_DET", "1") == "0" or os.environ.get("GS_TWIN_NATIVE", "1") == "0"
-                     or os.environ.get("GS_TWIN_WGRAD", "1") == "0"):       # (A/B switch)
+        fresh = bool(fresh) and not twin and pair is None and switches.on("GS_WGRAD_FRESH")
+        if twin and (not switches.on("GS_WGRAD_DET") or not switches.on("GS_TWIN_NATIVE")
+                     or not switches.on("GS_TWIN_WGRAD")):
             return self.twin_wgrad(w, a, g, dw, a_cs=a_cs, a_co=a_co, g_cs=g_cs, g_co=g_co, pair=pair)
         key = ("w", id(w), a.shape[0], a_cs, a_co, g_cs, g_co, fresh)
         ent = self._desc_cache.get(key)
@@ -481,8 +488,7 @@ class HipOps(TwinSplit):
             d = self._wdesc(w, a.shape[0], a_cs if a_cs is not None else a.shape[-1], a_co,
                             g_cs if g_cs is not None else g.shape[-1], g_co, fresh)
             ent = self._desc_cache[key] = (d, w)
-        if getattr(w, "p_real", 0) == 1 and os.environ.get("GS_COUT1", "1") != "0" and \
-                os.environ.get("GS_WGRAD_DET", "1") != "0":
+        if getattr(w, "p_real", 0) == 1 and switches.on("GS_COUT1") and switches.on("GS_WGRAD_DET"):
             ckey = ("cout1_w", id(ent[0]))
             nws = self._plans.get(ckey)
             if nws is None:
@@ -520,7 +526,7 @@ class HipOps(TwinSplit):
                 t_end.record()
             return
         t_end = self._time_begin("wgrad", w, pair is not None, a.shape[0])
-        if os.environ.get("GS_WGRAD_DET", "1") != "0":
+        if switches.on("GS_WGRAD_DET"):
             # deterministic accumulation (default): partial sums to a per-launch workspace, fixed-order second stage
             wkey = ("wgrad_ws", id(ent[0]), pair is not None)
             nws = self._plans.get(wkey)
@@ -556,7 +562,7 @@ class HipOps(TwinSplit):
             L.check(self.lib.gs_bias_grad_head_ws(_ptr(dy), pixels, cs_, co + full, C_ - full, _ptr(db[full:]),
                                                   _ptr(ws), nws, _stream()), "gs_bias_grad_head_ws")
             return
-        if os.environ.get("GS_WGRAD_DET", "1") != "0":      # deterministic: partial sums + fixed-order second stage
+        if switches.on("GS_WGRAD_DET"):      # deterministic: partial sums + fixed-order second stage
             nws = int(self.lib.gs_bias_grad_ws_floats(pixels, C_))
             ws = torch.empty(nws, dtype=torch.float32, device=self.device)
             L.check(self.lib.gs_bias_grad_ws(_ptr(dy), pixels, C_, cs if cs is not None else dy.shape[-1], co, _ptr(db),

@@ -14,6 +14,7 @@ from pathlib import Path
 
 import torch
 
+from ... import switches
 from ...utils import communication, io, streams
 from ...utils.builders import build_D, build_G
 from ...utils.metrics import TrainingMetrics
@@ -103,8 +104,8 @@ class BaseGAN(ABC):
                 raise ValueError("When inferring there should be only one network initialized - generator.")
         if self.conf[self.conf.mode].checkpointing.load_iter:
             self.load_networks(self.conf[self.conf.mode].checkpointing.load_iter)
-        if int(os.environ.get("WORLD_SIZE", 1)) > 1 or os.environ.get("GS_FORCE_DDP") == "1":
-            self.parallelize_networks()      # GS_FORCE_DDP: the data-parallel path with a 1-rank group (tests)
+        if int(os.environ.get("WORLD_SIZE", 1)) > 1 or switches.on("GS_FORCE_DDP"):
+            self.parallelize_networks()
         if self.is_train:
             self._init_step_graph()
 
@@ -115,7 +116,7 @@ class BaseGAN(ABC):
     # start (fork_side_work), wrap it (side_work) and join before the discriminator optimiser step.
     def _side_stream_enabled(self, name):
         from ..native.backend import get_ops
-        want = os.environ.get("GS_SIDE_STREAM", "1")        # "0": none, "1": all, or a comma list of names
+        want = switches.raw("GS_SIDE_STREAM")
         if not ((want == "1" or name in want.split(",")) and self.device.type == "cuda"
                 and getattr(get_ops(), "name", "") == "hip"):
             return False
@@ -161,7 +162,7 @@ class BaseGAN(ABC):
         the pass's own (Pix2Pix: 3.82 -> 3.65 ms per step, profiles/r06_ab_pix2pix.txt). GS_EARLY_ADAM=0: the update after the
         pass."""
         optim = self.optimizers[name]
-        if os.environ.get("GS_EARLY_ADAM", "1") == "0" or not hasattr(optim, "arm_early"):
+        if not switches.on("GS_EARLY_ADAM") or not hasattr(optim, "arm_early"):
             return False
         return optim.arm_early()
 
@@ -175,7 +176,7 @@ class BaseGAN(ABC):
         self._graph_update = None
         nets_capturable = all(getattr(net, "graph_capturable", True) for net in self.networks.values())
         self.step_graph_enabled = (self.graph_capturable and nets_capturable
-                                   and os.environ.get("GS_STEP_GRAPH", "1") != "0"
+                                   and switches.on("GS_STEP_GRAPH")
                                    and getattr(get_ops(), "name", "") == "hip" and self.device.type == "cuda")
         if self.device.type == "cuda":
             self._side = {n: {"stream": torch.cuda.Stream(device=self.device), "fork": None, "busy": False}
@@ -301,7 +302,7 @@ class BaseGAN(ABC):
         if dp_nets:
             import torch.distributed as dist
             default = "0" if dist.get_world_size(dp_nets[0]._dist) > 1 else "auto"
-            want = os.environ.get("GS_DDP_GRAPH_COLLECTIVES", default)
+            want = switches.raw("GS_DDP_GRAPH_COLLECTIVES", default)
         else:
             want = "none"
         self.ddp_form_requested = want

@@ -9,14 +9,13 @@ land in the same flat buffer and are all-reduced with it; the `mlp` optimiser st
 The encoder-only passes do not materialise NCHW feature maps: a "patch" is one pixel's channel vector, i.e. one
 contiguous row of the NHWC activation, so the sampled patches are gathered straight out of the executor's
 activations (Resnet2D.extract_patch_features) and their gradients scattered straight back."""
-import os
 from dataclasses import dataclass, field
 from typing import Tuple
 
 import numpy as np
 import torch
 
-from .... import configs
+from .... import configs, switches
 from ...losses.adversarial_loss import AdversarialLoss
 from ...losses.functional import fanout, scalar_affine, scalar_sum
 from ...optim import NativeAdam
@@ -136,13 +135,13 @@ class CUT(BaseGAN):
     @staticmethod
     def _batched(G):
         """same-network passes over independent batches run as one pass (GS_CUT_BATCH=0: one pass each, as the reference)"""
-        return os.environ.get("GS_CUT_BATCH", "1") != "0" and hasattr(G, "forward_parts") and \
+        return switches.on("GS_CUT_BATCH") and hasattr(G, "forward_parts") and \
             hasattr(G, "extract_patch_features_parts")
 
     def backward_D(self):
         real, fake = self.visuals["real_B"], self.visuals["fake_B"]
         D = self.networks["D"]
-        if hasattr(D, "forward_parts") and os.environ.get("GS_CUT_BATCH", "1") != "0":
+        if hasattr(D, "forward_parts") and switches.on("GS_CUT_BATCH"):
             pred_real, pred_fake = D.forward_parts((real, fake.detach()))      # one pass over both batches (per-sample norm)
         else:
             pred_real, pred_fake = D(real), D(fake.detach())

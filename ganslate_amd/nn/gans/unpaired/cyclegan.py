@@ -3,12 +3,11 @@ ganslate/nn/gans/unpaired/cyclegan.py:12-224, running on the HIP executors:
 forward (4 or 6 generator passes) -> SSIM metrics -> G step (Ds frozen: no D weight-gradient kernels are
 launched) -> D_B step, D_A step (image pools, `.detach()`), Adam on flat buffers."""
 import itertools
-import os
 from dataclasses import dataclass, field
 
 import torch
 
-from .... import configs
+from .... import configs, switches
 from ....data.utils.image_pool import ImagePool
 from ...losses.adversarial_loss import AdversarialLoss
 from ...losses.cyclegan_losses import CycleGANLosses
@@ -60,7 +59,7 @@ class CycleGAN(BaseGAN):
         the chip at batch 1 and the per-network PReLU-norm launches stay halves: profiles/r06_ab_vnet_twin.txt) — executors
         that set twin_default = False pair up only with GS_TWIN=all."""
         self.twin_G = self.twin_D = None
-        mode = os.environ.get("GS_TWIN", "1")
+        mode = switches.raw("GS_TWIN")
         if not self.is_train or mode == "0":
             return
         ok = lambda a, b: TwinNet.compatible(a, b) and (a.dims == 2 or mode != "2d") and \

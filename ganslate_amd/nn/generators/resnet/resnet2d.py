@@ -2,12 +2,11 @@
 names as ganslate/nn/generators/resnet/resnet2d.py:14-93:
 c7s1-64, d128, d256, n x R256, u128, u64, c7s1-out, tanh; ReflectionPad before the k7 and residual convs;
 InstanceNorm2d(affine=False) + ReLU; ConvTranspose2d(3, s2, p1, op1) up-sampling (always biased)."""
-import os
 from dataclasses import dataclass
 
 import torch
 
-from .... import configs
+from .... import configs, switches
 from ...native.net import NativeNet, Node
 from ...native.spec import ConvSpec
 from ...utils import is_bias_before_norm, require_instance_norm
@@ -27,7 +26,7 @@ def resnet_nodes(in_channels, out_channels, use_bias, n, dims=2, wfold=None):
     # the k7 convs at the image boundary have 1-3 channels on one side: their W taps are folded into the channel axis
     # so the 16-wide matrix tile is not mostly padding (csrc/wfold.hip); GS_WFOLD=0 keeps the plain lowering (A/B runs)
     if wfold is None:
-        wfold = os.environ.get("GS_WFOLD", "1") != "0"
+        wfold = switches.on("GS_WFOLD")
     wf_in = "in" if (wfold and 7 * in_channels <= 32) else ""
     wf_out = "out" if (wfold and 7 * out_channels <= 32) else ""
     nodes = [Node(conv("conv", in_channels, 64, 7, 1, 3, pad_mode=pad_mode, bias=use_bias, wfold=wf_in), True, "relu",

@@ -19,12 +19,12 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
+from ... import switches
 from .backend import get_ops
 from .spec import ConvSpec, Lowered, lower
 from .twin import Twin
 
 
-import os
 import weakref
 
 
@@ -353,7 +353,7 @@ class NativeNet:
         """(pack set, (inv_f, fpack, inv_d, dpack)) for gs_adam_step_dev_packs, or None: inv_x[i] = the group of 8 pack
         elements that IS master elements 8 i .. 8 i + 7 (-1: none). Built once per pack set; only for a network with ONE pack
         set (one input size) — with several, every set refreshes from the master as before. GS_ADAM_PACKS=0 switches it off."""
-        if os.environ.get("GS_ADAM_PACKS", "1") == "0" or len(self._packs) != 1 or self.master.data_ptr() % 16:
+        if not switches.on("GS_ADAM_PACKS") or len(self._packs) != 1 or self.master.data_ptr() % 16:
             return None
         (pk,) = self._packs.values()
         if "fused" not in pk:

@@ -1,10 +1,9 @@
 """Fused flat Adam over the executor's master buffers (gs_adam_step). Subclasses torch.optim.Optimizer so the
 reference's LambdaLR schedule (nn/utils.py:83-99) and `param_groups[0]['lr']` logging (base.py:318-319) work
 unchanged; constructor signature mirrors torch.optim.Adam(params, lr, betas) as used in cyclegan.py:81-82."""
-import os
-
 import torch
 
+from .. import switches
 from .native.backend import get_ops
 
 
@@ -60,18 +59,18 @@ class NativeAdam(torch.optim.Optimizer):
         if not self.external_prepare:
             self.prepare()
         self._early = {"prepared": True,
-                       "tr": os.environ.get("GS_WGRAD_ADAM_TR", "1") != "0"}       # (A/B switch: transposed packs by the fused launch)
-        fuse = os.environ.get("GS_WGRAD_ADAM", "1") != "0"       # (A/B switch)
+                       "tr": switches.on("GS_WGRAD_ADAM_TR")}
+        fuse = switches.on("GS_WGRAD_ADAM")
         for net in nets:
             # a network whose large layers took the fused launch last step: what is left (biases, small layers) goes in ONE
             # multi-range launch behind the pass instead of a dozen chunk launches between its launches
-            ranged = fuse and getattr(net, "_last_fused", 0) > 0 and os.environ.get("GS_ADAM_RANGES", "1") != "0"      # (A/B switch)
+            ranged = fuse and getattr(net, "_last_fused", 0) > 0 and switches.on("GS_ADAM_RANGES")
             net._early_step = None if ranged else self._early_chunk
             # layers of few pixels: weight gradient + update in one launch (gs_wgrad_adam) — the executor asks per layer
             net._early_fuse = self._fuse_args if fuse else None
             net._early_fused, net._early_tr = [], []
             net._early_cursor = net.b_off[-1] + net.nodes[-1].spec.cout_p      # end of the node parameters
-            net._early_min = int(os.environ.get("GS_EARLY_ADAM_MIN", self.EARLY_MIN))
+            net._early_min = switches.value("GS_EARLY_ADAM_MIN", self.EARLY_MIN)
         return True
 
     @staticmethod

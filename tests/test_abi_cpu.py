@@ -28,19 +28,34 @@ def test_library_exports_every_declared_symbol():
     assert sorted(L.EXPORTS) == names, "ctypes prototypes and header declarations differ"
 
 
+def option_rows():
+    """(id suffix, option name, default) of every X(...) row of GS_OPTIONS in csrc/common.hpp"""
+    text = (ROOT / "ganslate_amd" / "csrc" / "common.hpp").read_text()
+    body = text[text.index("#define GS_OPTIONS(X)"):text.index("enum GsOpt {")]
+    return [(i, n, int(d)) for i, n, d in re.findall(r'^\s*X\((\w+),\s*"(\w+)",\s*(-?\d+)\)', body, flags=re.M)]
+
+
 def test_every_env_option_is_a_library_option():
-    """HipOps.ENV_OPTIONS maps the host's GS_* variables onto gs_set_option names. sync_options skips names the library does
-    not know (an older build in an A/B), so a stale entry would go unnoticed: every name must be an option of this build
-    (gs_get_option is host code, no GPU needed)."""
+    """switches.LIBRARY_OPTIONS maps the host's GS_* variables onto gs_set_option names. sync_options skips names the library
+    does not know (an older build in an A/B), so a stale entry would go unnoticed: every name must be an option of this build
+    (gs_get_option is host code, no GPU needed), with the default its row of GS_OPTIONS states — and the table must hold
+    exactly the names of that list, so an option added on one side only fails here."""
+    from ganslate_amd import switches
     from ganslate_amd.hip import lib as L
-    from ganslate_amd.hip.ops import HipOps
     if not L.library_path().is_file():
         import __graft_entry__
         __graft_entry__.build()
     lib = L.load()
+    rows = option_rows()
+    assert len(rows) >= 30 and len({n for _, n, _ in rows}) == len(rows) == len({i for i, _, _ in rows})
+    assert {n for _, n, _ in rows} == set(switches.LIBRARY_OPTIONS)
+    defaults = {n: d for _, n, d in rows}
     value = ctypes.c_int(0)
-    for env, name in HipOps.ENV_OPTIONS.items():
+    for name, env in switches.LIBRARY_OPTIONS.items():
         assert lib.gs_get_option(name.encode(), ctypes.byref(value)) == 0, f"{env} -> '{name}': not an option of the library"
+        assert value.value == defaults[name], f"'{name}': the library answers {value.value}, its row says {defaults[name]}"
+    envs = [e for e in switches.LIBRARY_OPTIONS.values() if e is not None]
+    assert len(set(envs)) == len(envs) and all(e.startswith("GS_") for e in envs)
 
 
 def test_descriptor_layouts_match_header():

@@ -101,21 +101,6 @@ def case_of(case, **kw):
     return exact.make_case(case[0], case[1], case[2:], **kw)
 
 
-class option:
-    """option set for a block and restored to the value read before"""
-    def __init__(self, ops, **values):
-        self.ops, self.values = ops, values
-
-    def __enter__(self):
-        self.before = {k: self.ops.get_option(k) for k in self.values}
-        for k, v in self.values.items():
-            self.ops.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.before.items():
-            self.ops.set_option(k, v)
-
-
 # ---- every layer on the paths the library picks by itself -------------------------------------------------------------------
 @pytest.mark.parametrize("case", CONV_CASES, ids=_ids)
 def test_forward_and_statistics(hip_ops, case):
@@ -154,7 +139,7 @@ def test_narrow_halo_kernel_box_forms(hip_ops, case):
     c = case_of(case, check=("fwd", "dgrad"))
     slots = {}
     for box8 in (0, 1):
-        with option(hip_ops, hconv_box8=box8):
+        with hip_ops.options(hconv_box8=box8):
             slots[box8] = hip_ops.stat_slots(c.low.fwd[0], c.N)
             check_forward(hip_ops, c, f"hconv_box8={box8}", "relu")
             check_dgrad(hip_ops, c, f"hconv_box8={box8}")
@@ -166,7 +151,7 @@ def test_narrow_halo_kernel_box_forms(hip_ops, case):
 @pytest.mark.parametrize("case", WIDE_HALO_CASES, ids=_ids)
 def test_wide_halo_kernel(hip_ops, case, persist):
     c = case_of(case, check=("fwd",))
-    with option(hip_ops, hconvw_persist=persist):
+    with hip_ops.options(hconvw_persist=persist):
         assert hip_ops.stat_slots(c.low.fwd[0], c.N) == (c.sizes[0] // 16) * (c.sizes[1] // 16), \
             "the wide halo kernel must take this layer"
         check_forward(hip_ops, c, f"hconvw (persist={persist})")
@@ -177,7 +162,7 @@ def test_boundary_convs_on_the_strip_kernels(hip_ops, case):
     c = case_of(case)
     g0 = c.low.fwd[0]
     for form, (on, regs) in (("regs", (1, 2)), ("lds", (1, 0)), ("im2col", (0, 0))):
-        with option(hip_ops, hstrip=on, hstrip_regs=regs):
+        with hip_ops.options(hstrip=on, hstrip_regs=regs):
             if on and g0.Ci in (32, 64):
                 rows = 16 if (regs and g0.Ci == 64 and g0.Co <= 32) else 32
                 assert hip_ops.stat_slots(g0, c.N) == ((g0.Ho + rows - 1) // rows) * ((g0.Wo + 7) // 8)
@@ -228,9 +213,9 @@ def test_register_resident_k5_kernel(hip_ops, sizes, seg):
     spec, N = ConvSpec("conv", 16, 16, 5, 1, 2, dims=3), 2
     c, x2, base = _slice_case(spec, N, sizes, 31)
     ref = cached("slice", c, lambda cc: _run_slice(RefOps(), "cpu", cc, x2, base))
-    with option(hip_ops, hconv5_seg=seg, hconv5=1):
+    with hip_ops.options(hconv5_seg=seg, hconv5=1):
         on = _run_slice(hip_ops, hip_ops.device, c, x2, base)
-    with option(hip_ops, hconv5_seg=seg, hconv5=0):
+    with hip_ops.options(hconv5_seg=seg, hconv5=0):
         off = _run_slice(hip_ops, hip_ops.device, c, x2, base)
     assert on[3] == (sizes[0] // 4) * (sizes[1] // 16) * (sizes[2] // 16) and off[3] != on[3], (on[3], off[3])
     _check_slice(on, ref, base, 16, "hconv5")
@@ -244,7 +229,7 @@ def test_persistent_narrow_volume_kernel(hip_ops, case):
     c, x2, base = _slice_case(ConvSpec("conv", cin, cout, 5, 1, 2, dims=3), 1, sizes, 61)
     ref = _run_slice(RefOps(), "cpu", c, x2, base)
     for v in (4, 0):
-        with option(hip_ops, hconv2=v):
+        with hip_ops.options(hconv2=v):
             _check_slice(_run_slice(hip_ops, hip_ops.device, c, x2, base), ref, base, cin, f"hconv2 = {v}")
 
 
@@ -263,7 +248,7 @@ def test_split_k_on_the_bottleneck_layers(hip_ops, case, on):
     """the single-class forward of the U-Net bottleneck convs with and without split-K (the transposed sibling's classes go
     through the merged split-K launch: test_split_k_over_merged_parity_classes); statistics come out of the finalize pass"""
     c = case_of(case, check=("fwd", "dgrad"))
-    with option(hip_ops, splitk=on):
+    with hip_ops.options(splitk=on):
         g0 = c.low.fwd[0]
         slots = hip_ops.stat_slots(g0, c.N)
         d = hip_ops._gdesc(g0, c.N, c.xa.shape[-1], 0, g0.Co, 0, "none", 0.2, slots, 0)      # the launch check_forward makes
@@ -277,7 +262,7 @@ def test_split_k_on_the_bottleneck_layers(hip_ops, case, on):
 def test_pointwise_kernels(hip_ops, chans, sizes):
     c = exact.make_case(ConvSpec("conv", chans[0], chans[1], 1, 1, 0, dims=3), 2, sizes, seed=41, prefill=7.0)
     for on in (1, 0):
-        with option(hip_ops, pwise=on):
+        with hip_ops.options(pwise=on):
             check_forward(hip_ops, c, f"pwise={on}", "lrelu", 0.25)
             check_dgrad(hip_ops, c, f"pwise={on}")
             check_wgrad(hip_ops, c, f"pwise={on}")
@@ -302,7 +287,7 @@ def test_persistent_im2col_kernel(hip_ops, case, persist):
     """(the three smaller launches of PERSIST_CASES: the oracle of the 16 x 256 x 256 ones costs more than the rest of the file)"""
     c = case_of(case, check=("fwd",))
     g0 = c.low.fwd[0]
-    with option(hip_ops, gconv_persist=persist):
+    with hip_ops.options(gconv_persist=persist):
         # pconv.hip takes a 256 x 128 tile launch with more tiles than CUs and at most `gconv_persist` K-steps: this one is
         tiles = c.N * hip_ops.stat_slots(g0, c.N) * ((g0.Co + 127) // 128)
         assert hip_ops.tile_m(g0, c.N) == 256 and tiles > torch.cuda.get_device_properties(hip_ops.device).multi_processor_count
@@ -320,7 +305,7 @@ def test_parity_classes(hip_ops, case, path):
     opts = {"hconvt": dict(hconvt=1, gconv_multi=1), "merged": dict(hconvt=0, gconv_multi=1),
             "per-class": dict(hconvt=0, gconv_multi=0)}[path]
     for persist in ((1, 0) if path == "hconvt" else (1,)):
-        with option(hip_ops, hconvt_persist=persist, **opts):
+        with hip_ops.options(hconvt_persist=persist, **opts):
             for classes in (c.low.fwd, c.low.dgrad):       # the class kernel takes exactly the layers its restatement names
                 if len(classes) > 1:
                     taken = hip_ops.fused_multi_plan(classes, c.N, classes[0].Co) is not None
@@ -337,7 +322,7 @@ def test_persistent_parity_class_kernel(hip_ops, case, persist):
     PatchGAN k4 data gradient. (PERSIST_PARITY_CASES[0], [2], [3] are the same two patterns at 2 - 4 times the oracle cost.)"""
     c = case_of(case, check=("fwd", "dgrad"))
     cus = torch.cuda.get_device_properties(hip_ops.device).multi_processor_count
-    with option(hip_ops, hconvt=1, hconvt_persist=persist):
+    with hip_ops.options(hconvt=1, hconvt_persist=persist):
         ran = 0
         for classes, check in ((c.low.fwd, check_forward), (c.low.dgrad, check_dgrad)):
             if len(classes) != 4:
@@ -357,7 +342,7 @@ def test_split_k_over_merged_parity_classes(hip_ops, case, on):
     c = case_of(case, check=("fwd", "dgrad"))
     fwd_multi, dg_multi = len(c.low.fwd) == 4, len(c.low.dgrad) == 4
     assert fwd_multi or dg_multi
-    with option(hip_ops, splitk_multi=on):
+    with hip_ops.options(splitk_multi=on):
         classes = c.low.fwd if fwd_multi else c.low.dgrad
         descs = [hip_ops._gdesc(g, c.N, (c.xa if fwd_multi else c.gy).shape[-1], 0,
                                 (c.spec.cout_p if fwd_multi else c.spec.cin_p), 0, "none", 0.2, 0, 0) for g in classes]
@@ -507,7 +492,7 @@ def test_weight_gradient_epilogues(hip_ops, case, misalign, rows):
     pre = torch.randint(-8, 9, (n + 4,), generator=torch.Generator().manual_seed(5)).float()
     ref = pre.clone()
     RefOps().wgrad(c.low.wgrad, a, gt, ref[misalign:misalign + n])
-    with option(hip_ops, wgrad_rows=rows):
+    with hip_ops.options(wgrad_rows=rows):
         buf = pre.clone().to(dev)
         hip_ops.wgrad(c.low.wgrad, a.to(dev), gt.to(dev), buf[misalign:misalign + n])
         torch.cuda.synchronize()
@@ -522,7 +507,7 @@ def test_weight_gradient_epilogues(hip_ops, case, misalign, rows):
 @pytest.mark.parametrize("v", [2, 1])
 def test_one_channel_volume_weight_gradient(hip_ops, v):
     c = exact.make_case(ConvSpec("conv", 256, 1, 4, 1, 1, dims=3), 2, (11, 15, 19), seed=51, prefill=7.0, check=("wgrad",))
-    with option(hip_ops, hwgrad2=v):
+    with hip_ops.options(hwgrad2=v):
         check_wgrad(hip_ops, c, f"hwgrad2={v}")
 
 

@@ -161,20 +161,16 @@ def test_halo_resident_narrow_kernel_box_forms(hip_ops, case):
     xa = torch.zeros(N, *sizes, spec.cin_p, dtype=torch.bfloat16)
     xa[..., :spec.cin] = torch.randn(N, *sizes, spec.cin, generator=g).to(torch.bfloat16)
     y_ref, mr_ref = run_forward(RefOps(), "cpu", low, bias, fpack, xa, N, act="relu")
-    default = hip_ops.get_option("hconv_box8")
-    try:
-        slots = {}
-        for form, box8 in {"4x8x8": 0, "8x8x8": 1}.items():
-            hip_ops.set_option("hconv_box8", box8)
+    slots = {}
+    for form, box8 in {"4x8x8": 0, "8x8x8": 1}.items():
+        with hip_ops.options(hconv_box8=box8):
             slots[form] = hip_ops.stat_slots(low.fwd[0], N)
             y_hip, mr_hip = run_forward(hip_ops, hip_ops.device, low, bias, fpack, xa, N, act="relu")
             torch.cuda.synchronize()
             close_bf16(y_hip, y_ref, f"conv output ({form})")
             close_stats(mr_hip, mr_ref, N, spec.cout_p, spec.cout, f"({form}) ")
-        if sizes[0] >= 8 and spec.cout <= 16:
-            assert slots["8x8x8"] < slots["4x8x8"], slots          # the 8-deep boxes were really taken
-    finally:
-        hip_ops.set_option("hconv_box8", default)
+    if sizes[0] >= 8 and spec.cout <= 16:
+        assert slots["8x8x8"] < slots["4x8x8"], slots          # the 8-deep boxes were really taken
 
 
 WIDE_HALO_CASES = [
@@ -192,19 +188,17 @@ def test_wide_halo_kernel_forward(hip_ops, case, persist):
     """hconvw.hip, forward form, against the oracle (bias, one statistics slot per 16 x 16 box, bf16 NHWC output): one tile per
     workgroup and — more tiles than CUs, at least two channel chunks — several (option hconvw_persist); the chunk-count and
     border edge cases of its DMA pipeline."""
-    default = hip_ops.get_option("hconvw_persist")
-    hip_ops.set_option("hconvw_persist", persist)
     spec, N, sizes = case[0], case[1], case[2:]
     low, master, bias, fpack, dpack = make_layer(spec, sizes, 11)
-    assert hip_ops.stat_slots(low.fwd[0], N) == (sizes[0] // 16) * (sizes[1] // 16), "the wide halo kernel must take this layer"
-    g = torch.Generator().manual_seed(12)
-    xa = torch.randn(N, *sizes, spec.cin_p, generator=g).to(torch.bfloat16)
-    y_ref, mr_ref = run_forward(RefOps(), "cpu", low, bias, fpack, xa, N)
-    y_hip, mr_hip = run_forward(hip_ops, hip_ops.device, low, bias, fpack, xa, N)
-    torch.cuda.synchronize()
+    with hip_ops.options(hconvw_persist=persist):
+        assert hip_ops.stat_slots(low.fwd[0], N) == (sizes[0] // 16) * (sizes[1] // 16), "the wide halo kernel must take this layer"
+        g = torch.Generator().manual_seed(12)
+        xa = torch.randn(N, *sizes, spec.cin_p, generator=g).to(torch.bfloat16)
+        y_ref, mr_ref = run_forward(RefOps(), "cpu", low, bias, fpack, xa, N)
+        y_hip, mr_hip = run_forward(hip_ops, hip_ops.device, low, bias, fpack, xa, N)
+        torch.cuda.synchronize()
     close_bf16(y_hip, y_ref, "conv output")
     close_stats(mr_hip, mr_ref, N, spec.cout_p, spec.cout, "")
-    hip_ops.set_option("hconvw_persist", default)
 
 
 STRIP_CASES = [
@@ -227,14 +221,11 @@ def test_halo_resident_boundary_convs(hip_ops, case):
     xa = torch.zeros(N, *low.in_dims, low.fwd[0].Ci, dtype=torch.bfloat16)
     xa.copy_(torch.randn(xa.shape, generator=g).to(torch.bfloat16))
     gy = torch.randn(N, *low.out_dims, low.fwd[0].Co, generator=g).to(torch.bfloat16)
-    default, default_regs = hip_ops.get_option("hstrip"), hip_ops.get_option("hstrip_regs")
     res = {}
-    try:
-        # "regs": the persistent form with the weights in registers (any grid: option value 2), "lds": one tile per workgroup
-        # with the weights staged in LDS (every eligible layer whatever its grid), "im2col": both off
-        for form, (on, regs) in (("regs", (1, 2)), ("lds", (1, 0)), ("im2col", (0, 0))):
-            hip_ops.set_option("hstrip", on)
-            hip_ops.set_option("hstrip_regs", regs)
+    # "regs": the persistent form with the weights in registers (any grid: option value 2), "lds": one tile per workgroup
+    # with the weights staged in LDS (every eligible layer whatever its grid), "im2col": both off
+    for form, (on, regs) in (("regs", (1, 2)), ("lds", (1, 0)), ("im2col", (0, 0))):
+        with hip_ops.options(hstrip=on, hstrip_regs=regs):
             ci, co = low.fwd[0].Ci, low.fwd[0].Co
             if on and ci in (32, 64):      # (the 1-channel stem folds to 8 channels: stays on the im2col kernel)
                 rows = 16 if (regs and ci == 64 and co <= 32) else 32
@@ -244,9 +235,6 @@ def test_halo_resident_boundary_convs(hip_ops, case):
             hip_ops.gconv_classes(low.dgrad, gy.to(hip_ops.device), dpack.to(hip_ops.device), None, gx)
             torch.cuda.synchronize()
             res[form] = (y.cpu(), mr.cpu(), gx.cpu())
-    finally:
-        hip_ops.set_option("hstrip", default)
-        hip_ops.set_option("hstrip_regs", default_regs)
     y_ref, mr_ref = run_forward(RefOps(), "cpu", low, bias, fpack, xa, N)
     gx_ref = torch.zeros(N, *low.dgrad_dims, low.dgrad[0].Co, dtype=torch.bfloat16)
     RefOps().gconv_classes(low.dgrad, gy, dpack, None, gx_ref)
@@ -314,11 +302,9 @@ def test_merged_parity_classes_equal_separate_launches(hip_ops, case):
     gy = torch.zeros(N, *low.out_dims, spec.cout_p, dtype=torch.bfloat16)
     gy[..., :spec.cout] = torch.randn(N, *low.out_dims, spec.cout, generator=g).to(torch.bfloat16)
     res = {}
-    hconvt_default = hip_ops.get_option("hconvt")
-    try:
-        hip_ops.set_option("hconvt", 0)          # the im2col class launches are what is compared here (hconvt.hip has its own test)
-        for merged in (1, 0):
-            hip_ops.set_option("gconv_multi", merged)
+    for merged in (1, 0):
+        # hconvt = 0: the im2col class launches are what is compared here (hconvt.hip has its own test)
+        with hip_ops.options(hconvt=0, gconv_multi=merged):
             slots, offs = stats_slots(hip_ops, low, low.fwd, N)
             ya = torch.zeros(N, *low.out_dims, spec.cout_p, dtype=torch.bfloat16, device=dev)
             part = torch.full((N * slots * 2 * spec.cout_p,), float("nan"), dtype=torch.float32, device=dev)
@@ -328,9 +314,6 @@ def test_merged_parity_classes_equal_separate_launches(hip_ops, case):
             hip_ops.gconv_classes(low.dgrad, gy.to(dev), dpack.to(dev), None, gx)
             torch.cuda.synchronize()
             res[merged] = (ya.cpu(), part.cpu(), gx.cpu())
-    finally:
-        hip_ops.set_option("gconv_multi", 1)
-        hip_ops.set_option("hconvt", hconvt_default)
     assert len(low.fwd) > 1 or len(low.dgrad) > 1
     assert not torch.isnan(res[1][1]).any()
     for a, b, what in zip(res[1], res[0], ("forward", "statistics", "data gradient")):
@@ -377,9 +360,8 @@ def test_split_k_over_merged_parity_classes(hip_ops, case):
         return out
 
     res = {}
-    try:
-        for on in (1, 1, 0):
-            hip_ops.set_option("splitk_multi", on)
+    for on in (1, 1, 0):
+        with hip_ops.options(splitk_multi=on):
             classes = low.fwd if fwd_multi else low.dgrad
             descs = [hip_ops._gdesc(c, N, (xa if fwd_multi else gy).shape[-1], 0, (spec.cout_p if fwd_multi else spec.cin_p), 0,
                                     "none", 0.2, 0, 0) for c in classes]
@@ -389,8 +371,6 @@ def test_split_k_over_merged_parity_classes(hip_ops, case):
             r = run(hip_ops, dev)
             torch.cuda.synchronize()
             res.setdefault(on, []).append(r)
-    finally:
-        hip_ops.set_option("splitk_multi", 1)
     ref = run(RefOps(), "cpu")
     a, a2, b = res[1][0], res[1][1], res[0][0]
     for k in a:
@@ -427,10 +407,8 @@ def test_halo_resident_parity_classes(hip_ops, case):
     fwd_multi, dg_multi = len(low.fwd) == 4, len(low.dgrad) == 4
     assert fwd_multi or dg_multi
     res = {}
-    hconvt_default = hip_ops.get_option("hconvt")     # = the smallest grid the kernel takes; 1: every eligible layer, 0: off
-    try:
-        for on in (1, 0):
-            hip_ops.set_option("hconvt", on)
+    for on in (1, 0):
+        with hip_ops.options(hconvt=on):     # = the smallest grid the kernel takes; 1: every eligible layer, 0: off
             out = {}
             if fwd_multi:
                 slots, offs = stats_slots(hip_ops, low, low.fwd, N)
@@ -446,8 +424,6 @@ def test_halo_resident_parity_classes(hip_ops, case):
                 out["gx"] = gx.cpu()
             torch.cuda.synchronize()
             res[on] = out
-    finally:
-        hip_ops.set_option("hconvt", hconvt_default)
     ref = RefOps()
     if fwd_multi:
         yr = torch.zeros(N, *low.out_dims, spec.cout_p, dtype=torch.bfloat16)
@@ -682,10 +658,8 @@ def test_parity_class_dgrad_with_fused_norm_sums(hip_ops, monkeypatch, case, wit
     gy = torch.randn(N, *low.out_dims, spec.cout_p, generator=g).to(torch.bfloat16)
     y = (torch.randn(N, *sizes, C, generator=g) * 1.5 + 0.2).to(torch.bfloat16)
     g2 = torch.randn(N, *sizes, C, generator=g).to(torch.bfloat16) if with_g2 else None
-    hconvt_default = hip_ops.get_option("hconvt")
     res = {}
-    try:
-        hip_ops.set_option("hconvt", 1)
+    with hip_ops.options(hconvt=1):
         ref = RefOps()
         for name, ops, d in (("ref", ref, "cpu"), ("hip", hip_ops, dev)):
             yd, g2d = y.to(d), None if g2 is None else g2.to(d)
@@ -706,8 +680,6 @@ def test_parity_class_dgrad_with_fused_norm_sums(hip_ops, monkeypatch, case, wit
             sums = plan[1][:N * plan[0] * 3 * C].view(N, plan[0], 3, C).sum(1)
             res[name] = (gx, gx_plain, dy_pre, dy_own, sums)
         torch.cuda.synchronize()
-    finally:
-        hip_ops.set_option("hconvt", hconvt_default)
     assert torch.equal(res["hip"][0], res["hip"][1]), "fusion must not change the data gradient"
     close_bf16(res["hip"][0], res["ref"][0], "dgrad vs oracle")
     close_f32(res["hip"][4], res["ref"][4], "fused partial sums", rel=3e-3)
@@ -888,7 +860,6 @@ def test_register_resident_k5_kernel(hip_ops, sizes, seg):
     and the data gradient accumulated into a slice; one column of two steps and 2 x 3 columns of nine steps (the ring of input
     planes turns over twice; with two segments the second one is a step shorter); 2 images"""
     ops = hip_ops
-    ops.set_option("hconv5_seg", seg)
     spec, N = ConvSpec("conv", 16, 16, 5, 1, 2, dims=3), 2
     low, master, bias, fpack, dpack = make_layer(spec, sizes, 31)
     g = torch.Generator().manual_seed(32)
@@ -909,16 +880,12 @@ def test_register_resident_k5_kernel(hip_ops, sizes, seg):
             o.gconv(gc, gy.to(dev), dpack.to(dev), None, G, out_co=16, accumulate=True)
         return ya, mr, G, slots
     y_ref, mr_ref, G_ref, _ = run(RefOps(), "cpu")
-    default = ops.get_option("hconv5")
-    try:
-        ops.set_option("hconv5", 1)           # (any number of boxes: the test volumes are small)
-        y5, mr5, G5, slots5 = run(ops, ops.device)
-        ops.set_option("hconv5", 0)
-        y0, mr0, G0, slots0 = run(ops, ops.device)
+    with ops.options(hconv5_seg=seg):
+        with ops.options(hconv5=1):           # (any number of boxes: the test volumes are small)
+            y5, mr5, G5, slots5 = run(ops, ops.device)
+        with ops.options(hconv5=0):
+            y0, mr0, G0, slots0 = run(ops, ops.device)
         torch.cuda.synchronize()
-    finally:
-        ops.set_option("hconv5", default)
-        ops.set_option("hconv5_seg", 0)
     assert slots5 == (sizes[0] // 4) * (sizes[1] // 16) * (sizes[2] // 16) and slots0 != slots5, (slots5, slots0)
     close_bf16(y5, y_ref, "forward (hconv5)")
     close_bf16(y5, y0.cpu(), "forward, hconv5 vs hconv_kernel")
@@ -954,15 +921,11 @@ def test_pointwise_kernels(hip_ops, chans, sizes):
             dws.append(dw)
         return y, gx, dws
     y_ref, gx_ref, dw_ref = run(RefOps(), "cpu")
-    default = ops.get_option("pwise")
-    try:
-        ops.set_option("pwise", 1)
+    with ops.options(pwise=1):
         y1, gx1, dw1 = run(ops, ops.device)
-        ops.set_option("pwise", 0)
+    with ops.options(pwise=0):
         y0, gx0, dw0 = run(ops, ops.device)
         torch.cuda.synchronize()
-    finally:
-        ops.set_option("pwise", default)
     close_bf16(y1, y_ref, "forward (pwise)")
     close_bf16(y1, y0.cpu(), "forward, pwise vs im2col")
     close_bf16(gx1, gx_ref, "data gradient (pwise)")
@@ -985,16 +948,12 @@ def test_one_channel_volume_weight_gradient(hip_ops):
     ref = torch.full((spec.P * spec.T * spec.Q,), 0.5, dtype=torch.float32)
     RefOps().wgrad(low.wgrad, gy, x, ref)
     out = {}
-    default = ops.get_option("hwgrad2")
-    try:
-        for v in (2, 2, 1):
-            ops.set_option("hwgrad2", v)
+    for v in (2, 2, 1):
+        with ops.options(hwgrad2=v):
             dw = torch.full((spec.P * spec.T * spec.Q,), 0.5, dtype=torch.float32, device=ops.device)
             ops.wgrad(low.wgrad, gy.to(ops.device), x.to(ops.device), dw)
             torch.cuda.synchronize()
             out.setdefault(v, []).append(dw.cpu())
-    finally:
-        ops.set_option("hwgrad2", default)
     assert torch.equal(out[2][0], out[2][1]), "two runs must be bit-identical"
     close_f32(out[2][0], ref, "one-channel volume weight gradient vs oracle")
     close_f32(out[2][0], out[1][0], "vs the im2col kernel", rel=1e-3)
@@ -1029,15 +988,11 @@ def test_persistent_narrow_volume_kernel(hip_ops, case):
             o.gconv(gc, gy.to(dev), dpack.to(dev), None, G, out_co=cin, accumulate=True)
         return ya, mr, G
     y_ref, mr_ref, G_ref = run(RefOps(), "cpu")
-    default = ops.get_option("hconv2")
-    try:
-        ops.set_option("hconv2", 4)           # (>= 3 / 4: a 32- / 64-channel layer on 64 boxes runs as two / four 16-channel groups per box)
+    with ops.options(hconv2=4):           # (>= 3 / 4: a 32- / 64-channel layer on 64 boxes runs as two / four 16-channel groups per box)
         y2, mr2, G2 = run(ops, ops.device)
-        ops.set_option("hconv2", 0)
+    with ops.options(hconv2=0):
         y0, mr0, G0 = run(ops, ops.device)
         torch.cuda.synchronize()
-    finally:
-        ops.set_option("hconv2", default)
     close_bf16(y2, y_ref, "forward (hconv2)")
     close_bf16(y2, y0.cpu(), "forward, hconv2 vs hconv2 = 0")
     close_f32(mr2, mr_ref, "mean / rstd (hconv2)", rel=1e-3)
@@ -1066,10 +1021,8 @@ def test_one_tap_parity_classes(hip_ops, case):
     fwd_multi, dg_multi = len(low.fwd) == 8, len(low.dgrad) == 8
     assert fwd_multi or dg_multi
     res = {}
-    default = ops.get_option("pwise")
-    try:
-        for on in (1, 0):
-            ops.set_option("pwise", on)
+    for on in (1, 0):
+        with ops.options(pwise=on):
             out = {}
             if fwd_multi:
                 slots, offs = stats_slots(ops, low, low.fwd, N)
@@ -1085,8 +1038,6 @@ def test_one_tap_parity_classes(hip_ops, case):
                 out["gx"] = gx.cpu()
             torch.cuda.synchronize()
             res[on] = out
-    finally:
-        ops.set_option("pwise", default)
     ref = RefOps()
     if fwd_multi:
         yr = torch.zeros(N, *low.out_dims, spec.cout_p, dtype=torch.bfloat16)
@@ -1567,14 +1518,10 @@ def test_fused_adam_plan_follows_the_options(hip_ops):
         torch.cuda.synchronize()
         return launched, [t.cpu() for t in (p, m, v, pack)]
     assert run(True)[0], "case must take the fused launch"          # (its plan is cached now)
-    default = ops.get_option("wgrad_rows")
-    try:
-        ops.set_option("wgrad_rows", 0)
+    with ops.options(wgrad_rows=0):
         launched, out = run(True)
         assert not launched, "wgrad_rows = 0: the layer must not take the fused launch"
         assert torch.equal(out[0], p0) and torch.equal(out[1], m0) and torch.equal(out[2], v0), "nothing may be launched"
-    finally:
-        ops.set_option("wgrad_rows", default)
     launched, fused = run(True)
     assert launched, "the option restored: the fused launch again"
     plain = run(False)[1]
@@ -1875,17 +1822,13 @@ def test_weight_gradient_rows_through_lds(hip_ops, case, misalign):
     n = spec.P * spec.T * spec.Q
     pre = torch.randn(n + 4, generator=g)
     outs = {}
-    default = hip_ops.get_option("wgrad_rows")
-    try:
-        for on in (1, 0):
-            hip_ops.set_option("wgrad_rows", on)
+    for on in (1, 0):
+        with hip_ops.options(wgrad_rows=on):
             buf = pre.clone().to(dev)
             dw = buf[misalign:misalign + n]
             hip_ops.wgrad(low.wgrad, a, gt, dw)
             torch.cuda.synchronize()
             outs[on] = buf.cpu()
-    finally:
-        hip_ops.set_option("wgrad_rows", default)
     assert torch.equal(outs[1], outs[0]), "row epilogue vs accumulator-layout epilogue"
     assert torch.equal(outs[1][:misalign], pre[:misalign]) and torch.equal(outs[1][misalign + n:], pre[misalign + n:])
     ref = pre.clone()
@@ -2113,36 +2056,32 @@ def test_persistent_im2col_kernel(hip_ops, case):
     x = torch.randn(N, H, W, g0.Ci, generator=g).to(torch.bfloat16).to(dev)
     packs = torch.stack([fpack_a, fpack_b]).to(dev)
     biases = torch.stack([bias_a, bias_b]).to(dev)
-    default = hip_ops.get_option("gconv_persist")
 
     def run(persist, twin, act, with_stats):
-        hip_ops.set_option("gconv_persist", persist)
-        slots = hip_ops.stat_slots(g0, N, twin=twin) if twin else hip_ops.stat_slots(g0, N)
-        y = torch.full((N, *low.out_dims, g0.Co), 7.0, dtype=torch.bfloat16, device=dev)
-        part = torch.full((N * slots * 2 * g0.Co,), float("nan"), dtype=torch.float32, device=dev)
-        pack, bias = (Twin(packs[0], packs[1]), Twin(biases[0], biases[1])) if twin else (packs[0], biases[0])
-        if with_stats:
-            hip_ops.gconv(g0, x, pack, bias, y, act=act, stats=part, stats_slots=slots)
-        else:
-            hip_ops.gconv(g0, x, pack, bias, y, act=act)
-        torch.cuda.synchronize()
+        with hip_ops.options(gconv_persist=persist):
+            slots = hip_ops.stat_slots(g0, N, twin=twin) if twin else hip_ops.stat_slots(g0, N)
+            y = torch.full((N, *low.out_dims, g0.Co), 7.0, dtype=torch.bfloat16, device=dev)
+            part = torch.full((N * slots * 2 * g0.Co,), float("nan"), dtype=torch.float32, device=dev)
+            pack, bias = (Twin(packs[0], packs[1]), Twin(biases[0], biases[1])) if twin else (packs[0], biases[0])
+            if with_stats:
+                hip_ops.gconv(g0, x, pack, bias, y, act=act, stats=part, stats_slots=slots)
+            else:
+                hip_ops.gconv(g0, x, pack, bias, y, act=act)
+            torch.cuda.synchronize()
         return y, part
-    try:
-        for twin in (False, True):
-            if twin and not hip_ops.twin_native(g0, N):
-                continue
-            for act, with_stats in (("none", True), ("lrelu", False), ("relu", True)):
-                y0, p0 = run(0, twin, act, with_stats)
-                y1, p1 = run(1000, twin, act, with_stats)
-                assert torch.equal(y0, y1), (twin, act, "outputs differ from the one-tile-per-workgroup kernel")
-                if with_stats:
-                    assert not torch.isnan(p1).any() and torch.equal(p0, p1), (twin, act, "statistics slots differ")
-        y_ref = torch.zeros(N, *low.out_dims, g0.Co, dtype=torch.bfloat16)
-        RefOps().gconv(g0, x.cpu(), fpack_a, bias_a, y_ref)
-        y1, _ = run(1000, False, "none", False)
-        close_bf16(y1, y_ref, "persistent kernel vs oracle")
-    finally:
-        hip_ops.set_option("gconv_persist", default)
+    for twin in (False, True):
+        if twin and not hip_ops.twin_native(g0, N):
+            continue
+        for act, with_stats in (("none", True), ("lrelu", False), ("relu", True)):
+            y0, p0 = run(0, twin, act, with_stats)
+            y1, p1 = run(1000, twin, act, with_stats)
+            assert torch.equal(y0, y1), (twin, act, "outputs differ from the one-tile-per-workgroup kernel")
+            if with_stats:
+                assert not torch.isnan(p1).any() and torch.equal(p0, p1), (twin, act, "statistics slots differ")
+    y_ref = torch.zeros(N, *low.out_dims, g0.Co, dtype=torch.bfloat16)
+    RefOps().gconv(g0, x.cpu(), fpack_a, bias_a, y_ref)
+    y1, _ = run(1000, False, "none", False)
+    close_bf16(y1, y_ref, "persistent kernel vs oracle")
 
 
 @pytest.mark.parametrize("case", [
@@ -2167,11 +2106,9 @@ def test_persistent_im2col_kernel_fused_sums(hip_ops, case, with_g2, act):
     part = torch.stack([y.float().sum((1, 2)), (y.float() ** 2).sum((1, 2))], 1).reshape(-1).contiguous()
     mr = torch.empty(N * 2 * C, dtype=torch.float32, device=dev)
     hip_ops.inorm_finalize(part, N, 1, C, y.numel() // (N * C), mr)
-    default = hip_ops.get_option("gconv_persist")
     res = []
-    try:
-        for persist in (0, 1000):
-            hip_ops.set_option("gconv_persist", persist)
+    for persist in (0, 1000):
+        with hip_ops.options(gconv_persist=persist):
             plan = hip_ops.fused_norm_plan(gc, N, C, force=True)
             assert plan is not None
             plan[1].fill_(float("nan"))
@@ -2181,8 +2118,6 @@ def test_persistent_im2col_kernel_fused_sums(hip_ops, case, with_g2, act):
                                 "fold_mode": spec.pad_mode if f else "reflect", "act": act, "slope": 0.2})
             torch.cuda.synchronize()
             res.append((gx, plan[1][:N * plan[0] * 3 * C].clone()))
-    finally:
-        hip_ops.set_option("gconv_persist", default)
     assert torch.equal(res[0][0], res[1][0]), "data gradient differs"
     assert not torch.isnan(res[1][1]).any() and torch.equal(res[0][1], res[1][1]), "fused sums differ"
 
@@ -2221,12 +2156,9 @@ def test_persistent_parity_class_kernel(hip_ops, monkeypatch, case):
     biases = torch.stack([bias_a, bias_b]).to(dev)
     fwd_multi, dg_multi = len(low.fwd) == 4, len(low.dgrad) == 4
     assert fwd_multi or dg_multi
-    defaults = {k: hip_ops.get_option(k) for k in ("hconvt", "hconvt_persist")}
     res = {}
-    try:
-        hip_ops.set_option("hconvt", 1)
-        for persist in (0, 1):
-            hip_ops.set_option("hconvt_persist", persist)
+    for persist in (0, 1):
+        with hip_ops.options(hconvt=1, hconvt_persist=persist):
             out = []
             for twin in (False, True):
                 if fwd_multi:
@@ -2261,9 +2193,6 @@ def test_persistent_parity_class_kernel(hip_ops, monkeypatch, case):
                     out += [gxf, sums]
             torch.cuda.synchronize()
             res[persist] = out
-    finally:
-        for k, v in defaults.items():
-            hip_ops.set_option(k, v)
     assert len(res[0]) == len(res[1]) and len(res[0]) >= 2
     for i, (a, b) in enumerate(zip(res[0], res[1])):
         assert torch.equal(a, b), f"result {i} differs between one tile per workgroup and the persistent form"

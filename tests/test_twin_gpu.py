@@ -118,9 +118,7 @@ def test_twin_boundary_convs_on_the_strip_kernels(hip_ops, case, regs):
     dev = hip_ops.device
     low, _, bias_a, fpack_a, dpack_a = make_layer(spec, (H, W), 311)
     _, _, bias_b, fpack_b, dpack_b = make_layer(spec, (H, W), 312)
-    default = hip_ops.get_option("hstrip_regs")
-    hip_ops.set_option("hstrip_regs", regs)
-    try:
+    with hip_ops.options(hstrip_regs=regs):
         g = torch.Generator().manual_seed(9)
         for cls, pa, pb, ba, bb, with_stats in ((low.fwd[0], fpack_a, fpack_b, bias_a, bias_b, True),
                                                 (low.fwd[0], fpack_a, fpack_b, bias_a, bias_b, False),
@@ -149,8 +147,6 @@ def test_twin_boundary_convs_on_the_strip_kernels(hip_ops, case, regs):
             if with_stats:
                 want = torch.cat([p_a, p_b])
                 assert (p_tw - want).abs().max().item() <= 1e-5 * want.abs().max().item(), "statistics differ"
-    finally:
-        hip_ops.set_option("hstrip_regs", default)
 
 
 @pytest.mark.parametrize("case", [
@@ -203,14 +199,10 @@ def test_many_tiles_per_workgroup_equal_one_tile_each(hip_ops, persist):
     low, _, bias, fpack, _ = make_layer(spec, (H, W), 7)
     g = torch.Generator().manual_seed(8)
     x = torch.randn(N, H, W, C, generator=g).to(torch.bfloat16)
-    default = hip_ops.get_option("hconvw_persist")
-    try:
-        hip_ops.set_option("hconvw_persist", persist)
+    with hip_ops.options(hconvw_persist=persist):
         y = torch.zeros(N, H, W, C, dtype=torch.bfloat16, device=dev)
         hip_ops.gconv(low.fwd[0], x.to(dev), fpack.to(dev), bias.to(dev), y, act="relu")
         torch.cuda.synchronize()
-    finally:
-        hip_ops.set_option("hconvw_persist", default)
     ref = RefOps()
     y_ref = torch.zeros(N, H, W, C, dtype=torch.bfloat16)
     ref.gconv(low.fwd[0], x, fpack, bias, y_ref, act="relu")

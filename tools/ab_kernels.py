@@ -65,17 +65,16 @@ def main():
     times = {s: [] for s in settings}
     for r in range(args.rounds):
         for s in settings:
-            for n, v in zip(names, s):
-                ops.set_option(n, v)
-            for _ in range(3):
-                run()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(args.iters):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
+            with ops.options(**dict(zip(names, s))):
+                for _ in range(3):
+                    run()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(args.iters):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
             times[s].append(e0.elapsed_time(e1) / args.iters * 1e3)
     for s in settings:
         t = times[s]

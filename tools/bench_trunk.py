@@ -83,9 +83,8 @@ def main():
     for label, make in (("forward", fwd), ("dgrad (ring, fused sums)", ring), ("dgrad + norm apply, 2 launches", ring_then_apply)):
         t1 = timed(make(N, False), args.iters)
         t2 = timed(make(2 * N, True), args.iters)
-        ops.set_option("hconvw_persist", 0)
-        t3 = timed(make(2 * N, True), args.iters)
-        ops.set_option("hconvw_persist", 1)
+        with ops.options(hconvw_persist=0):
+            t3 = timed(make(2 * N, True), args.iters)
         rows.append((label, t1, t2, t3))
         print(f"{label:28s} single batch {N}: {t1:6.1f} us ({flop / t1 * 1e-6:5.0f} TFLOP/s) | twin 2 x {N}: {t2:6.1f} us = "
               f"{t2 / 2:5.1f} per network ({2 * flop / t2 * 1e-6:5.0f} TFLOP/s) | twin, one tile per workgroup: {t3:6.1f} us = "
