@@ -7,8 +7,11 @@ wrapper (cut.py:205-211) — here the encoder passes are partial passes of the s
 land in the same flat buffer and are all-reduced with it; the `mlp` optimiser state is checkpointed too.
 
 The encoder-only passes do not materialise NCHW feature maps: a "patch" is one pixel's channel vector, i.e. one
-contiguous row of the NHWC activation, so the sampled patches are gathered straight out of the executor's
-activations (Resnet2D.extract_patch_features) and their gradients scattered straight back."""
+contiguous row of the channels-last activation, so the sampled patches are gathered straight out of the executor's
+activations (Resnet2D / Vnet3D.extract_patch_features) and their gradients scattered straight back. Patch ids are flat
+over the level's spatial shape in row-major order — (H, W) or (D, H, W), the reference's permute(0, 2, 3, [4,] 1).flatten
+(cut.py:252-257) — so the recipe is the same for images and volumes; generators with an `encoder` are Resnet2D and the
+V-Nets, as in the reference (resnet2d.py:46, vnet3d.py:88, vnet2d.py:79, selfattention_vnet3d.py:116)."""
 from dataclasses import dataclass, field
 from typing import Tuple
 
@@ -71,7 +74,13 @@ class CUT(BaseGAN):
         super().init_networks()           # builds G and D; 'mlp' matches neither prefix and is built here
         if self.is_train:
             G = self.networks["G"]
-            channels = [G.encoder_tap(e)[1] for e in self.nce_layers]
+            # the listed layers that exist: the V-Nets mirror the reference's `>=` assert, under which the brats cut.yaml's
+            # five indices give four feature levels and four MLPs (cut.py:301,316-331) while the loss is still divided by
+            # len(nce_layers) (cut.py:226; the criterion of the missing level is dropped by zip, :219-220)
+            self.tap_layers = G.encoder_layers(self.nce_layers)
+            n_tap, n_all = len(self.tap_layers), len(self.nce_layers)
+            self._nce_weight = self.lambda_nce if n_tap == n_all else self.lambda_nce * n_tap / n_all
+            channels = [G.encoder_tap(e)[1] for e in self.tap_layers]
             mlp = FeaturePatchMLP(channels, self.num_patches, self.conf.train.gan.mlp_nc)
             mlp.init_weights(self.conf.train.gan.weight_init_type, self.conf.train.gan.weight_init_gain)
             self.networks["mlp"] = mlp
@@ -190,13 +199,13 @@ class CUT(BaseGAN):
             combined_loss = out[-1]
         self.backward(loss=combined_loss, optimizer=(self.optimizers["G"], self.optimizers["mlp"]), loss_id=1)
 
-    def sample_patch_ids(self, H, W):
-        """one torch.randperm per feature level, in level order — the RNG call sequence of FeaturePatchMLP.forward on
-        the source features (cut.py:262-268)"""
+    def sample_patch_ids(self, *sizes):
+        """one torch.randperm per existing feature level, in level order — the RNG call sequence of
+        FeaturePatchMLP.forward on the source features (cut.py:262-268); sizes = the input's spatial shape"""
         G = self.networks["G"]
         ids = []
-        for e in self.nce_layers:
-            n = G.tap_extent(e, H, W)
+        for e in self.tap_layers:
+            n = G.tap_extent(e, *sizes)
             pid = torch.randperm(n, device=self.device)
             ids.append(pid[:int(min(self.num_patches, n))] if self.num_patches > 0 else torch.arange(n, device=self.device))
         return ids
@@ -217,11 +226,12 @@ class CUT(BaseGAN):
         host = torch.tensor([int(self.is_flipped)], dtype=torch.int32)
         self._flip_flag.copy_(host.pin_memory() if self._flip_flag.is_cuda else host, non_blocking=True)
 
-    def _flipped_ids(self, ids, H, W):
-        """patch ids of the target features when the inputs were flipped along W (cut.py:213-215 flips the features back)"""
+    def _flipped_ids(self, ids, *sizes):
+        """patch ids of the target features when the inputs were flipped along the last axis (cut.py:213-215 flips the
+        features back): the id's position in its row is mirrored, the row — (y) or (z, y) — stays"""
         G, out = self.networks["G"], []
-        for e, pid in zip(self.nce_layers, ids):
-            w = G.tap_dims(e, H, W)[1]          # the generator knows its own feature widths
+        for e, pid in zip(self.tap_layers, ids):
+            w = G.tap_dims(e, *sizes)[-1]       # the generator knows its own feature widths
             out.append((pid // w) * w + (w - 1 - pid % w))
         return out
 
@@ -229,11 +239,11 @@ class CUT(BaseGAN):
         super()._prepare_host_state()
         if self.use_equivariance_flip and self.is_train:
             self._draw_flip()
-        H, W = self.visuals["real_A"].shape[-2:]
-        drawn = [self.sample_patch_ids(H, W) for _ in range(self._nce_calls_per_step())]      # the step's own draw order
+        sizes = tuple(self.visuals["real_A"].shape[2:])
+        drawn = [self.sample_patch_ids(*sizes) for _ in range(self._nce_calls_per_step())]    # the step's own draw order
         # (the targets' ids: the same, or mirrored along W when this iteration's inputs are flipped — data of static tensors
         # either way, so the captured launches do not change)
-        tgt = [self._flipped_ids(c, H, W) if (self.use_equivariance_flip and self.is_flipped) else c for c in drawn]
+        tgt = [self._flipped_ids(c, *sizes) if (self.use_equivariance_flip and self.is_flipped) else c for c in drawn]
         if self._pid_static is None or [[t.shape for t in c] for c in self._pid_static] != [[t.shape for t in c] for c in drawn]:
             self._pid_static = [[t.clone() for t in c] for c in drawn]
             self._tid_static = [[t.clone() for t in c] for c in tgt]
@@ -252,35 +262,35 @@ class CUT(BaseGAN):
         G, mlp = self.networks["G"], self.networks["mlp"]
         src_feats, tgt_ids = [], []
         for source, _ in pairs:
-            H, W = source.shape[-2:]
+            sizes = tuple(source.shape[2:])
             if self.external_draw_ids:                        # captured / replayed iteration: ids are static tensors
                 ids, tids = self._pid_static[self._nce_call], self._tid_static[self._nce_call]
                 self._nce_call += 1
             else:
-                ids = self.sample_patch_ids(H, W)
+                ids = self.sample_patch_ids(*sizes)
                 # target features are flipped back along W before sampling (cut.py:214-215)
-                tids = self._flipped_ids(ids, H, W) if self.is_flipped else ids
-            src_feats.append(G.extract_patch_features(source, self.nce_layers, ids, detached=True))
+                tids = self._flipped_ids(ids, *sizes) if self.is_flipped else ids
+            src_feats.append(G.extract_patch_features(source, self.tap_layers, ids, detached=True))
             tgt_ids.append(tids)
-        tgt_feats = G.extract_patch_features_parts([t for _, t in pairs], self.nce_layers, tgt_ids)
-        return [mlp.nce_loss(tf, sf, source.shape[0], self.nce_T, self.lambda_nce)
+        tgt_feats = G.extract_patch_features_parts([t for _, t in pairs], self.tap_layers, tgt_ids)
+        return [mlp.nce_loss(tf, sf, source.shape[0], self.nce_T, self._nce_weight)
                 for tf, sf, (source, _) in zip(tgt_feats, src_feats, pairs)]
 
     def _calculate_nce_loss(self, source, target, patch_ids=None):
         G, mlp = self.networks["G"], self.networks["mlp"]
-        H, W = source.shape[-2:]
+        sizes = tuple(source.shape[2:])
         tgt_ids = None
         if patch_ids is None and self.external_draw_ids:          # captured / replayed iteration: ids are static tensors
             patch_ids, tgt_ids = self._pid_static[self._nce_call], self._tid_static[self._nce_call]
             self._nce_call += 1
-        ids = patch_ids if patch_ids is not None else self.sample_patch_ids(H, W)
+        ids = patch_ids if patch_ids is not None else self.sample_patch_ids(*sizes)
         # (keys are detached in the loss: read out of this iteration's recorded pass over `source` where there is one)
-        source_feats = G.extract_patch_features(source, self.nce_layers, ids, detached=True)
+        source_feats = G.extract_patch_features(source, self.tap_layers, ids, detached=True)
         if tgt_ids is None:       # target features are flipped back along W before sampling (cut.py:214-215)
-            tgt_ids = self._flipped_ids(ids, H, W) if self.is_flipped else ids
-        target_feats = G.extract_patch_features(target, self.nce_layers, tgt_ids)
+            tgt_ids = self._flipped_ids(ids, *sizes) if self.is_flipped else ids
+        target_feats = G.extract_patch_features(target, self.tap_layers, tgt_ids)
         # both MLP passes, the logits, the cross-entropy and the mean over patches and levels: one autograd node
-        return mlp.nce_loss(target_feats, source_feats, source.shape[0], self.nce_T, self.lambda_nce)
+        return mlp.nce_loss(target_feats, source_feats, source.shape[0], self.nce_T, self._nce_weight)
 
 
 class _PatchNCEFn(torch.autograd.Function):

@@ -85,6 +85,12 @@ class Resnet2D(NativeNet):
     def encoder_len(self):
         return 10 + self.n_residual_blocks
 
+    def encoder_layers(self, layers):
+        """the entries of `layers` (CUT's nce_layers) that name an encoder module: all of them, or encoder_tap raises"""
+        for e in layers:
+            self.encoder_tap(e)
+        return list(layers)
+
     def encoder_tap(self, e):
         """encoder module index -> ("pad", None) | ("y", node) | ("x", node), channels.
         The reference appends the module OUTPUT; outputs of InstanceNorm modules are later overwritten in place by the

@@ -585,6 +585,10 @@ class NativeNet:
         k = len(taps)
         return [outs[p * k:(p + 1) * k] for p in range(len(xs))]
 
+    def _tap_source(self, saved, kind, node):
+        """(channels-last buffer of a recorded pass, its live channels) that tap (kind, node) samples rows of"""
+        return (saved.ys[node] if kind == "y" else saved.acts[node + 1]), self.nodes[node].spec.cout
+
     def _forward(self, x, save, stop=None, tw=None):
         """stop = index of the last node to run (encoder-only passes of CUT, cut.py:297-312); None = whole net.
         tw = a second network of identical architecture (nn/native/twin.py): x is then the pair (xa, xb) and the pass runs
@@ -1022,8 +1026,8 @@ class _TapFn(torch.autograd.Function):
         outs, n0 = [], 0
         for np_, pids in zip(ctx.sizes, ids):
             for (kind, node), pid in zip(taps, pids):
-                src = saved.ys[node] if kind == "y" else saved.acts[node + 1]
-                outs.append(net.ops.tap_gather(src[n0:n0 + np_], pid, net.nodes[node].spec.cout))
+                src, ch = net._tap_source(saved, kind, node)
+                outs.append(net.ops.tap_gather(src[n0:n0 + np_], pid, ch))
             n0 += np_
         return tuple(outs)
 
