@@ -235,7 +235,10 @@ __device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v,
   X(HCONV2, "hconv2", 4)                       /* hconv.hip: persistent double-buffered form of the narrow volume forward / data-gradient kernel (17..64 output channels; */ \
                                                /* >= 2: also 64 -> 64 channels — wide on both sides — instead of the split-K im2col launch + its finalize; */ \
                                                /* >= 3: 32-channel layers on <= 128 boxes as two 16-channel groups per box; >= 4: 64-channel layers on <= 64 boxes as four) */ \
-  X(PWISE, "pwise", 8)                         /* pwise.hip: register-operand kernels for one-tap layers with <= 8 channels on one side (smallest volume in 2048-voxel units, 0 = off) */
+  X(PWISE, "pwise", 8)                         /* pwise.hip: register-operand kernels for one-tap layers with <= 8 channels on one side (smallest volume in 2048-voxel units, 0 = off) */ \
+  X(DAXIS, "daxis", 8192)                         /* daxis.hip: streaming kernel for layers whose taps all lie on the row axis, 8..64 channels (the (k,1,1) half of a */ \
+                                               /* separable volume conv and its data gradient): smallest launch in 64-voxel units (default: 2^19 voxels, where it measured */ \
+                                               /* 2.9 x the other kernels; a tie at 2^18 voxels x 32 channels, a loss at 2^15 x 64: DESIGN.md 4.6), 0 = off */
 enum GsOpt {
 #define GS_OPT_ENUM(id, name, def) GS_OPT_##id,
   GS_OPTIONS(GS_OPT_ENUM)

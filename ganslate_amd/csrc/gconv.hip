@@ -656,6 +656,10 @@ int gs_pwise_multi_try(const gs_gconv_desc* const* descs, int count, const void*
                        void* out, float* stats, void* stream, int* handled);
 int gs_hconv_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
                  void* stream, int* handled);
+// daxis.hip: streaming kernel for layers whose taps all lie on the row axis (the (k,1,1) half of a separable volume conv)
+int gs_daxis_slots(const gs_gconv_desc* d);
+int gs_daxis_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
+                 void* stream, int* handled);
 // hconvw.hip: halo-resident forward kernel for the wide 3x3 stride-1 layers
 int gs_hconvw_slots(const gs_gconv_desc* d);
 int gs_hconvw_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
@@ -679,6 +683,8 @@ extern "C" int gs_tile_m(const gs_gconv_desc* d) { return pick_tile(d).bm; }
 
 extern "C" int gs_gconv_stat_slots(const gs_gconv_desc* d) {
   if (!d || d->Dc < 1 || d->Hc < 1 || d->Wc < 1) return 0;
+  const int as = gs_daxis_slots(d);
+  if (as) return as;
   const int hs = gs_hconv_slots(d);
   if (hs) return hs;
   const int ws = gs_hconvw_slots(d);
@@ -702,7 +708,7 @@ extern "C" int gs_gconv_forward(const gs_gconv_desc* d, const void* in, const vo
 // floats of workspace gs_gconv_forward_ws wants for this launch (0: the launch does not split K)
 extern "C" int64_t gs_gconv_splitk_ws_floats(const gs_gconv_desc* d) {
   if (!d || d->Dc < 1 || d->Hc < 1 || d->Wc < 1 || d->Co < 1) return 0;
-  if (gs_hconv_slots(d) || gs_hconvw_slots(d) || gs_hstrip_slots(d)) return 0;
+  if (gs_daxis_slots(d) || gs_hconv_slots(d) || gs_hconvw_slots(d) || gs_hstrip_slots(d)) return 0;
   const TileCfg tc = pick_tile(d);
   const int splits = splitk_plan(d, tc, false);
   return splits > 1 ? (int64_t)splits * d->N * d->Do * d->Ho * d->Wo * d->Co : 0;
@@ -727,7 +733,7 @@ extern "C" int gs_gconv_twin_native(const gs_gconv_desc* d, const gs_gconv_fuse*
     if (fuse->fold > 0 && d->Do == fuse->Dy && d->Ho == fuse->Hy && d->Wo == fuse->Wy) return gs_gconv_ring_slots(d) > 0;
     return gs_opt(GS_OPT_GCONV_TWIN) != 0;        // padded-domain fused launch: always the im2col kernel (no split-K there)
   }
-  if (gs_hconv_slots(d)) return 0;
+  if (gs_daxis_slots(d) || gs_hconv_slots(d)) return 0;
   if (gs_hconvw_slots(d) > 0) return 1;
   // the im2col kernel picks the weight set per tile (tiles never straddle images) — unless the halves would run split-K (few
   // tiles, long K: kept, the caller owns that workspace)
@@ -786,6 +792,8 @@ static int gconv_forward_impl(const gs_gconv_desc* d, const void* in, const void
   if (!fuse) {
     int handled = 0;
     if (!tw) {
+      if (int rc = gs_daxis_try(d, in, w_pack, bias, out, stats, stream, &handled)) return rc;
+      if (handled) return 0;
       if (int rc = gs_pwise_try(d, in, w_pack, bias, out, stream, &handled)) return rc;
       if (handled) return 0;
       if (int rc = gs_hconv_try(d, in, w_pack, bias, out, stats, stream, &handled)) return rc;

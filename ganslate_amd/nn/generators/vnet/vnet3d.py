@@ -15,6 +15,15 @@ buffers (in_co / out_co of gs_gconv_desc), the norm + PReLU + residual chain is 
 place by data-gradient launches that accumulate into a slice (gs_gconv_desc.accumulate). PReLU slopes live in the flat
 master buffer behind the conv weights (`Extra`), their gradients come out of the norm-backward reductions.
 
+`is_separable=True` (ganslate/nn/separable.py:5-78 through nn/utils.py:39-50): every Conv3d above is SeparableConv3d — a
+(1,k,k) conv cin -> cout, then a (k,1,1) conv cout -> cout, both dense in channels and both biased, nothing in between — and
+every ConvTranspose3d the same split of transposed layers (state_dict: `<conv>.conv_depthwise`, `.conv_pointwise`,
+`.conv_transp_depthwise`, `.conv_transp_pointwise`). Here such a conv is two nodes behind each other, hidden behind the three
+helpers everything else goes through: `_conv` runs both launches (statistics from the second only), `_dgrad` runs them
+backwards (out / out_co / accumulate apply to the (1,k,k) launch, the one that writes into a coupling's gradient slice) and
+`_wgrad` produces both weight gradients and the (1,k,k) layer's bias gradient. Each half runs as a uniform-stride class on a
+view of the NDHWC tensor (nn/native/spec.py). Twin passes are not built for separable networks.
+
 `use_inverse=True` (RevGAN, ganslate/nn/gans/unpaired/revgan.py:120-146) adds the B->A copies of the non-invertible layers
 (in_ba, out_ba, down_conv_ba, up_conv_ba: vnet3d.py:60-69,179-181,213-214) and `forward(x, inverse=True)`: the same walk
 with those layers and every core run backwards, x2 = y2 - G(y1), x1 = y1 - F(x2) per coupling in reversed block order
@@ -27,7 +36,7 @@ first and rebuilds every coupling's input from its output with the inverse equat
 outputs F(x2), G(y1) the gradient needs — before differentiating it. Per core the live activations drop from
 O(couplings) to O(1) at the price of one extra evaluation of F and G per coupling (+1/3 of the core's work). The rebuilt
 input equals the original up to storage rounding (bf16 here, fp32 in memcnn)."""
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Tuple
 
 import torch
@@ -70,6 +79,7 @@ class Vnet3D(NativeNet):
     dims = 3
     twin_extras_ok = True        # TwinNet: the PReLU slopes (extras) are handled per network (see _tw below)
     twin_default = False         # ... but recipes pair V-Nets only on request (GS_TWIN=all): measured slower on the brats recipe
+    is_separable = False         # (class default: executors that borrow the conv helpers below — Piresnet3D — are dense)
     _tw = None                   # the second network of a twin pass while that pass is being launched: every per-network
                                  # tensor (master, packs, gradient buffer, slopes) is then a Twin and the batch holds both
                                  # networks' images, first this network's (nn/native/twin.py)
@@ -82,8 +92,12 @@ class Vnet3D(NativeNet):
         self.attention = tuple(bool(a) for a in attention) + (False,) * (len(down_blocks) - len(attention))
         self.use_inverse = bool(use_inverse)
         self.use_memory_saving = bool(use_memory_saving)
-        if is_separable:
-            raise NotImplementedError("separable convolutions are not implemented")
+        self.is_separable = bool(is_separable)
+        if self.is_separable and type(self).dims != 3:
+            raise NotImplementedError("separable convolutions exist for volumes only")
+        # twin passes of separable V-Nets are not built: TwinNet.compatible then says no and a CycleGAN pair stays two
+        # passes whatever GS_TWIN says
+        self.twin_extras_ok = not self.is_separable
         if first_layer_channels % in_channels:
             raise ValueError("`first_layer_channels` has to be divisible by `in_channels`.")
         if len(down_blocks) != len(up_blocks):
@@ -99,12 +113,25 @@ class Vnet3D(NativeNet):
 
         order = []           # parameter keys in the order the blocks register them
 
-        def add_conv(spec, norm, name, aliases=()):
+        def add_node(spec, norm, name, aliases):
             nodes.append(Node(spec, norm, "none", name=name, aliases=tuple(aliases)))
             order.append(f"{name}.weight")
             if spec.bias:
                 order.append(f"{name}.bias")
             return len(nodes) - 1
+
+        def add_conv(spec, norm, name, aliases=()):
+            """one conv of the reference net. Separable: SeparableConv3d / SeparableConvTranspose3d (nn/separable.py:5-78)
+            — two nodes behind each other, the (1,k,k) layer cin -> cout at index i and the (k,1,1) layer cout -> cout at
+            i + 1, both dense in channels and both with the bias flag; the norm follows the second"""
+            if not self.is_separable:
+                return add_node(spec, norm, name, aliases)
+            tr = "transp_" if spec.kind == "convT" else ""
+            i = add_node(replace(spec, axes="plane"), False, f"{name}.conv_{tr}depthwise",
+                         [f"{a}.conv_{tr}depthwise" for a in aliases])
+            add_node(replace(spec, cin=spec.cout, axes="axis"), norm, f"{name}.conv_{tr}pointwise",
+                     [f"{a}.conv_{tr}pointwise" for a in aliases])
+            return i
 
         def add_slope(name, size, aliases=()):
             extras.append(Extra(name, size, 0.25, tuple(aliases)))
@@ -194,27 +221,34 @@ class Vnet3D(NativeNet):
             assert all(x % (1 << self.L) == 0 for x in key), f"input {key} must be divisible by 2^{self.L}"
             lv = lambda k: tuple(x >> k for x in key)
             lows = [None] * len(self.nodes)
-            lows[self.n_in] = lower(self.nodes[self.n_in].spec, *key)
+
+            def put(i, *dims):
+                """lowers conv i at these input dims; a separable conv is nodes i and i + 1, the second on the first's output"""
+                lows[i] = lower(self.nodes[i].spec, *dims)
+                if self.is_separable:
+                    lows[i + 1] = lower(self.nodes[i + 1].spec, *lows[i].out_dims)
+
+            put(self.n_in, *key)
             if self.use_inverse:
-                lows[self.n_in_ba] = lower(self.nodes[self.n_in_ba].spec, *key)
-                lows[self.n_o1_ba] = lower(self.nodes[self.n_o1_ba].spec, *key)
-                lows[self.n_o2_ba] = lower(self.nodes[self.n_o2_ba].spec, *key)
+                put(self.n_in_ba, *key)
+                put(self.n_o1_ba, *key)
+                put(self.n_o2_ba, *key)
                 for blk in self.downs:
-                    lows[blk.conv_ba] = lower(self.nodes[blk.conv_ba].spec, *lv(blk.level - 1))
+                    put(blk.conv_ba, *lv(blk.level - 1))
                 for blk in self.ups:
-                    lows[blk.conv_ba] = lower(self.nodes[blk.conv_ba].spec, *lv(blk.level + 1))
+                    put(blk.conv_ba, *lv(blk.level + 1))
             for blk in self.downs:
-                lows[blk.conv] = lower(self.nodes[blk.conv].spec, *lv(blk.level - 1))
+                put(blk.conv, *lv(blk.level - 1))
                 for nf, _, ng, _ in blk.couplings:
-                    lows[nf] = lower(self.nodes[nf].spec, *lv(blk.level))
-                    lows[ng] = lower(self.nodes[ng].spec, *lv(blk.level))
+                    put(nf, *lv(blk.level))
+                    put(ng, *lv(blk.level))
             for blk in self.ups:
-                lows[blk.conv] = lower(self.nodes[blk.conv].spec, *lv(blk.level + 1))
+                put(blk.conv, *lv(blk.level + 1))
                 for nf, _, ng, _ in blk.couplings:
-                    lows[nf] = lower(self.nodes[nf].spec, *lv(blk.level))
-                    lows[ng] = lower(self.nodes[ng].spec, *lv(blk.level))
-            lows[self.n_o1] = lower(self.nodes[self.n_o1].spec, *key)
-            lows[self.n_o2] = lower(self.nodes[self.n_o2].spec, *key)
+                    put(nf, *lv(blk.level))
+                    put(ng, *lv(blk.level))
+            put(self.n_o1, *key)
+            put(self.n_o2, *key)
             self._low_cache[key] = lows
         return self._low_cache[key]
 
@@ -223,24 +257,35 @@ class Vnet3D(NativeNet):
         return torch.empty(N, *sizes, C, dtype=self.ops.act_dtype, device=self.device)
 
     def _conv(self, s, i, x, in_co=0, stats=True, out=None):
-        """raw output of node i (+ mean/rstd of its InstanceNorm) reading channels [in_co, in_co + cin) of x"""
+        """raw output of conv i (+ mean/rstd of its InstanceNorm) reading channels [in_co, in_co + cin) of x. Separable: the
+        (1,k,k) launch into an intermediate, then the (k,1,1) launch, which alone writes statistics; the intermediate is the
+        weight gradient's operand and is returned through s.mid[i] (rebuilt by whatever re-runs this conv)"""
+        if not self.is_separable:
+            return self._conv1(s, i, x, in_co, stats, out)
+        mid, _ = self._conv1(s, i, x, in_co, False, None)
+        s.mid[i] = mid
+        return self._conv1(s, i + 1, mid, 0, stats, out)
+
+    def _conv1(self, s, i, x, in_co=0, stats=True, out=None):
         ops, sp, lw, N = self.ops, self.nodes[i].spec, s.lows[i], s.N
         tw = self._tw
         m = self.master.detach() if tw is None else Twin(self.master.detach(), tw.master.detach())
         bias = m[self.b_off[i]:self.b_off[i] + sp.cout_p]
         fpack = (s.pk["fpack"] if tw is None else Twin(s.pk["fpack"], s.pk_tw["fpack"]))[s.pk["f_off"][i]:]
         y = out if out is not None else self._new(N, lw.out_dims, sp.cout_p)
+        xv, yv = lw.vin(x), lw.vout(y)          # (the halves of a separable conv run on views, spec.py)
         if not stats:
-            ops.gconv_classes(lw.fwd, x, fpack, bias, y, in_co=in_co)
+            ops.gconv_classes(lw.fwd, xv, fpack, bias, yv, in_co=in_co)
             return y, None
+        Nv = N * lw.out_images                  # images of the launch; a volume's statistics are the sums over its view images
         slots, offs = 0, []
         for g in lw.fwd:
             offs.append(slots)
-            slots += ops.stat_slots(g, N, twin=tw is not None, multi=lw.fwd if len(lw.fwd) > 1 else None)
-        part = torch.empty(N * slots * 2 * sp.cout_p, dtype=torch.float32, device=self.device)
-        ops.gconv_classes(lw.fwd, x, fpack, bias, y, in_co=in_co, stats=part, stats_slots=slots, stats_slot0s=offs)
+            slots += ops.stat_slots(g, Nv, twin=tw is not None, multi=lw.fwd if len(lw.fwd) > 1 else None)
+        part = torch.empty(Nv * slots * 2 * sp.cout_p, dtype=torch.float32, device=self.device)
+        ops.gconv_classes(lw.fwd, xv, fpack, bias, yv, in_co=in_co, stats=part, stats_slots=slots, stats_slot0s=offs)
         mr = torch.empty(N * 2 * sp.cout_p, dtype=torch.float32, device=self.device)
-        ops.inorm_finalize(part, N, slots, sp.cout_p, lw.out_pixels, mr)
+        ops.inorm_finalize(part, N, slots * lw.out_images, sp.cout_p, lw.out_pixels, mr)
         return y, mr
 
     def _slope(self, name, grad=False):
@@ -257,8 +302,15 @@ class Vnet3D(NativeNet):
         for cp in blk.couplings:
             Y, ya, mra, yb, mrb = self._coupling_fwd_one(s, blk, cp, X)
             saved.append(None if s.recompute else (X, Y, ya, mra, yb, mrb))
+            self._drop_mid(s, cp)
             X = Y
         return X, saved
+
+    def _drop_mid(self, s, cp):
+        """memory saving keeps nothing per coupling: the recompute that re-runs _conv yields the intermediates again"""
+        if s.recompute:
+            s.mid.pop(cp[0], None)
+            s.mid.pop(cp[2], None)
 
     def _coupling_fwd_one(self, s, blk, cp, X):
         """y1 = x1 + F(x2), y2 = x2 + G(y1); returns Y and the raw conv outputs (+ statistics) of F and G"""
@@ -288,6 +340,7 @@ class Vnet3D(NativeNet):
         for cp in reversed(blk.couplings):
             X, ya, mra, yb, mrb = self._coupling_inv_one(s, blk, cp, Y)
             saved.append(None if s.recompute else (X, Y, ya, mra, yb, mrb))
+            self._drop_mid(s, cp)
             Y = X
         return Y, saved
 
@@ -323,6 +376,7 @@ class Vnet3D(NativeNet):
         N, sizes = sum(t.shape[0] for t in xs), tuple(xs[0].shape[2:])
         s = _Saved()
         s.tw = tw
+        s.mid, s.dmid = {}, {}        # separable convs: output of the (1,k,k) launch by conv index / its gradient
         assert tw is None or not getattr(self, "_next_inverse", False), "twin passes run A -> B"
         # (the reference's encoder walk calls the modules without `inverse`: an encoder pass runs A -> B, cut.py:297-312)
         inv = s.inverse = bool(getattr(self, "_next_inverse", False)) and stop is None
@@ -481,9 +535,22 @@ class Vnet3D(NativeNet):
     # ---- backward ----------------------------------------------------------------------------------------------------
     def _wgrad(self, s, i, x_in, dy, x_co=0):
         """parameter gradients of node i: dense side / gathered side by layer kind; x_in may be a channel slice"""
+        if self.is_separable:
+            # the (k,1,1) layer: operand = the intermediate; its bias gradient is the caller's (norm backward / bias_grad of dy).
+            # The (1,k,k) layer sees the intermediate's gradient: weight gradient against x_in, bias gradient = its pixel sum
+            self._wgrad1(s, i + 1, s.mid[i], dy, 0)
+            dmid = self._dmid(s, i, dy)
+            sp = self.nodes[i].spec
+            if sp.bias:
+                self.ops.bias_grad(dmid, sp.cout_p, self._grad_buf()[self.b_off[i]:self.b_off[i] + sp.cout_p])
+            return self._wgrad1(s, i, x_in, dmid, x_co)
+        self._wgrad1(s, i, x_in, dy, x_co)
+
+    def _wgrad1(self, s, i, x_in, dy, x_co=0):
         ops, sp, lw, grad = self.ops, self.nodes[i].spec, s.lows[i], self._grad_buf()
         dw = grad[self.w_off[i]:self.w_off[i] + sp.master_numel]
         self._wgrad_written(i, self._tw)    # (every weight-gradient launch is noted, NativeNet._wgrad_written; no fresh= hint here)
+        x_in, dy = lw.vin(x_in), lw.vout(dy)
         if sp.kind == "conv":
             ops.wgrad(lw.wgrad, dy, x_in, dw, g_co=x_co)
         else:
@@ -493,14 +560,33 @@ class Vnet3D(NativeNet):
             self._tw.grad_dirty = True
 
     def _bias_slice(self, i, want_w):
+        """gradient slice of the bias in front of conv i's norm (separable: the (k,1,1) layer's)"""
+        i = i + 1 if self.is_separable else i
         sp = self.nodes[i].spec
         return self._grad_buf()[self.b_off[i]:self.b_off[i] + sp.cout_p] if (want_w and sp.bias) else None
 
+    def _dmid(self, s, i, dy):
+        """separable conv i: gradient of the intermediate = data gradient of the (k,1,1) layer, computed once per dy"""
+        ent = s.dmid.get(i)
+        if ent is None or ent[0] is not dy:
+            ent = s.dmid[i] = (dy, self._dgrad1(s, i + 1, dy))
+        return ent[1]
+
     def _dgrad(self, s, i, dy, out=None, out_co=0, accumulate=False):
+        """data gradient of conv i; out / out_co / accumulate: the launch that writes the result (separable: the (1,k,k)
+        layer's, behind the (k,1,1) layer's into a fresh intermediate gradient)"""
+        if not self.is_separable:
+            return self._dgrad1(s, i, dy, out, out_co, accumulate)
+        dmid = self._dmid(s, i, dy)
+        s.dmid.pop(i, None)
+        s.mid.pop(i, None)
+        return self._dgrad1(s, i, dmid, out, out_co, accumulate)
+
+    def _dgrad1(self, s, i, dy, out=None, out_co=0, accumulate=False):
         sp, lw = self.nodes[i].spec, s.lows[i]
         gx = out if out is not None else self._new(s.N, lw.in_dims, sp.cin_p)
         dpack = (s.pk["dpack"] if self._tw is None else Twin(s.pk["dpack"], s.pk_tw["dpack"]))[s.pk["d_off"][i]:]
-        self.ops.gconv_classes(lw.dgrad, dy, dpack, None, gx, out_co=out_co, accumulate=accumulate)
+        self.ops.gconv_classes(lw.dgrad, lw.vout(dy), dpack, None, lw.vin(gx), out_co=out_co, accumulate=accumulate)
         return gx
 
     def _block_backward(self, s, blk, rec, g, g2, g2_co, want_w):
@@ -683,8 +769,9 @@ class Vnet3D(NativeNet):
                 n0 = n1
         if want_w:
             self._wgrad(s, n_o2, s.t, gz)
-            sp = self.nodes[n_o2].spec
-            ops.bias_grad(gz, sp.cout_p, grad[self.b_off[n_o2]:self.b_off[n_o2] + sp.cout_p])
+            n_b = n_o2 + 1 if self.is_separable else n_o2       # (the bias behind which gz arrives)
+            sp = self.nodes[n_b].spec
+            ops.bias_grad(gz, sp.cout_p, grad[self.b_off[n_b]:self.b_off[n_b] + sp.cout_p])
         gt = self._dgrad(s, n_o2, gz)
         dy = torch.empty_like(s.y_o1)
         ops.pnorm_backward(gt, s.y_o1, s.mr_o1, dy, C=2 * c, slope=self._slope(s_o1), dslope=dsl(s_o1),

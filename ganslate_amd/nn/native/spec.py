@@ -53,6 +53,11 @@ class ConvSpec:
     #   "in" : input channels (dw, ci) = k*cin, produced by gs_image_unfold
     #   "out": output channels (dw, co) = k*cout on a W + 2*pad wide domain, reduced by gs_shiftadd_to_image
     wfold: str = ""
+    # One half of a (2+1)-D separable volume layer (ganslate/nn/separable.py:5-78), dims == 3 only; k / stride / pad then
+    # hold on the live axes and the other axes have kernel 1, stride 1, no padding:
+    #   "plane": kernel (1, k, k) — SeparableConv3d.conv_depthwise / SeparableConvTranspose3d.conv_transp_depthwise
+    #   "axis" : kernel (k, 1, 1) — conv_pointwise / conv_transp_pointwise
+    axes: str = ""
 
     @property
     def cin_p(self): return pad8pow2(self.k * self.cin) if self.wfold == "in" else pad8(self.cin)
@@ -61,7 +66,16 @@ class ConvSpec:
     @property
     def kw(self): return 1 if self.wfold else self.k
     @property
-    def T(self): return self.k ** (self.dims - 1) * self.kw
+    def T(self):
+        if self.axes:
+            return self.k * self.k if self.axes == "plane" else self.k
+        return self.k ** (self.dims - 1) * self.kw
+    @property
+    def kernel(self):
+        """kernel extent per spatial axis, as torch has it"""
+        if self.axes:
+            return (1, self.k, self.k) if self.axes == "plane" else (self.k, 1, 1)
+        return (self.k,) * self.dims
     @property
     def P(self): return self.cout_p if self.kind == "conv" else self.cin_p
     @property
@@ -75,12 +89,15 @@ class ConvSpec:
         return (x - 1) * self.stride - 2 * self.pad + self.k + self.out_pad
 
     def out_hw(self, *sizes) -> Tuple[int, ...]:
+        if self.axes:
+            live = (False, True, True) if self.axes == "plane" else (True, False, False)
+            return tuple(self.out_size(x) if l else x for x, l in zip(sizes, live))
         return tuple(self.out_size(x) for x in sizes)
 
     # ---- torch <-> master layout ---------------------------------------------------------------
     def torch_weight_shape(self):
         io = (self.cout, self.cin) if self.kind == "conv" else (self.cin, self.cout)
-        return io + (self.k,) * self.dims
+        return io + self.kernel
 
     def master_from_torch(self, w):
         """torch weight (OI[D]HW for conv, IO[D]HW for convT) -> padded OTI master (numpy or torch)."""
@@ -98,7 +115,7 @@ class ConvSpec:
     def torch_from_master(self, m):
         p, q = (self.cout, self.cin) if self.kind == "conv" else (self.cin, self.cout)
         m = m.reshape(self.P, self.T, self.Q)
-        shape = (p, q) + (self.k,) * self.dims
+        shape = (p, q) + self.kernel
         if self.wfold == "in":
             return m[:p, :, :self.k * q].reshape(p, self.T, self.k, q).permute(0, 3, 1, 2).reshape(shape).contiguous()
         if self.wfold == "out":
@@ -173,6 +190,28 @@ class Lowered:
     Di: int = 1
     Do: int = 1
     dgrad_dims3: Optional[Tuple[int, int, int]] = None   # (D, H, W) extent of the data-gradient tensor
+    # Halves of a separable volume layer (ConvSpec.axes) run on reshaped VIEWS of the contiguous NDHWC tensors: the classes
+    # above describe images of these spatial shapes (None: the tensor as it is). A view only regroups the leading axes, so
+    # an [N, D, H, W, C] tensor becomes [N * m, *view, C] with m = D * H * W / prod(view) view images per volume.
+    in_view: Optional[Tuple[int, ...]] = None
+    out_view: Optional[Tuple[int, ...]] = None
+
+    def vin(self, x):
+        """the layer's input-side tensor (activation, or its gradient) as the classes see it"""
+        return x if self.in_view is None else x.view(-1, *self.in_view, x.shape[-1])
+
+    def vout(self, y):
+        return y if self.out_view is None else y.view(-1, *self.out_view, y.shape[-1])
+
+    @property
+    def out_images(self):
+        """view images per volume on the output side (statistics slots are counted per view image)"""
+        if self.out_view is None:
+            return 1
+        n = 1
+        for v in self.out_view:
+            n *= v
+        return self.out_pixels // n
 
     @property
     def in_dims(self): return (self.Hi, self.Wi) if self.spec.dims == 2 else (self.Di, self.Hi, self.Wi)
@@ -204,6 +243,8 @@ def lower(spec: ConvSpec, *sizes) -> Lowered:
     """sizes = (H, W) for dims == 2, (D, H, W) for dims == 3. Every axis follows the same 1-D rule; a 2-D layer gets
     a dummy depth axis (extent 1, kernel 1, no padding)."""
     assert len(sizes) == spec.dims, f"expected {spec.dims} spatial sizes, got {sizes}"
+    if spec.axes:
+        return _lower_separable(spec, *sizes)
     k, s, p = spec.k, spec.stride, spec.pad
     T, P, Q = spec.T, spec.P, spec.Q
     wf = spec.wfold
@@ -303,6 +344,72 @@ def lower(spec: ConvSpec, *sizes) -> Lowered:
         # wgrad: dense = X, gathered = dY at (2i - p + r)
         dd, dh, dw = offs
         low.wgrad = WGrad(Hi, Wi, spec.cin_p, Ho, Wo, spec.cout_p, 2, dh, dw, "zero", Da=Di, Dg=Do, dd=dd)
+    low.fwd_index = low.fwd_index.astype(np.int32)
+    low.dgrad_index = low.dgrad_index.astype(np.int32)
+    return low
+
+
+# ---- halves of a (2+1)-D separable volume layer (ganslate/nn/separable.py) -----------------------------------------------
+# gs_gconv_desc has ONE input / output stride for all axes, so a kernel that is strided along some axes only does not fit a
+# class on the volume itself. Each half runs as a uniform-stride layer on a view of the contiguous NDHWC tensor instead:
+#   plane conv  (1,k,k) stride (1,s,s) pad (0,p,p) : the 2-D layer k x k, stride s, pad p on [N D, H, W, C]
+#   plane convT (1,2,2) stride (1,2,2)             : the 2-D transposed layer on [N D, H, W, C]
+#   axis conv   (k,1,1) stride 1, pad (p,0,0)      : conv (k,1), pad (p,0) on [N, D, H W, C]
+#   axis conv   (2,1,1) stride (2,1,1)             : VALID stride-1 conv (2,1) on N D/2 images of 2 x H W -> 1 x H W
+#   axis convT  (2,1,1) stride (2,1,1)             : stride-1 conv (2,1), pad (1,0), taps flipped, on N D images of
+#                                                    1 x H W -> 2 x H W
+# In every axis form out[o] = sum_r in[o + off_r] W[r] over the rows of a view image (zero outside it), so the data gradient
+# is the same form with the offsets negated on the swapped views and the weight gradient pairs out[o] with in[o + off_r].
+def _check_view_limits(spec, classes):
+    for g in classes:
+        if g.Di * g.Hi >= 32768 or g.Wi >= 32768 or g.Dc * g.Hc * g.Wc >= (1 << 24):
+            raise ValueError(
+                f"separable {spec.axes} layer: the view {g.Di} x {g.Hi} x {g.Wi} -> {g.Dc} x {g.Hc} x {g.Wc} exceeds the "
+                f"library's class limits (rows Di*Hi < 32768, Wi < 32768, class pixels < 2^24); for an axis layer Wi is H*W")
+
+
+def _lower_separable(spec: ConvSpec, D: int, H: int, W: int) -> Lowered:
+    assert spec.dims == 3 and spec.axes in ("plane", "axis") and not spec.wfold and spec.pad_mode == "zero", \
+        "separable halves: zero-padded volume layers"
+    k, s, p = spec.k, spec.stride, spec.pad
+    if spec.axes == "plane":
+        from dataclasses import replace
+        l2 = lower(replace(spec, dims=2, axes=""), H, W)
+        low = Lowered(spec, H, W, l2.Ho, l2.Wo, fwd=l2.fwd, fwd_index=l2.fwd_index, dgrad=l2.dgrad,
+                      dgrad_index=l2.dgrad_index, wgrad=l2.wgrad, Di=D, Do=D, in_view=(H, W), out_view=(l2.Ho, l2.Wo))
+        _check_view_limits(spec, low.fwd + low.dgrad)
+        return low
+    HW = H * W
+    T, P, Q = spec.T, spec.P, spec.Q
+    if spec.kind == "conv" and s == 1:
+        Do, rin, rout, offs = spec.out_size(D), D, spec.out_size(D), [r - p for r in range(k)]
+    elif spec.kind == "conv":
+        assert s == 2 and k == 2 and p == 0 and D % 2 == 0, "strided axis conv: kernel 2, stride 2, no padding, even depth"
+        Do, rin, rout, offs = D // 2, 2, 1, [0, 1]
+    else:
+        assert s == 2 and k == 2 and p == 0 and spec.out_pad == 0, "axis ConvTranspose: kernel 2, stride 2"
+        Do, rin, rout, offs = 2 * D, 1, 2, [0, -1]
+    low = Lowered(spec, H, W, H, W, Di=D, Do=Do, in_view=(rin, HW), out_view=(rout, HW))
+    zeros = [0] * T
+    m_conv = lambda row, t, ch: (row * T + t) * Q + ch      # master[row][t][ch]
+    m_tr = lambda row, t, ch: (ch * T + t) * Q + row        # master[ch][t][row]
+    neg = [-o for o in offs]
+    low.fwd = [GConv(rin, HW, spec.cin_p, rout, HW, spec.cout_p, rout, HW, 1, 0, 0, 1, list(offs), list(zeros), "zero", 0,
+                     spec.cout_p)]
+    low.dgrad = [GConv(rout, HW, spec.cout_p, rin, HW, spec.cin_p, rin, HW, 1, 0, 0, 1, neg, list(zeros), "zero", 0,
+                       spec.cin_p)]
+    taps = list(range(T))
+    if spec.kind == "conv":
+        low.fwd_index = _pack_index(spec.cout_p, taps, spec.cin_p, m_conv).reshape(-1)
+        low.dgrad_index = _pack_index(spec.cin_p, taps, spec.cout_p, m_tr).reshape(-1)
+        low.wgrad = WGrad(rout, HW, spec.cout_p, rin, HW, spec.cin_p, 1, list(offs), list(zeros), "zero", p_real=spec.cout)
+        low.fwd[0].co_real = spec.cout
+    else:
+        low.fwd_index = _pack_index(spec.cout_p, taps, spec.cin_p, m_tr).reshape(-1)
+        low.dgrad_index = _pack_index(spec.cin_p, taps, spec.cout_p, m_conv).reshape(-1)
+        # dense = X, gathered = dY at row (i - off_r)
+        low.wgrad = WGrad(rin, HW, spec.cin_p, rout, HW, spec.cout_p, 1, neg, list(zeros), "zero")
+    _check_view_limits(spec, low.fwd + low.dgrad)
     low.fwd_index = low.fwd_index.astype(np.int32)
     low.dgrad_index = low.dgrad_index.astype(np.int32)
     return low

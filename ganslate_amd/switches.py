@@ -45,6 +45,7 @@ LIBRARY_OPTIONS = {
     "hwgrad2": "GS_HWGRAD2",
     "hconv2": "GS_HCONV2",
     "pwise": "GS_PWISE",
+    "daxis": "GS_DAXIS",
 }
 
 # ---- host switches ---------------------------------------------------------------------------------------------------

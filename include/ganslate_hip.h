@@ -115,7 +115,9 @@ const char* gs_last_error(void);
  * hconv5 (register-resident-weights kernel for the 16 -> 16 channel k5 volume convs: smallest volume in units of 2048 voxels,
  * 0 = off), hconv5_seg (z segments per column, 0 = auto), hwgrad2 / hconv2 (double-buffered volume forms of the narrow weight
  * gradient / forward kernels), pwise (one-tap layers with <= 8 channels on one side — the V-Net's 32 -> 1 output conv — on
- * register-operand kernels: smallest volume in units of 2048 voxels, 0 = off). Every setting computes the same function (up to
+ * register-operand kernels: smallest volume in units of 2048 voxels, 0 = off), daxis (streaming kernel for stride-1 classes
+ * whose taps all lie on the row axis with 8..64 channels — the (k,1,1) half of a separable volume conv on its [N, D, H W, C]
+ * view, and its data gradient: smallest launch in units of 64 voxels, 0 = off; default 8192). Every setting computes the same function (up to
  * the fp32 summation order and, for hconvw_ring, where the bf16 rounding of the folded gradient happens); none skips work.
  * Unknown name -> non-zero. */
 int gs_set_option(const char* name, int value);
