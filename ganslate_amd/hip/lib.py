@@ -228,6 +228,12 @@ _PROTOS = {
     "gs_valmetrics_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_valmetric_masked_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gs_sw_gather": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_void_p]),
+    "gs_sw_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_sw_finalize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_patchnce_param_floats": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_work_bytes": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_forward": (C.c_int, [C.POINTER(PatchNCEDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,

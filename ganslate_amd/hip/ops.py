@@ -873,13 +873,16 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_tap_rows_sum(_ptr(g), g.numel() // g.shape[-1], g.shape[-1], _ptr(db), _stream()),
                 "gs_tap_rows_sum")
 
-    def zeros_like_act(self, t):
-        out = torch.empty_like(t)
+    def zero_fill(self, out):
+        """zeroes a dense tensor in place and returns it"""
         nbytes = out.numel() * out.element_size()
         if nbytes % 16 or out.data_ptr() % 16:
             return out.zero_()
         L.check(self.lib.gs_zero_bytes(_ptr(out), nbytes, _stream()), "gs_zero_bytes")
         return out
+
+    def zeros_like_act(self, t):
+        return self.zero_fill(torch.empty_like(t))
 
     def image_tap_gather(self, x, pid, pad):
         N, Cc, H, W = x.shape
@@ -994,6 +997,101 @@ class HipOps(TwinSplit):
         B = L.VM_BINS
         c = counts.long()
         return table, (c[..., :B], c[..., B:2 * B], c[..., 2 * B:].reshape(N, nl, B, B))
+
+    # ---- sliding-window inference (slidewin.hip) -------------------------------------------------------------
+    # The stitching of utils/sliding_window_inferer.py around a predictor. Tensors are dense fp32 [N, C, D, H, W] on the
+    # device (an image: D == 1); `table` is an int32 [n, 4] device tensor of (batch item, z, y, x) window starts in padded
+    # coordinates. Enqueued on the current stream; nothing syncs; shape errors raise ValueError before any launch.
+    @staticmethod
+    def _sw_dense(name, t, dim=5, dtype=torch.float32):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a tensor; got {type(t).__name__}")
+        if not (t.is_cuda and t.dtype == dtype and t.dim() == dim and t.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous {dim}-D {dtype} device tensor; got {tuple(t.shape)} {t.dtype} "
+                             f"on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+        return t
+
+    @classmethod
+    def _sw_table(cls, table):
+        cls._sw_dense("table", table, 2, torch.int32)
+        if table.shape[0] < 1 or table.shape[1] != 4:
+            raise ValueError(f"table: expected int32 [n >= 1, 4]; got {tuple(table.shape)}")
+        return table
+
+    @staticmethod
+    def _sw_triple(name, v, lowest):
+        v = [int(a) for a in v]
+        if len(v) != 3 or min(v) < lowest:
+            raise ValueError(f"{name}: expected three integers >= {lowest}; got {v}")
+        return v, (C.c_int32 * 3)(*v)
+
+    def sw_gather(self, x, table, roi, pad_before, cval, out=None):
+        """gs_sw_gather: the windows of `table`'s rows, [n, C, *roi], cut from x [B, C, D, H, W] as if it were padded with
+        `cval` to max(size, roi) with pad_before[k] elements in front (the padded copy is never built)."""
+        self._sw_dense("x", x)
+        self._sw_table(table)
+        roi, c_roi = self._sw_triple("roi", roi, 1)
+        pad, c_pad = self._sw_triple("pad_before", pad_before, 0)
+        B, Cc, D, H, W = x.shape
+        if any(p > max(s, r) - s for p, s, r in zip(pad, (D, H, W), roi)):
+            raise ValueError(f"pad_before {pad} exceeds max(size, roi) - size for size {(D, H, W)}, roi {roi}")
+        n = table.shape[0]
+        if out is None:
+            out = torch.empty((n, Cc, *roi), dtype=torch.float32, device=x.device)
+        elif self._sw_dense("out", out).shape != (n, Cc, *roi):
+            raise ValueError(f"out: expected {(n, Cc, *roi)}; got {tuple(out.shape)}")
+        L.check(self.lib.gs_sw_gather(_ptr(x), B, Cc, D, H, W, _ptr(table), n, c_roi, c_pad, float(cval), _ptr(out),
+                                      _stream()), "gs_sw_gather")
+        return out
+
+    def sw_accumulate(self, acc, pred, imap, table, table_host):
+        """gs_sw_accumulate: acc[b, :, window_i] += imap * pred[i] for the rows of one chunk in table order, with the host
+        loop's roundings and no atomics. acc [B, C, Dp, Hp, Wp] at the padded size, pred [n, C, *roi], imap [*roi];
+        table_host = the same rows as a CPU int32 tensor (checked against acc; sizes the launch)."""
+        self._sw_dense("acc", acc)
+        self._sw_dense("pred", pred)
+        self._sw_dense("imap", imap, 3)
+        self._sw_table(table)
+        n = table.shape[0]
+        if not (isinstance(table_host, torch.Tensor) and not table_host.is_cuda and table_host.dtype == torch.int32
+                and table_host.is_contiguous() and table_host.shape == table.shape):
+            raise ValueError(f"table_host: expected a contiguous CPU int32 tensor of shape {tuple(table.shape)}")
+        roi, c_roi = self._sw_triple("roi", imap.shape, 1)
+        B, Cc, Dp, Hp, Wp = acc.shape
+        if pred.shape != (n, Cc, *roi):
+            raise ValueError(f"pred: expected {(n, Cc, *roi)} (table rows, acc channels, imap shape); got {tuple(pred.shape)}")
+        if any(r > s for r, s in zip(roi, (Dp, Hp, Wp))):
+            raise ValueError(f"acc {(Dp, Hp, Wp)} is smaller than the window {roi}")
+        th = table_host
+        lim = torch.tensor([B - 1, Dp - roi[0], Hp - roi[1], Wp - roi[2]], dtype=torch.int32)
+        if bool((th < 0).any()) or bool((th > lim).any()):
+            raise ValueError("table_host: a window lies outside the accumulator")
+        L.check(self.lib.gs_sw_accumulate(_ptr(acc), B, Cc, Dp, Hp, Wp, _ptr(table), C.c_void_p(th.data_ptr()), n, c_roi,
+                                          _ptr(imap), _ptr(pred), _stream()), "gs_sw_accumulate")
+
+    def sw_finalize(self, acc, imap, table, size, pad_before, out=None):
+        """gs_sw_finalize: [B, C, *size] = acc[.., v + pad_before] / count(v + pad_before), count = the sum of imap over all
+        windows of `table` (every row of the call) that cover the voxel, in table order; acc at the padded size
+        max(size, roi)."""
+        self._sw_dense("acc", acc)
+        self._sw_dense("imap", imap, 3)
+        self._sw_table(table)
+        roi, c_roi = self._sw_triple("roi", imap.shape, 1)
+        size, _ = self._sw_triple("size", size, 1)
+        pad, c_pad = self._sw_triple("pad_before", pad_before, 0)
+        B, Cc = acc.shape[:2]
+        padded = tuple(max(s, r) for s, r in zip(size, roi))
+        if tuple(acc.shape[2:]) != padded:
+            raise ValueError(f"acc: expected spatial size {padded} = max(size, roi); got {tuple(acc.shape[2:])}")
+        if any(p > q - s for p, q, s in zip(pad, padded, size)):
+            raise ValueError(f"pad_before {pad} exceeds max(size, roi) - size for size {size}, roi {roi}")
+        if out is None:
+            out = torch.empty((B, Cc, *size), dtype=torch.float32, device=acc.device)
+        elif self._sw_dense("out", out).shape != (B, Cc, *size):
+            raise ValueError(f"out: expected {(B, Cc, *size)}; got {tuple(out.shape)}")
+        L.check(self.lib.gs_sw_finalize(_ptr(acc), B, Cc, *size, _ptr(table), table.shape[0], c_roi, c_pad, _ptr(imap),
+                                        _ptr(out), _stream()), "gs_sw_finalize")
+        return out
 
     # ---- optimiser -----------------------------------------------------------------------------------------
     def adam_step(self, p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, zero_grad=True):

@@ -14,7 +14,13 @@ monai/data/utils.py `dense_patch_slices` / `compute_importance_map`, MONAI 0.5-0
 
 The ganslate layer on top (kept verbatim in behaviour): a 2-D `roi_size` on a volume is broadcast to [1, H, W] and the
 network then sees [N, C, H, W] slices (`network_wrapper`, sliding_window_inferer.py:36-52). The predictor is the HIP
-generator's no-grad forward; windows of one batch go through it as ONE launch sequence (batch = sw_batch_size)."""
+generator's no-grad forward; windows of one batch go through it as ONE launch sequence (batch = sw_batch_size).
+
+On the device the stitching around the predictor runs as three HIP kernels (csrc/slidewin.hip, `HipOps.sw_gather` /
+`sw_accumulate` / `sw_finalize`): per chunk one gather (the padded input of step 1 is never built), the predictor, one
+ordered blend into the accumulator; after the last chunk one normalising pass that recomputes `count` per voxel from the
+window table instead of keeping it as a volume. Same roundings and summation order as the torch code below, which stays
+as the CPU path and as the `device_kernels=False` comparison path."""
 import math
 
 import torch
@@ -63,11 +69,23 @@ def window_starts(size, roi, overlap):
     return out
 
 
+def window_table(size, roi, overlap, batch):
+    """The windows of one call as an int32 [n, 4] tensor of (batch item, z, y, x), in the order the inferer visits them
+    (start-major, batch item inner). `size` is the padded size, max(image, roi) per axis; an image (two axes) gets z = 0."""
+    starts = window_starts(size, roi, overlap)
+    rows = [[b] + [0] * (3 - len(st)) + st for st in starts for b in range(batch)]
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 4)
+
+
 class SlidingWindowInferer:
 
-    def __init__(self, roi_size, sw_batch_size=1, overlap=0.25, mode="constant", cval=0.0):
+    def __init__(self, roi_size, sw_batch_size=1, overlap=0.25, mode="constant", cval=0.0, device_kernels=None):
+        """device_kernels: None = the HIP kernels for fp32 device tensors, the torch code otherwise; False = always the torch
+        code; True = the kernels or an error (there is no CPU form of them)."""
         self.roi_size = list(roi_size)
         self.sw_batch_size, self.overlap, self.mode, self.cval = int(sw_batch_size), float(overlap), mode, float(cval)
+        self.device_kernels = device_kernels
+        self._imaps = {}                         # (roi, mode, device) -> importance map
         if not 0 <= self.overlap < 1:
             raise ValueError("overlap must be >= 0 and < 1.")
 
@@ -84,7 +102,64 @@ class SlidingWindowInferer:
             return network(x.squeeze(dim=2), *args, **kwargs).unsqueeze(dim=2)
         return network(x, *args, **kwargs)
 
+    def _use_kernels(self, inputs):
+        if self.device_kernels is False:
+            return False
+        fits = inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() in (4, 5)
+        if self.device_kernels and not fits:
+            raise RuntimeError(f"device_kernels=True needs an fp32 image or volume batch on the GPU (got {inputs.dtype} "
+                               f"{tuple(inputs.shape)} on {inputs.device}); the kernels have no CPU form")
+        if not fits:
+            return False
+        from ..nn.native.backend import get_ops
+        loaded = hasattr(get_ops(), "sw_gather")         # the HIP backend (a missing library raises in get_ops)
+        if self.device_kernels and not loaded:
+            raise RuntimeError("device_kernels=True, but the active backend is not the HIP library")
+        return loaded
+
+    def _importance_map(self, roi, device):
+        key = (tuple(roi), self.mode, str(device))
+        if key not in self._imaps:
+            self._imaps[key] = importance_map(roi, self.mode, device)
+        return self._imaps[key]
+
     def _infer(self, inputs, predictor):
+        if self._use_kernels(inputs):
+            return self._infer_device(inputs, predictor)
+        return self._infer_torch(inputs, predictor)
+
+    def _infer_device(self, inputs, predictor):
+        """gather -> predictor -> accumulate per chunk, then finalize: what _infer_torch computes, bit for bit"""
+        from ..nn.native.backend import get_ops
+        ops = get_ops()
+        nd = inputs.dim() - 2
+        size0 = list(inputs.shape[2:])
+        roi = [r if r > 0 else s for r, s in zip(self.roi_size, size0)]          # fall_back_tuple
+        size = [max(s, r) for s, r in zip(size0, roi)]
+        pad3 = [0] * (3 - nd) + [(p - s) // 2 for p, s in zip(size, size0)]
+        roi3, size3 = [1] * (3 - nd) + roi, [1] * (3 - nd) + size
+        B = inputs.shape[0]
+        x = inputs.detach().contiguous()
+        x = x if nd == 3 else x.unsqueeze(2)
+        table_host = window_table(size, roi, self.overlap, B)
+        table = table_host.to(x.device)                                          # uploaded once per call
+        imap = self._importance_map(roi, x.device).reshape(roi3)
+        acc = None
+        for g0 in range(0, table.shape[0], self.sw_batch_size):
+            rows, rows_host = table[g0:g0 + self.sw_batch_size], table_host[g0:g0 + self.sw_batch_size]
+            win = ops.sw_gather(x, rows, roi3, pad3, self.cval)
+            pred = predictor(win if nd == 3 else win.squeeze(2)).float().contiguous()
+            if pred.dim() != nd + 2 or pred.shape[0] != win.shape[0] or list(pred.shape[2:]) != roi:
+                raise ValueError(f"the predictor returned {tuple(pred.shape)} for windows {tuple(win.shape)}")
+            pred = pred if nd == 3 else pred.unsqueeze(2)
+            if acc is None:
+                acc = ops.zero_fill(torch.empty((B, pred.shape[1], *size3), dtype=torch.float32, device=x.device))
+            ops.sw_accumulate(acc, pred, imap, rows, rows_host)
+            del win, pred                        # the chunk's buffers go back before the next gather / the result
+        out = ops.sw_finalize(acc, imap, table, [1] * (3 - nd) + size0, pad3)
+        return out if nd == 3 else out.squeeze(2)
+
+    def _infer_torch(self, inputs, predictor):
         nd = inputs.dim() - 2
         size0 = list(inputs.shape[2:])
         roi = [r if r > 0 else s for r, s in zip(self.roi_size, size0)]          # fall_back_tuple

@@ -536,6 +536,41 @@ int gs_valmetrics_masked(const float* t, const float* p, const uint8_t* const* m
                          void* stream);
 int64_t gs_valmetric_masked_scratch_bytes(int32_t N, int32_t L, int32_t P, int32_t H, int32_t W);
 
+/* ---- sliding-window (patch-wise) inference (ganslate/utils/sliding_window_inferer.py:8-52 -> monai/inferers/utils.py
+ *      sliding_window_inference; slidewin.hip) ----
+ * The stitching around a predictor that sees sw_batch_size windows at a time. Dense fp32 NCDHW tensors; an image is the
+ * D == 1 case. roi = host {rd, rh, rw}, every entry >= 1. An input of D x H x W is, in the algorithm, padded symmetrically
+ * with cval to the padded size max(size, roi) per axis; pad_before = host {z, y, x}, the part in front (the reference puts
+ * (roi - size) / 2, rounded down, there), 0 <= pad_before[k] <= max(size, roi)[k] - size[k]. table = device int32 [n][4],
+ * 16-byte aligned, one row (batch item, z, y, x) per window with the starts in padded coordinates; n >= 1. A padded sample
+ * (all channels) and a window batch item hold fewer than 2^31 elements. imap = the importance map, device [rd][rh][rw].
+ * Whatever the rows hold, no kernel writes outside the tensor it is given.
+ *
+ * gs_sw_gather: out [n][C][rd][rh][rw] = the windows of rows 0..n-1 cut from the padded input; in = the UNPADDED
+ * [B][C][D][H][W], the padded copy is never built: a coordinate in the padding (or a row whose batch item is not in
+ * [0, B)) reads cval. Every element of out is written.
+ *
+ * gs_sw_accumulate: acc[b][c][window of row i] += imap * pred[i][c] for the n rows of one chunk, in increasing i; per
+ * element one rounded multiply, then one rounded add (no fma), so acc holds the bits of the sequential host loop
+ * `for i: acc[window_i] += imap * pred[i]`. acc = [B][C][Dp][Hp][Wp] at the PADDED size (the caller zeroes it before the
+ * first chunk), pred = [n][C][rd][rh][rw]. table_host = the same n rows in host memory: they are checked against the
+ * accumulator (error code, nothing launched) and give the largest per-sample bounding box of the chunk's windows, over
+ * which the launch runs. One thread owns an accumulator element and walks the rows in order: windows of a chunk may
+ * overlap, and no atomics are used. Bitwise reproducible.
+ *
+ * gs_sw_finalize: result [B][C][D][H][W] (original size) = acc[.., v + pad_before] / count(v + pad_before), correctly
+ * rounded division, where count(q) = the sum of imap over ALL n windows of the call that cover q, added in increasing
+ * row index from zero — the bits of the host's `count[window_i] += imap`; no count buffer exists. A voxel no window covers
+ * gives 0 / 0 = NaN, as on the host. */
+int gs_sw_gather(const float* in, int32_t B, int32_t C, int32_t D, int32_t H, int32_t W, const int32_t* table, int32_t n,
+                 const int32_t* roi, const int32_t* pad_before, float cval, float* out, void* stream);
+int gs_sw_accumulate(float* acc, int32_t B, int32_t C, int32_t Dp, int32_t Hp, int32_t Wp, const int32_t* table,
+                     const int32_t* table_host, int32_t n, const int32_t* roi, const float* imap, const float* pred,
+                     void* stream);
+int gs_sw_finalize(const float* acc, int32_t B, int32_t C, int32_t D, int32_t H, int32_t W, const int32_t* table,
+                   int32_t n, const int32_t* roi, const int32_t* pad_before, const float* imap, float* result,
+                   void* stream);
+
 /* ---- PatchNCE + patch MLP of CUT (ganslate/nn/gans/unpaired/cut.py:229-294, ganslate/nn/losses/cut_losses.py:14-43) ----
  * For every feature level l: sampled patches xq[l], xk[l] are [batch*patches][channels[l]] fp32 (target = query, source =
  * key, row = image * patches + patch); FeaturePatchMLP level l = Linear(C_l, nc) - ReLU - Linear(nc, nc) - x/(||x||+1e-7);
