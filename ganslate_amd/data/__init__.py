@@ -1,5 +1,6 @@
 from .image_datasets import (PairedImageDataset, PairedImageDatasetConfig, UnpairedImageDataset,  # noqa: F401
                              UnpairedImageDatasetConfig)
 from .synthetic import (SyntheticImageDataset, SyntheticImageDatasetConfig,  # noqa: F401
-                        SyntheticMaskedImageDataset, SyntheticMaskedImageDatasetConfig)
+                        SyntheticMaskedImageDataset, SyntheticMaskedImageDatasetConfig, SyntheticSavingImageDataset,
+                        SyntheticSavingImageDatasetConfig)
 from .volume_datasets import UnpairedVolumeDataset, UnpairedVolumeDatasetConfig  # noqa: F401

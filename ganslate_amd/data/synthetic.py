@@ -4,10 +4,15 @@ no dataset can be downloaded on the target machines.
 
 `SyntheticMaskedImageDataset` yields the same samples plus `masks = {label: bool tensor of the sample's shape}`, the
 form in which the medical val / test datasets hand region masks (BODY, GTV, ...) to the validator
-(validator_tester.py:78-98): seeded boxes and balls, never empty."""
+(validator_tester.py:78-98): seeded boxes and balls, never empty.
+
+`SyntheticSavingImageDataset` yields the same samples plus a `metadata` entry and has a `save()`: the path by which the
+val / test / infer engines hand every generated tensor back to the dataset (engines/base.py save_generated_tensor)."""
 from dataclasses import dataclass, field
+from pathlib import Path
 from typing import Tuple
 
+import numpy as np
 import torch
 from torch.utils.data import Dataset
 
@@ -27,6 +32,11 @@ class SyntheticImageDatasetConfig(configs.base.BaseDatasetConfig):
 @dataclass
 class SyntheticMaskedImageDatasetConfig(SyntheticImageDatasetConfig):
     mask_labels: Tuple[str, ...] = field(default_factory=lambda: ["BODY", "GTV"])
+
+
+@dataclass
+class SyntheticSavingImageDatasetConfig(SyntheticImageDatasetConfig):
+    pass
 
 
 class SyntheticImageDataset(Dataset):
@@ -75,3 +85,19 @@ class SyntheticMaskedImageDataset(SyntheticImageDataset):
         sample = super().__getitem__(index)
         sample["masks"] = {k: self._mask(index, i) for i, k in enumerate(self.labels)}
         return sample
+
+
+class SyntheticSavingImageDataset(SyntheticImageDataset):
+    """The samples of SyntheticImageDataset for the same seed, each with `metadata = {"id": "sample_<index>", "index":
+    index}`; `save(tensor, save_dir, metadata)` writes the generated tensor as `<save_dir>/<metadata id>.npy` (fp32)."""
+
+    def __getitem__(self, index):
+        sample = super().__getitem__(index)
+        sample["metadata"] = {"id": f"sample_{int(index):04d}", "index": int(index)}
+        return sample
+
+    def save(self, tensor, save_dir, metadata):
+        path = Path(save_dir) / f"{metadata['id']}.npy"
+        path.parent.mkdir(parents=True, exist_ok=True)
+        np.save(path, tensor.detach().float().cpu().numpy())
+        return path

@@ -1,12 +1,14 @@
 """Engine bases (ganslate/engines/base.py:11-50): `BaseEngineWithInference.infer` sends a batch through the model's
 generator — patch-wise through the MONAI-free sliding-window inferer when `<mode>.sliding_window` is configured
-(window_size / batch_size / overlap / mode, padding value -1 like the reference, base.py:41-50)."""
+(window_size / batch_size / overlap / mode, padding value -1 like the reference, base.py:41-50).
+`save_generated_tensor` hands every generated sample to the dataset's own `save()` where it has one (base.py:52-87)."""
 import copy
 import logging
 from abc import ABC, abstractmethod
 from pathlib import Path
 
 from ..utils import sliding_window_inferer
+from ..utils.io import decollate
 
 
 class BaseEngine(ABC):
@@ -41,3 +43,23 @@ class BaseEngineWithInference(BaseEngine):
             return None
         return sliding_window_inferer.SlidingWindowInferer(roi_size=list(sw.window_size), sw_batch_size=sw.batch_size,
                                                            overlap=sw.overlap, mode=sw.mode, cval=-1)
+
+    def save_generated_tensor(self, generated_tensor, metadata, data_loader, idx=None, dataset_name=None):
+        """A dataset that wants the outputs stored in its own way or format defines `save(tensor, save_dir[, metadata])`;
+        it is called once per sample of the batch with `save_dir = <output_dir>/saved/[{dataset_name}/][{idx}/]` and that
+        sample's share of the collated `metadata` (left out when the batch carries none)."""
+        save_fn = getattr(data_loader.dataset, "save", None)
+        if not save_fn:
+            return
+        save_dir = self.output_dir / "saved"
+        if dataset_name is not None:
+            save_dir = save_dir / f"{dataset_name}"
+        if idx is not None:
+            save_dir = save_dir / f"{idx}"
+        if metadata:
+            metadata = decollate(metadata, batch_size=len(generated_tensor))
+        for i in range(len(generated_tensor)):
+            if metadata:
+                save_fn(tensor=generated_tensor[i], save_dir=save_dir, metadata=metadata[i])
+            else:
+                save_fn(tensor=generated_tensor[i], save_dir=save_dir)

@@ -1,7 +1,9 @@
 """Trainer — the caller of the hot path (ganslate/engines/trainer.py:11-112): constructor order (seed -> loader
 -> model -> iteration range), per-iteration sequence set_input -> optimize_parameters -> get_loggable_data ->
 [log] -> [checkpoint] -> update_learning_rate, `iters = range(1 + load_iter, 1 + n_iters + n_iters_decay)`,
-rank-0 checkpoint cadence. Timers are rank-local and synchronise the device only at logging time — the
+rank-0 checkpoint cadence. At logging time the first example of the model's visuals is written as
+`<train.output_dir>/train/images/{iter}_{names}.png` (utils/trackers.py): one grid kernel on the current stream, outside
+the captured step graph, whose output buffers the visuals of a replayed step are. Timers are rank-local and synchronise the device only at logging time — the
 reference's two per-iteration timer reduces + `.item()` (trackers/base.py:56,61) are not reproduced."""
 import logging
 import time
@@ -10,6 +12,7 @@ import torch
 
 from ..utils import communication, environment
 from ..utils.builders import build_gan, build_loader
+from ..utils.trackers import ImageWriter
 
 
 class Trainer:
@@ -36,6 +39,7 @@ class Trainer:
         self.iter_idx = 0
         self.history = []           # (iter, losses, metrics) captured at logging time
         self._t_comp, self._n_comp = 0.0, 0
+        self.writer = ImageWriter(self.conf)
         self.validator = self._init_validator()
 
     def _init_validator(self):
@@ -60,6 +64,7 @@ class Trainer:
             self._n_comp += 1
             learning_rates, losses, visuals, metrics = self.model.get_loggable_data()
             self._log_iter(learning_rates, losses, metrics)
+            self._log_visuals(visuals)
             self._save_checkpoint()
             self._perform_scheduler_step()
             self._run_validation()
@@ -86,6 +91,13 @@ class Trainer:
             t = self._t_comp / max(self._n_comp, 1) / self.conf.train.batch_size
             self.history.append((self.iter_idx, lo, me))
             self.logger.info(f"iter {self.iter_idx} | comp {t:.4f} s/img | {learning_rates} | {lo} | {me}")
+
+    def _log_visuals(self, visuals):
+        if self.iter_idx % self.conf.train.logging.freq != 0:
+            return
+        if communication.get_rank() == 0:       # one example is enough when training: no gather (training.py:28-33)
+            named = self.writer.compose(visuals, single_example=True)
+            self.writer.write_train(self.iter_idx, named)
 
     def _save_checkpoint(self):
         if communication.get_rank() == 0:

@@ -16,8 +16,13 @@ enabled metric once more per label on the device path, as `<metric>_<label>` (an
 `compute_over_input`), between the standard keys and `cycle_SSIM` as validator_tester.py:78-98 orders them. The masks are
 not denormalised; all labels of a batch go through one masked call. The host path ignores masks. The Tester writes
 `<test.output_dir>/test/metrics.csv` when `test.metrics.save_to_csv` is set: one row per sample, one column per metric,
-plus a `dataset` column with `multi_dataset`. Saving generated tensors and the W&B / TensorBoard trackers stay out of
-scope."""
+plus a `dataset` column with `multi_dataset`.
+
+Every batch's `fake_B` goes to the dataset's `save()` where it has one (BaseEngineWithInference.save_generated_tensor,
+`saved/[{dataset}/][{iter}/]`), and every sample is logged as one PNG of `real_A, fake_B, real_B` and then each mask label as
+`2 * mask - 1` side by side, a volume as its middle slice: `images/[{dataset}/]{iter}/{idx}_{name}.png` in validation,
+`images/[{dataset}/]{idx}_{name}.png` in test (utils/trackers.py; the grid is one kernel, HipOps.visuals_grid, so images are
+written on the device path only). The W&B / TensorBoard trackers stay out of scope."""
 import csv
 import inspect
 from pathlib import Path
@@ -27,6 +32,7 @@ import torch
 
 from ..utils import environment
 from ..utils.builders import build_gan, build_loader
+from ..utils.trackers import ImageWriter
 from .base import BaseEngineWithInference
 
 
@@ -71,6 +77,7 @@ class BaseValTestEngine(BaseEngineWithInference):
         self.samples = {}          # dataset name -> per-sample rows of the last run
         self.metricizer = None
         self._masks_logged = False
+        self.writer = ImageWriter(self.conf)
 
     def _init_metrics(self):
         wanted = self.conf[self.conf.mode].metrics
@@ -107,7 +114,8 @@ class BaseValTestEngine(BaseEngineWithInference):
                 denormalize = getattr(dataset, "denormalize", None)
                 over_input = bool(getattr(self.conf[self.conf.mode].metrics, "compute_over_input", False))
                 score = self._device_rows if self.on_device else self._host_rows
-                rows = score(loader, denormalize, over_input)
+                rows = score(loader, denormalize, over_input, name, current_idx)
+                self.writer.write_samples(current_idx, dataset_name=name)
                 self.samples[name] = rows
                 mean = {k: float(np.mean([r[k] for r in rows])) for k in rows[0]} if rows else {}
                 self.history.append((current_idx, name, mean))
@@ -122,13 +130,24 @@ class BaseValTestEngine(BaseEngineWithInference):
                              "path ignores the masks")
             self._masks_logged = True
 
-    def _host_rows(self, loader, denormalize, over_input):
+    def _save_and_log(self, data, loader, visuals, dataset_name, current_idx):
+        """the output side of a batch (validator_tester.py:70-78,117 + ValTestTracker.add_sample)"""
+        self.save_generated_tensor(generated_tensor=visuals["fake_B"], metadata=data.get("metadata"), data_loader=loader,
+                                   idx=current_idx, dataset_name=dataset_name)
+        visuals = dict(visuals)
+        for label, mask in data.get("masks", {}).items():
+            visuals[label] = mask.to(self.model.device).float() * 2 - 1
+        self.writer.add_samples(self.writer.compose(visuals, mid_slice_only=True))
+
+    def _host_rows(self, loader, denormalize, over_input, dataset_name=None, current_idx=None):
         rows = []
         for data in loader:
             self._log_masks(data)
             real_A = data["A"].to(self.model.device)
             with torch.no_grad():
                 fake_B = self.infer(real_A)
+            self._save_and_log(data, loader, {"real_A": real_A, "fake_B": fake_B, "real_B": data["B"]}, dataset_name,
+                               current_idx)
             pred, target, original = fake_B.detach().float().cpu(), data["B"].float(), data["A"].float()
             if denormalize:
                 pred, target = denormalize(pred.clone()), denormalize(target.clone())
@@ -144,7 +163,7 @@ class BaseValTestEngine(BaseEngineWithInference):
                 rows.append(row)
         return rows
 
-    def _device_rows(self, loader, denormalize, over_input):
+    def _device_rows(self, loader, denormalize, over_input, dataset_name=None, current_idx=None):
         """per-batch device tables, one host copy per dataset (validator_tester.py:62-112)"""
         m = self.metricizer
         tables, originals, cycles = [], [], []
@@ -154,6 +173,8 @@ class BaseValTestEngine(BaseEngineWithInference):
             with torch.no_grad():
                 fake_B = self.infer(real_A)
                 target = data["B"].to(self.model.device)
+                self._save_and_log(data, loader, {"real_A": real_A, "fake_B": fake_B, "real_B": target}, dataset_name,
+                                   current_idx)
                 pred, target, original = fake_B.detach().float(), target.float(), real_A.float()
                 if denormalize:
                     pred, target = denormalize(pred.clone()), denormalize(target.clone())

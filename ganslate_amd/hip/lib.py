@@ -12,6 +12,7 @@ ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
 VM_FLAGS = {"ssim": 1, "hist": 2}     # GS_VM_SSIM, GS_VM_HIST
 VM_BINS = 100
 VM_MAX_LABELS = 8                       # GS_VM_MAX_LABELS
+VIS_MAX_SRCS = 16                       # GS_VIS_MAX_SRCS
 
 
 class GConvDesc(C.Structure):
@@ -234,6 +235,9 @@ _PROTOS = {
                                    C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_sw_finalize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_visuals_grid_u8": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p]),
     "gs_patchnce_param_floats": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_work_bytes": (C.c_int64, [C.POINTER(PatchNCEDesc)]),
     "gs_patchnce_forward": (C.c_int, [C.POINTER(PatchNCEDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,

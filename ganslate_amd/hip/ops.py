@@ -1093,6 +1093,80 @@ class HipOps(TwinSplit):
                                         _ptr(out), _stream()), "gs_sw_finalize")
         return out
 
+    # ---- logged image grids (visgrid.hip) ---------------------------------------------------------------------
+    @staticmethod
+    def visuals_plan(visuals, multi_modality_split=None):
+        """The host side of the reference's process_visuals_for_logging (trackers/utils.py): drops the `None` entries and
+        splits multi-modality tensors channel-wise as `_split_multimodal_visuals` does (`real_A` -> `real_A1`, `real_A2`
+        for a split {"A": [c1, c2]}; a `_A` / `_B` name that ends with no domain of the split is left out, as there; names
+        without `_A` / `_B`, the masks, pass). Returns [(name, tensor, first channel, channels)]: a split is an offset into
+        the same tensor, never a copy. Needs no GPU."""
+        visuals = {k: v for k, v in visuals.items() if v is not None}
+        plan = []
+        for name, t in visuals.items():
+            if multi_modality_split is None or not ("_A" in name or "_B" in name):
+                plan.append((name, t, 0, int(t.shape[1])))
+                continue
+            for domain in multi_modality_split:
+                if not name.endswith(domain):
+                    continue
+                split = multi_modality_split[domain]
+                if split is None:            # a split may be given for one of the two domains only
+                    plan.append((name, t, 0, int(t.shape[1])))
+                    continue
+                split = tuple(int(c) for c in split)
+                if sum(split) != t.shape[1]:
+                    raise ValueError("Please specify channel-split correctly!")
+                first = 0
+                for i, c in enumerate(split):
+                    plan.append((f"{name}{i + 1}", t, first, c))
+                    first += c
+        return plan
+
+    def visuals_grid(self, visuals, *, single_example=False, mid_slice_only=False, multi_modality_split=None, out=None):
+        """gs_visuals_grid_u8: the image the reference logs for an ordered {name: tensor} of visuals ([N, C, H, W] or
+        [N, C, D, H, W], dense fp32 on the device, values in [-1, 1]): the visuals side by side along the width, the slices of
+        a volume stacked along the height (or the middle slice, D // 2, with `mid_slice_only`), gray replicated to RGB.
+        Returns ("-".join(names), uint8 device tensor [n, Hout, K * W, 3]) with n = 1 for `single_example`, else N. One
+        launch on the current stream; nothing syncs; ValueError before any launch."""
+        plan = self.visuals_plan(visuals, multi_modality_split)
+        if not plan:
+            raise ValueError("visuals_grid: no visuals")
+        if len(plan) > L.VIS_MAX_SRCS:
+            raise ValueError(f"visuals_grid: at most {L.VIS_MAX_SRCS} visuals (after the modality split); got {len(plan)}")
+        shape = None
+        for name, t, _, c in plan:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: expected a tensor; got {type(t).__name__}")
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() in (4, 5) and t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous 4-D or 5-D torch.float32 device tensor; got {tuple(t.shape)} "
+                                 f"{t.dtype} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+            if c not in (1, 3):
+                raise ValueError(f"{name}: a visual holds 1 or 3 channels; got {c}")
+            if shape is None:
+                shape = (t.shape[0], *t.shape[2:])
+            elif (t.shape[0], *t.shape[2:]) != shape:
+                raise ValueError(f"{name}: batch and spatial shape {(t.shape[0], *t.shape[2:])} differ from {shape} of "
+                                 f"`{plan[0][0]}`")
+        N, (D, H, W) = shape[0], (shape[1:] if len(shape) == 4 else (1, *shape[1:]))
+        if min(N, D, H, W) < 1:
+            raise ValueError(f"visuals_grid: empty visuals {shape}")
+        K, n = len(plan), 1 if single_example else N
+        slice_ = D // 2 if (mid_slice_only and len(shape) == 4) else -1
+        want = (n, H * (D if slice_ < 0 else 1), K * W, 3)
+        if out is None:
+            out = torch.empty(want, dtype=torch.uint8, device=plan[0][1].device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+                  and tuple(out.shape) == want):
+            raise ValueError(f"out: expected a contiguous torch.uint8 device tensor of shape {want}")
+        src = (C.c_void_p * K)(*[t.data_ptr() for _, t, _, _ in plan])
+        ctot = (C.c_int32 * K)(*[t.shape[1] for _, t, _, _ in plan])
+        c0 = (C.c_int32 * K)(*[f for _, _, f, _ in plan])
+        cc = (C.c_int32 * K)(*[c for _, _, _, c in plan])
+        L.check(self.lib.gs_visuals_grid_u8(src, ctot, c0, cc, K, n, N, D, H, W, slice_, _ptr(out), _stream()),
+                "gs_visuals_grid_u8")
+        return "-".join(name for name, _, _, _ in plan), out
+
     # ---- optimiser -----------------------------------------------------------------------------------------
     def adam_step(self, p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, zero_grad=True):
         bc1 = 1.0 - beta1 ** step

@@ -54,6 +54,34 @@ def shared_random_seed() -> int:
     return int(seed)
 
 
+_gloo_group = None
+
+
+def _global_gloo_group():
+    """a gloo group over all ranks for pickled host objects (communication.py:120-130): the world itself under gloo"""
+    global _gloo_group
+    if dist.get_backend() != "nccl":
+        return dist.group.WORLD
+    if _gloo_group is None:
+        _gloo_group = dist.new_group(backend="gloo")
+    return _gloo_group
+
+
+def gather(value):
+    """`value` of every rank on rank 0, as a list in rank order (communication.py:133-147, torch.distributed.gather_object);
+    the other ranks, and a run that is not distributed, get `value` itself back. For host objects: the engines gather the
+    finished byte grids of the logged images, not fp32 tensors."""
+    if get_world_size() < 2:
+        return value
+    group = _global_gloo_group()
+    if dist.get_rank() == 0:
+        gathered = [None] * get_world_size()
+        dist.gather_object(value, gathered, dst=0, group=group)
+        return gathered
+    dist.gather_object(value, dst=0, group=group)
+    return value
+
+
 def reduce_dict(d, average=True):
     """stacked reduce of a dict of 0-d tensors to rank 0 (communication.py:226-250) — ONE collective, called at
     logging time only (the reference's per-iteration timer reduces, C6, are deliberately not reproduced)."""

@@ -571,6 +571,26 @@ int gs_sw_finalize(const float* acc, int32_t B, int32_t C, int32_t D, int32_t H,
                    int32_t n, const int32_t* roi, const int32_t* pad_before, const float* imap, float* result,
                    void* stream);
 
+/* ---- the logged image grid (ganslate/utils/trackers/utils.py process_visuals_for_logging followed by
+ *      torchvision.utils.save_image; visgrid.hip) ----
+ * One kernel, one launch: K visuals side by side along the width, HWC bytes ready for a PNG encoder.
+ * src = host array of K (1..GS_VIS_MAX_SRCS) device pointers to dense fp32 [N][ctot[k]][D][H][W] tensors (an image is the
+ * D == 1 case); visual k shows the c[k] (1 or 3) channels from c0[k] on of its tensor, so a channel-wise modality split is
+ * two entries with the same pointer and no copy. ctot, c0, c = host arrays of K; all four arrays reach the kernel by value
+ * in its argument struct: the call allocates nothing on the device and uploads no table. The first n (1..N) samples are
+ * written. slice == -1 stacks all D slices along the height, slice 0 on top; slice in [0, D) shows that slice only.
+ * out = device [n][Hout][K * W][3] bytes, Hout = (slice < 0 ? D : 1) * H:
+ *   out[s][row][k * W + x][ch] = byte(src[k][s][c0[k] + (c[k] == 3 ? ch : 0)][z][y][x]), row = z * H + y or y
+ *   byte(v) = (uint8) clamp(((v + 1) / 2) * 255 + 0.5, 0, 255), every operation rounded to fp32 on its own (no fma, not
+ *   re-associated), then truncated: the bits of the separate torch ops. NaN gives 0, +inf 255, -inf 0.
+ * Every source element that appears in the image is read once (float4 where W % 4 == 0 and the line is 16-byte aligned),
+ * every output byte is written once, there is no scratch buffer; out needs no alignment. H * W, D * H and K * W must be
+ * < 2^31, D and n * K <= 65535; offsets into the tensors are 64-bit. What does not fit is rejected with a non-zero
+ * return and nothing is launched. No thread writes outside out. */
+#define GS_VIS_MAX_SRCS 16
+int gs_visuals_grid_u8(const float* const* src, const int32_t* ctot, const int32_t* c0, const int32_t* c, int32_t K,
+                       int32_t n, int32_t N, int32_t D, int32_t H, int32_t W, int32_t slice, uint8_t* out, void* stream);
+
 /* ---- PatchNCE + patch MLP of CUT (ganslate/nn/gans/unpaired/cut.py:229-294, ganslate/nn/losses/cut_losses.py:14-43) ----
  * For every feature level l: sampled patches xq[l], xk[l] are [batch*patches][channels[l]] fp32 (target = query, source =
  * key, row = image * patches + patch); FeaturePatchMLP level l = Linear(C_l, nc) - ReLU - Linear(nc, nc) - x/(||x||+1e-7);
