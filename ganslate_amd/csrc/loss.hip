@@ -221,6 +221,26 @@ extern "C" int gs_mean(const float* x, int64_t n, float* out, void* stream) {
 #define SSIM_TW 32
 __constant__ float c_gauss[11];
 
+// A1 / B1 = S1 and A2 / B2 = S2 rounded as the reference's separate torch ops round them (ssim.py:85-98): every product
+// first, then the sums. hipcc contracts a * b + c to an fma by default, which rounds 2 m1 m2 + C1 once but
+// m1 m1 + m2 m2 + C1 twice: for identical images (m1 == m2) the two then differ by an ulp, S = 2 - S1 - S2 is +-1.2e-7
+// instead of 0 and the backward multiplies by 1 / (2 sqrt(S)). Without contraction 2 m1 m2 and m1 m1 + m2 m2 are the same
+// doubling of one rounded product, 2 s12 equals s1sq + s2sq bit for bit, S is exactly 0 and no gradient passes. The forward
+// and the gradient maps share this body, so they agree on which pixels have S > 0.
+struct SsimTerms { float A1, B1, A2, B2; };
+__device__ __forceinline__ SsimTerms ssim_terms(float m1, float m2, float xx, float yy, float xy) {
+#pragma clang fp contract(off)
+  const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+  const float m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
+  const float s1sq = xx - m11, s2sq = yy - m22, s12 = xy - m12;
+  SsimTerms t;
+  t.A1 = 2.f * m12 + C1;
+  t.B1 = (m11 + m22) + C1;
+  t.A2 = 2.f * s12 + C2;
+  t.B2 = (s1sq + s2sq) + C2;
+  return t;
+}
+
 __global__ __launch_bounds__(256) void ssim_kernel(const float* x, const float* y, int H, int W, int tiles_w,
                                                    int tiles_h, float* partial) {
   __shared__ float sx[SSIM_TH + 10][SSIM_TW + 10];
@@ -264,11 +284,8 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* x, const float* 
         m1 += g * hz[0][r + k][c]; m2 += g * hz[1][r + k][c]; xx += g * hz[2][r + k][c];
         yy += g * hz[3][r + k][c]; xy += g * hz[4][r + k][c];
       }
-      const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-      const float s1sq = xx - m1 * m1, s2sq = yy - m2 * m2, s12 = xy - m1 * m2;
-      const float S1 = (2.f * m1 * m2 + C1) / (m1 * m1 + m2 * m2 + C1);
-      const float S2 = (2.f * s12 + C2) / (s1sq + s2sq + C2);
-      const float S = fmaxf(2.f - (S1 + S2), 0.f);
+      const SsimTerms t = ssim_terms(m1, m2, xx, yy, xy);
+      const float S = fmaxf(2.f - (t.A1 / t.B1 + t.A2 / t.B2), 0.f);
       acc += sqrtf(S);
     }
   }
@@ -368,10 +385,8 @@ __global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, con
         m1 += g * hz[0][r + k][c]; m2 += g * hz[1][r + k][c]; xx += g * hz[2][r + k][c];
         yy += g * hz[3][r + k][c]; xy += g * hz[4][r + k][c];
       }
-      const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-      const float s1sq = xx - m1 * m1, s2sq = yy - m2 * m2, s12 = xy - m1 * m2;
-      const float A1 = 2.f * m1 * m2 + C1, B1 = m1 * m1 + m2 * m2 + C1;
-      const float A2 = 2.f * s12 + C2, B2 = s1sq + s2sq + C2;
+      const SsimTerms t = ssim_terms(m1, m2, xx, yy, xy);
+      const float A1 = t.A1, B1 = t.B1, A2 = t.A2, B2 = t.B2;
       const float S = 2.f - (A1 / B1 + A2 / B2);
       float g0 = 0.f, g1 = 0.f, g2 = 0.f;
       if (S > 0.f) {

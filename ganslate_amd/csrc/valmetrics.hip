@@ -168,6 +168,19 @@ __device__ __forceinline__ void vm_row7(const float (*st)[VM_TW + 6], const floa
   }
 }
 
+// (A1 A2) / (B1 B2) of one pixel, every product rounded before the sums as numpy rounds them (structural_similarity's
+// own statements): contracted to fmas, 2 ux uy + C1 rounds once and ux ux + uy uy + C1 twice, so identical images score
+// 1 - 2^-53 on some pixels instead of exactly 1 (csrc/loss.hip, ssim_terms, has the fp32 case, where a root amplifies it)
+__device__ __forceinline__ double vm_ssim_pixel(double ux, double uy, double uxx, double uyy, double uxy, double C1,
+                                                double C2, double cov) {
+#pragma clang fp contract(off)
+  const double pxx = ux * ux, pyy = uy * uy, pxy = ux * uy;
+  const double vx = cov * (uxx - pxx), vy = cov * (uyy - pyy), vxy = cov * (uxy - pxy);
+  const double A1 = 2.0 * pxy + C1, A2 = 2.0 * vxy + C2;
+  const double B1 = (pxx + pyy) + C1, B2 = (vx + vy) + C2;
+  return (A1 * A2) / (B1 * B2);
+}
+
 // the tile body shared by the unmasked and the masked kernel: stages the (32+6) x (64+6) patch at (y0, x0) of one plane
 // (MASKED: an element whose bit `label` of `bits` is clear is staged as 0, so t*m and p*m exist in LDS only) and returns
 // the workgroup's sum of the SSIM map over the tile's interior pixels (in every thread)
@@ -209,10 +222,7 @@ __device__ __forceinline__ double vm_ssim_tile(const float* tp, const float* pp,
       }
       if (r >= 6 && y0 + r0 + r - 6 < Ho) {
         const double ux = v[0] * inv, uy = v[1] * inv, uxx = v[2] * inv, uyy = v[3] * inv, uxy = v[4] * inv;
-        const double vx = cov * (uxx - ux * ux), vy = cov * (uyy - uy * uy), vxy = cov * (uxy - ux * uy);
-        const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
-        const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
-        acc += (A1 * A2) / (B1 * B2);
+        acc += vm_ssim_pixel(ux, uy, uxx, uyy, uxy, C1, C2, cov);
       }
     }
   }
