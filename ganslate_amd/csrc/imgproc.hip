@@ -145,3 +145,116 @@ extern "C" int gs_u8_resample_v_crop_normalize(const void* tmp, float* out, int3
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// ---- the batched form: every image of a batch in one launch per pass (val / test / infer folders) -------------------------
+// One GsU8BatchItem per image in a device array; blockIdx.z is the image, so every descriptor read is wave-uniform. The
+// bodies are resample_h_kernel / resample_v_crop_norm_kernel operation for operation; what changes is where the sizes,
+// tables and pointers come from, and that the horizontal pass starts at row0 and stops after `rows` rows.
+namespace {
+template <int C>
+__global__ __launch_bounds__(256) void batch_resample_h_kernel(const GsU8BatchItem* __restrict__ items,
+                                                               unsigned char* __restrict__ tmp) {
+  const GsU8BatchItem& it = items[blockIdx.z];
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;                    // row of the tmp slice; input row row0 + r
+  const int out_w = it.rw;
+  if (r >= it.rows || xx >= out_w) return;
+  const int* bounds = it.bounds_h;
+  const int ksize = it.ksize_h;
+  const int xmin = bounds[xx * 2], xn = bounds[xx * 2 + 1];
+  const int* k = it.kk_h + (size_t)xx * ksize;
+  int acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 1 << (PRECISION_BITS - 1);
+  const unsigned char* row = static_cast<const unsigned char*>(it.src) + ((size_t)(it.row0 + r) * it.in_w + xmin) * C;
+  for (int x = 0; x < xn; ++x) {
+    const int w = k[x];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += (int)row[x * C + c] * w;
+  }
+  unsigned char* o = tmp + it.tmp_off + ((size_t)r * out_w + xx) * C;
+#pragma unroll
+  for (int c = 0; c < C; ++c) o[c] = (unsigned char)clip8(acc[c]);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void batch_resample_v_crop_norm_kernel(const GsU8BatchItem* __restrict__ items,
+                                                                         const unsigned char* __restrict__ tmp,
+                                                                         float* __restrict__ out, int fh, int fw) {
+  const GsU8BatchItem& it = items[blockIdx.z];
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = blockIdx.y;
+  if (j >= fw) return;
+  const int yy = it.top + i;
+  const int xs = it.left + (it.flip ? fw - 1 - j : j);
+  const int tmp_w = it.rw;
+  const int* bounds = it.bounds_v;
+  const int ksize = it.ksize_v;
+  const int ymin = bounds[yy * 2] - it.row0, yn = bounds[yy * 2 + 1];      // tmp row 0 is input row row0
+  const int* k = it.kk_v + (size_t)yy * ksize;
+  const unsigned char* t = tmp + it.tmp_off;
+  int acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 1 << (PRECISION_BITS - 1);
+  for (int y = 0; y < yn; ++y) {
+    const unsigned char* p = t + ((size_t)(ymin + y) * tmp_w + xs) * C;
+    const int w = k[y];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += (int)p[c] * w;
+  }
+  float* o = out + (size_t)blockIdx.z * C * fh * fw;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float v = (float)clip8(acc[c]) / 255.0f;
+    o[((size_t)c * fh + i) * fw + j] = (v - 0.5f) / 0.5f;
+  }
+}
+}  // namespace
+
+extern "C" int gs_u8_batch_check(const GsU8BatchItem* items, int32_t n, int32_t C, int32_t fh, int32_t fw,
+                                 int64_t tmp_bytes) {
+  GS_REQUIRE(items && n >= 1 && n <= 65535 && (C == 1 || C == 3) && fh > 0 && fh <= 65535 && fw > 0 && tmp_bytes > 0,
+             "gs_u8_batch_check: bad argument (1 <= n <= 65535, C must be 1 or 3)");
+  for (int32_t i = 0; i < n; ++i) {
+    const GsU8BatchItem& it = items[i];
+    GS_REQUIRE(it.src && it.bounds_h && it.kk_h && it.bounds_v && it.kk_v && it.in_h > 0 && it.in_w > 0 && it.rh > 0 &&
+                   it.rw > 0 && it.ksize_h > 0 && it.ksize_v > 0,
+               "gs_u8_batch_check: image %d: bad descriptor (null pointer or non-positive size)", i);
+    GS_REQUIRE(it.top >= 0 && it.left >= 0 && it.top + fh <= it.rh && it.left + fw <= it.rw,
+               "gs_u8_batch_check: image %d: crop window [%d+%d, %d+%d] outside the %d x %d resized image", i, it.top, fh,
+               it.left, fw, it.rh, it.rw);
+    GS_REQUIRE(it.row0 >= 0 && it.rows > 0 && it.rows <= 65535 && it.row0 + it.rows <= it.in_h,
+               "gs_u8_batch_check: image %d: rows [%d, %d+%d) outside the %d input rows", i, it.row0, it.row0, it.rows,
+               it.in_h);
+    GS_REQUIRE(it.tmp_off >= 0 && it.tmp_off + (int64_t)it.rows * it.rw * C <= tmp_bytes,
+               "gs_u8_batch_check: image %d: tmp slice [%lld, +%lld) outside the arena of %lld bytes", i,
+               (long long)it.tmp_off, (long long)it.rows * it.rw * C, (long long)tmp_bytes);
+  }
+  return 0;
+}
+
+extern "C" int gs_u8_batch_resample_h(const GsU8BatchItem* items, int32_t n, int32_t C, void* tmp, int32_t grid_w,
+                                      int32_t grid_rows, void* stream) {
+  GS_REQUIRE(items && tmp && n >= 1 && n <= 65535 && grid_w > 0 && grid_rows > 0 && grid_rows <= 65535 && (C == 1 || C == 3),
+             "gs_u8_batch_resample_h: bad argument (1 <= n <= 65535, C must be 1 or 3)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((grid_w + 255) / 256, grid_rows, n);
+  unsigned char* t8 = static_cast<unsigned char*>(tmp);
+  if (C == 3) hipLaunchKernelGGL(batch_resample_h_kernel<3>, grid, dim3(256), 0, st, items, t8);
+  else hipLaunchKernelGGL(batch_resample_h_kernel<1>, grid, dim3(256), 0, st, items, t8);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gs_u8_batch_resample_v_crop_normalize(const GsU8BatchItem* items, int32_t n, int32_t C, const void* tmp,
+                                                     int32_t fh, int32_t fw, float* out, void* stream) {
+  GS_REQUIRE(items && tmp && out && n >= 1 && n <= 65535 && fh > 0 && fh <= 65535 && fw > 0 && (C == 1 || C == 3),
+             "gs_u8_batch_resample_v_crop_normalize: bad argument (1 <= n <= 65535, C must be 1 or 3)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((fw + 255) / 256, fh, n);
+  const unsigned char* t8 = static_cast<const unsigned char*>(tmp);
+  if (C == 3) hipLaunchKernelGGL(batch_resample_v_crop_norm_kernel<3>, grid, dim3(256), 0, st, items, t8, out, fh, fw);
+  else hipLaunchKernelGGL(batch_resample_v_crop_norm_kernel<1>, grid, dim3(256), 0, st, items, t8, out, fh, fw);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}

@@ -7,6 +7,13 @@ this backend that is the bottleneck. With `train.dataset.device_transforms: true
 8-bit HWC) and draw the random parameters; the pixels are uploaded as bytes and `DeviceImagePipeline` runs the whole
 transform in two kernels per image (csrc/imgproc.hip), writing the fp32 NCHW batch the recipes' `set_input` expects.
 
+The same switch works under `val`, `test` and `infer` (engines/base.py `input_pipeline`). There a folder goes through one
+generator forward per batch at batch sizes of 16-64, where the per-image launches, allocations and uploads dominate, so
+outside training the pipeline takes the batched form: all images of a key packed into one pinned staging buffer and
+uploaded with one copy, one descriptor table (`BatchItem` -> GsU8BatchItem), and the two batched kernels once per key
+(HipOps.u8_batch_resample). The horizontal pass then computes only the rows under the crop window. The Trainer and the
+oracle backend keep the per-image loop.
+
 The resize reproduces Pillow's resampler bit for bit: `resample_tables` restates `precompute_coeffs` and
 `normalize_coeffs_8bpc` of Pillow's src/libImaging/Resample.c (bicubic filter a = -0.5, support 2 x max(scale, 1),
 22-bit fixed point) in double precision, operation for operation; tests pin the tables' effect against PIL.Image.resize.
@@ -14,6 +21,7 @@ The resize reproduces Pillow's resampler bit for bit: `resample_tables` restates
 import math
 import random
 from functools import lru_cache
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -76,6 +84,31 @@ class RawImage:
         self.pixels, self.crop, self.flip, self.zoom = pixels, crop, flip, zoom
 
 
+class BatchItem(NamedTuple):
+    """host side of one GsU8BatchItem (include/ganslate_hip.h): the last resize of one image, restricted to what the crop
+    window needs. tables_h / tables_v: the (bounds, kk) tensor pairs of the two axes."""
+    in_h: int
+    in_w: int
+    rh: int
+    rw: int
+    row0: int
+    rows: int
+    top: int
+    left: int
+    flip: bool
+    tables_h: Any = None
+    tables_v: Any = None
+
+
+def batch_item(in_h, in_w, rh, rw, top, left, fh, flip, tables_h=None, tables_v=None):
+    """the rows [row0, row0 + rows) of the in_h x in_w image that the vertical pass of the crop rows [top, top + fh) reads:
+    from bounds_v[top].first to the end of the last row's support"""
+    bounds_v = resample_tables(in_h, rh)[0][top:top + fh].astype(np.int64)
+    row0 = int(bounds_v[:, 0].min())
+    rows = int((bounds_v[:, 0] + bounds_v[:, 1]).max()) - row0
+    return BatchItem(in_h, in_w, rh, rw, row0, rows, top, left, bool(flip), tables_h, tables_v)
+
+
 def draw_params():
     return (random.random(), random.random()), random.random() > 0.5
 
@@ -88,15 +121,20 @@ def collate_raw(samples):
 class DeviceImagePipeline:
     """callable(raw batch) -> {"A": fp32 [N, C, fh, fw] on the device, "B": ...}"""
 
-    def __init__(self, conf, device, ops=None):
-        d = conf[conf.mode].dataset
-        self.pre, self.load, self.final = list(d.preprocess), tuple(d.load_size), tuple(d.final_size)
+    def __init__(self, conf, device, ops=None, transform=None, batched=None):
+        # `transform`: the dataset's own _Transform (build_loader deep-copies the conf per multi_dataset entry, so the
+        # engine's conf has `dataset: None` there); `batched`: None -> everywhere but in training
+        d = transform if transform is not None else conf[conf.mode].dataset
+        pre = d.pre if transform is not None else d.preprocess
+        load, final = (d.load, d.final) if transform is not None else (d.load_size, d.final_size)
+        self.pre, self.load, self.final = list(pre), tuple(load), tuple(final)
         unknown = set(self.pre) - {"resize", "scale_width", "random_zoom", "random_crop", "random_flip"}
         if unknown:
             raise NotImplementedError(f"device_transforms: preprocess steps {sorted(unknown)} have no device path")
         self.device = torch.device(device)
         self._ops = ops
         self._tables = {}
+        self.batched = conf.mode != "train" if batched is None else bool(batched)
 
     @property
     def ops(self):
@@ -132,24 +170,35 @@ class DeviceImagePipeline:
             fh, fw, top, left = rh, rw, 0, 0
         return rh, rw, top, left, min(fh, rh), min(fw, rw)
 
-    def one(self, raw: RawImage, out):
-        px = raw.pixels
+    def _upload(self, px):
         if px.ndim == 2:
             px = px.unsqueeze(-1)
         px = px.contiguous()
         if not px.is_cuda:
             px = px.pin_memory().to(self.device, non_blocking=True) if self.device.type == "cuda" else px
+        return px
+
+    def _early_resizes(self, px, steps):
+        """the complete resizes in front of the last one, each with an 8-bit result (Pillow rounds to bytes between two
+        Image.resize calls)"""
         H, W, C = px.shape
-        rh, rw, top, left, fh, fw = self.geometry(H, W, raw.crop, raw.zoom)
-        steps = self.sizes(H, W, raw.zoom) or [(H, W)]
-        for h1, w1 in steps[:-1]:          # a complete resize with an 8-bit result in front of the last one (Pillow rounds
-            bh, kh = self._dev_tables(W, w1)          # to bytes between two Image.resize calls)
+        for h1, w1 in steps[:-1]:
+            bh, kh = self._dev_tables(W, w1)
             bv, kv = self._dev_tables(H, h1)
             tmp = torch.empty((H, w1, C), dtype=torch.uint8, device=px.device)
             self.ops.u8_resample_h(px, tmp, bh, kh)
             px = torch.empty((h1, w1, C), dtype=torch.uint8, device=px.device)
             self.ops.u8_resample_v(tmp, px, bv, kv)
             H, W = h1, w1
+        return px
+
+    def one(self, raw: RawImage, out):
+        px = self._upload(raw.pixels)
+        H, W, C = px.shape
+        rh, rw, top, left, fh, fw = self.geometry(H, W, raw.crop, raw.zoom)
+        steps = self.sizes(H, W, raw.zoom) or [(H, W)]
+        px = self._early_resizes(px, steps)
+        H, W = px.shape[:2]
         bh, kh = self._dev_tables(W, rw)
         bv, kv = self._dev_tables(H, rh)
         tmp = torch.empty((H, rw, C), dtype=torch.uint8, device=px.device)
@@ -157,10 +206,48 @@ class DeviceImagePipeline:
         flip = "random_flip" in self.pre and raw.flip
         self.ops.u8_resample_v_crop_normalize(tmp, out, rh, bv, kv, top, left, flip)
 
+    def describe(self, raw: RawImage, with_tables=True):
+        """the BatchItem of one image's LAST resize and the (h, w) of the image that resize reads (the decoded image, or the
+        8-bit result of the earlier resizes of its chain)"""
+        H, W = raw.pixels.shape[:2]
+        rh, rw, top, left, fh, fw = self.geometry(H, W, raw.crop, raw.zoom)
+        steps = self.sizes(H, W, raw.zoom) or [(H, W)]
+        in_h, in_w = steps[-2] if len(steps) > 1 else (H, W)
+        flip = "random_flip" in self.pre and raw.flip
+        th, tv = (self._dev_tables(in_w, rw), self._dev_tables(in_h, rh)) if with_tables else (None, None)
+        return batch_item(in_h, in_w, rh, rw, top, left, fh, flip, th, tv)
+
+    def _stage(self, items):
+        """decoded images of one key -> (H, W, C) uint8 device tensors: everything still on the host is packed into one
+        pinned staging buffer and uploaded with one copy"""
+        pxs = [r.pixels.unsqueeze(-1) if r.pixels.ndim == 2 else r.pixels for r in items]
+        host = [k for k, p in enumerate(pxs) if not p.is_cuda]
+        if host:
+            sizes = [pxs[k].numel() for k in host]
+            staging = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+            for k, part in zip(host, staging.split(sizes)):
+                part.view(pxs[k].shape).copy_(pxs[k])
+            dev = staging.to(self.device, non_blocking=True)
+            for k, part in zip(host, dev.split(sizes)):
+                pxs[k] = part.view(pxs[k].shape)
+        return [p.contiguous() for p in pxs]
+
+    def batch(self, items, dst):
+        """all images of one key through the two batched kernels; an image whose chain has a complete earlier resize runs
+        that through the per-image kernels and joins the batch for its last one"""
+        srcs, descs = [], []
+        for raw, px in zip(items, self._stage(items)):
+            H, W, C = px.shape
+            steps = self.sizes(H, W, raw.zoom) or [(H, W)]
+            srcs.append(self._early_resizes(px, steps))
+            descs.append(self.describe(raw))
+        # srcs, the cached tables the descriptors point at and the arena stay referenced until both launches are enqueued
+        self.ops.u8_batch_resample(descs, srcs, dst, dst.shape[1])
+
     def __call__(self, batch):
         out = {}
         for key, items in batch.items():
-            if not items or not isinstance(items[0], RawImage):
+            if not isinstance(items, (list, tuple)) or not items or not isinstance(items[0], RawImage):
                 out[key] = items
                 continue
             r0 = items[0]
@@ -169,7 +256,10 @@ class DeviceImagePipeline:
             assert len(shapes) == 1, f"images of one batch end at different sizes {shapes}: add random_crop or resize"
             fh, fw = next(iter(shapes))
             dst = torch.empty((len(items), C, fh, fw), dtype=torch.float32, device=self.device)
-            for n, r in enumerate(items):
-                self.one(r, dst[n])
+            if self.batched and hasattr(self.ops, "u8_batch_resample"):
+                self.batch(items, dst)
+            else:
+                for n, r in enumerate(items):
+                    self.one(r, dst[n])
             out[key] = dst
         return out

@@ -21,7 +21,8 @@ class UnpairedImageDatasetConfig(configs.base.BaseDatasetConfig):
     preprocess: Tuple[str] = ("resize", "random_crop", "random_flip")
     load_size: Tuple[int, int] = field(default_factory=lambda: [286, 286])
     final_size: Tuple[int, int] = field(default_factory=lambda: [256, 256])
-    # not in the reference: workers only decode, resize / crop / flip / normalise run on the GPU (data/device_transforms.py)
+    # not in the reference: workers only decode, resize / crop / flip / normalise run on the GPU (data/device_transforms.py);
+    # under `train`, and under `val`, `test` and `infer`, where whole batches go through two kernels
     device_transforms: bool = False
 
 
@@ -101,7 +102,8 @@ class _Transform:
 
 
 class _DevicePipelineMixin:
-    """build_loader picks these up: raw batches are lists (images differ in size), the Trainer runs the pipeline"""
+    """build_loader picks these up: raw batches are lists (images differ in size), the engine (Trainer, Validator, Tester,
+    Inferer) runs the pipeline"""
 
     @property
     def collate_fn(self):
@@ -114,7 +116,8 @@ class _DevicePipelineMixin:
         if not self.transform.raw:
             return None
         from .device_transforms import DeviceImagePipeline
-        return DeviceImagePipeline(conf, device)
+        # geometry from this dataset's own transform: with `multi_dataset` the engine's conf has no `dataset` node
+        return DeviceImagePipeline(conf, device, transform=self.transform)
 
 
 class UnpairedImageDataset(_DevicePipelineMixin, Dataset):

@@ -1,7 +1,10 @@
 """Engine bases (ganslate/engines/base.py:11-50): `BaseEngineWithInference.infer` sends a batch through the model's
 generator — patch-wise through the MONAI-free sliding-window inferer when `<mode>.sliding_window` is configured
 (window_size / batch_size / overlap / mode, padding value -1 like the reference, base.py:41-50).
-`save_generated_tensor` hands every generated sample to the dataset's own `save()` where it has one (base.py:52-87)."""
+`save_generated_tensor` hands every generated sample to the dataset's own `save()` where it has one (base.py:52-87).
+`input_pipeline` is this backend's device-side input path (`<mode>.dataset.device_transforms`, data/device_transforms.py) for
+the engines that only run a forward pass: one pipeline per loader, applied to every batch in front of everything that
+reads it."""
 import copy
 import logging
 from abc import ABC, abstractmethod
@@ -30,12 +33,35 @@ class BaseEngineWithInference(BaseEngine):
     def __init__(self, conf):
         super().__init__(conf)
         self.sliding_window_inferer = self._init_sliding_window_inferer()
+        self._input_pipelines = {}
 
     def infer(self, data, *args, **kwargs):
         data = data.to(self.model.device)
         if self.sliding_window_inferer:
             return self.sliding_window_inferer(data, self.model.infer, *args, **kwargs)
         return self.model.infer(data, *args, **kwargs)
+
+    def input_pipeline(self, loader):
+        """callable(raw batch) -> batch of device tensors for a loader whose dataset hands over undecoded work
+        (`device_transforms: true`), built once per loader from the dataset's own `device_pipeline`; None for a dataset on
+        the host path. Entries that are not raw images (`masks`, `metadata`) pass through the pipeline untouched."""
+        if loader not in self._input_pipelines:
+            self._input_pipelines[loader] = self._make_input_pipeline(loader.dataset)
+        return self._input_pipelines[loader]
+
+    def _make_input_pipeline(self, dataset):
+        from ..data.volume_datasets import UnpairedVolumeDataset
+        # where each dataset keeps the switch: the image folders in their transform, the volume folder on itself
+        places = ((getattr(dataset, "transform", None), "raw"), (dataset, "raw"), (getattr(dataset, "conf", None), "device_transforms"),
+                  (dataset, "device_transforms"))
+        flag = any(getattr(owner, name, False) is True for owner, name in places)
+        make = getattr(dataset, "device_pipeline", None)
+        if flag and (make is None or isinstance(dataset, UnpairedVolumeDataset)):
+            # UnpairedVolumeDataset's device path holds training patches, not whole volumes
+            raise NotImplementedError(f"{self.conf.mode} datasets run the host transform path: set "
+                                      f"`{self.conf.mode}.dataset.device_transforms: false` (the device-side "
+                                      "pipeline batches training samples only)")
+        return make(self.conf, self.model.device) if make else None
 
     def _init_sliding_window_inferer(self):
         sw = self.conf[self.conf.mode].sliding_window

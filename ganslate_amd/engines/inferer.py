@@ -39,8 +39,11 @@ class Inferer(BaseEngineWithInference):
         batch_size = self.conf.infer.batch_size
         n_samples = len(self.data_loader.dataset)
         input_key = None
+        pipeline = self.input_pipeline(self.data_loader)      # `infer.dataset.device_transforms` (data/device_transforms.py)
         t_start = time.perf_counter()
         for i, data in enumerate(self.data_loader):
+            if pipeline is not None:
+                data = pipeline(data)
             # every process does an iteration of batch_size samples; numbering starts at 1 (inferer.py:39-43)
             iter_idx = i * communication.get_world_size() * batch_size + 1
             if i == 0:

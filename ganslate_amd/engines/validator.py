@@ -18,6 +18,10 @@ not denormalised; all labels of a batch go through one masked call. The host pat
 `<test.output_dir>/test/metrics.csv` when `test.metrics.save_to_csv` is set: one row per sample, one column per metric,
 plus a `dataset` column with `multi_dataset`.
 
+With `<mode>.dataset.device_transforms: true` the image-folder datasets hand over decoded bytes and every batch goes through
+the device-side input pipeline first (BaseEngineWithInference.input_pipeline); what follows sees the same tensors, already
+on the device.
+
 Every batch's `fake_B` goes to the dataset's `save()` where it has one (BaseEngineWithInference.save_generated_tensor,
 `saved/[{dataset}/][{iter}/]`), and every sample is logged as one PNG of `real_A, fake_B, real_B` and then each mask label as
 `2 * mask - 1` side by side, a volume as its middle slice: `images/[{dataset}/]{iter}/{idx}_{name}.png` in validation,
@@ -105,11 +109,7 @@ class BaseValTestEngine(BaseEngineWithInference):
         try:
             for name, loader in self.data_loaders.items():
                 dataset = loader.dataset
-                if getattr(getattr(dataset, "conf", None), "device_transforms", False) or \
-                        getattr(dataset, "device_transforms", False):
-                    raise NotImplementedError(f"{self.conf.mode} datasets run the host transform path: set "
-                                              f"`{self.conf.mode}.dataset.device_transforms: false` (the device-side "
-                                              "pipeline batches training samples only)")
+                self.input_pipeline(loader)        # raises for a dataset whose device path cannot feed this engine
                 # Denormalize the data if the dataset defines `denormalize` (validator_tester.py:72-77)
                 denormalize = getattr(dataset, "denormalize", None)
                 over_input = bool(getattr(self.conf[self.conf.mode].metrics, "compute_over_input", False))
@@ -139,9 +139,14 @@ class BaseValTestEngine(BaseEngineWithInference):
             visuals[label] = mask.to(self.model.device).float() * 2 - 1
         self.writer.add_samples(self.writer.compose(visuals, mid_slice_only=True))
 
+    def _batches(self, loader):
+        """the loader's batches, through the device-side input pipeline where the dataset has one"""
+        pipeline = self.input_pipeline(loader)
+        return loader if pipeline is None else map(pipeline, loader)
+
     def _host_rows(self, loader, denormalize, over_input, dataset_name=None, current_idx=None):
         rows = []
-        for data in loader:
+        for data in self._batches(loader):
             self._log_masks(data)
             real_A = data["A"].to(self.model.device)
             with torch.no_grad():
@@ -168,7 +173,7 @@ class BaseValTestEngine(BaseEngineWithInference):
         m = self.metricizer
         tables, originals, cycles = [], [], []
         labels, masked, masked_originals = None, [], []
-        for data in loader:
+        for data in self._batches(loader):
             real_A = data["A"].to(self.model.device)
             with torch.no_grad():
                 fake_B = self.infer(real_A)

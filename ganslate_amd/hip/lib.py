@@ -87,6 +87,13 @@ class PNormDesc(C.Structure):
         "g2_cs", "g2_co", "dy_cs", "dy_co", "gres_cs", "gres_co")]
 
 
+class U8BatchItem(C.Structure):
+    """Mirror of GsU8BatchItem."""
+    _fields_ = [(n, C.c_void_p) for n in ("src", "bounds_h", "kk_h", "bounds_v", "kk_v")] + [("tmp_off", C.c_int64)] + [
+        (n, C.c_int32) for n in ("in_h", "in_w", "rh", "rw", "row0", "rows", "top", "left", "flip", "ksize_h", "ksize_v",
+                                 "pad_")]
+
+
 _PROTOS = {
     "gs_init": (C.c_int, [C.c_int]),
     "gs_shutdown": (None, []),
@@ -186,6 +193,10 @@ _PROTOS = {
     "gs_u8_resample_v_crop_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, C.c_int32, C.c_void_p]),
+    "gs_u8_batch_check": (C.c_int, [C.POINTER(U8BatchItem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "gs_u8_batch_resample_h": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gs_u8_batch_resample_v_crop_normalize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                        C.c_void_p, C.c_void_p]),
     "gs_patch_zscore_ws_floats": (C.c_int64, []),
     "gs_patch_zscore": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,

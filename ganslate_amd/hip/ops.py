@@ -807,6 +807,56 @@ class HipOps(TwinSplit):
                                                          int(bool(flip)), _stream()),
                 "gs_u8_resample_v_crop_normalize")
 
+    U8_TMP_ALIGN = 256
+
+    @staticmethod
+    def u8_batch_table(items_host, srcs, Cc, guard=0):
+        """(ctypes array of GsU8BatchItem, bytes of the tmp arena) for a batch: `items_host` carry the geometry of each
+        image (in_h, in_w, rh, rw, row0, rows, top, left, flip) and the (bounds, kk) tensor pairs of both axes, `srcs` the
+        (in_h, in_w, C) uint8 tensors. The slices of the arena follow each other, each rounded up to U8_TMP_ALIGN bytes, with
+        `guard` bytes in front of, between and behind them. Pure host code."""
+        table = (L.U8BatchItem * len(items_host))()
+        off = int(guard)
+        for d, it, src in zip(table, items_host, srcs):
+            (bh, kh), (bv, kv) = it.tables_h, it.tables_v
+            assert src.dtype == torch.uint8 and src.is_contiguous() and src.numel() == it.in_h * it.in_w * Cc, src.shape
+            assert bh.shape == (it.rw, 2) and bv.shape == (it.rh, 2) and kh.shape[0] == it.rw and kv.shape[0] == it.rh
+            assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (bh, kh, bv, kv))
+            d.src, d.bounds_h, d.kk_h, d.bounds_v, d.kk_v = (t.data_ptr() for t in (src, bh, kh, bv, kv))
+            d.in_h, d.in_w, d.rh, d.rw, d.row0, d.rows = it.in_h, it.in_w, it.rh, it.rw, it.row0, it.rows
+            d.top, d.left, d.flip = int(it.top), int(it.left), int(bool(it.flip))
+            d.ksize_h, d.ksize_v, d.tmp_off = kh.shape[1], kv.shape[1], off
+            size = max(it.rows, 0) * it.rw * Cc
+            off += -(-size // HipOps.U8_TMP_ALIGN) * HipOps.U8_TMP_ALIGN + int(guard)
+        return table, off
+
+    def u8_batch_check(self, table, Cc, fh, fw, tmp_bytes):
+        """the library's validation of a HOST descriptor table; raises its error (the kernels cannot report one)"""
+        L.check(self.lib.gs_u8_batch_check(table, len(table), Cc, fh, fw, tmp_bytes), "gs_u8_batch_check")
+
+    def u8_batch_resample(self, items_host, srcs, out, Cc, tmp=None, guard=0):
+        """Both Pillow passes + crop + flip + ToTensor + Normalize(0.5, 0.5) for a whole batch of decoded images of different
+        sizes in two launches: srcs[i] (in_h, in_w, C) uint8 on the device -> out[i] of the fp32 (n, C, fh, fw) batch. One
+        descriptor table, validated on the host and uploaded with one copy; one tmp arena that holds, per image, only the
+        rows its vertical pass reads. Returns (host table, tmp arena); `tmp` / `guard` let a test own the arena."""
+        n = len(items_host)
+        assert n == len(srcs) == out.shape[0] and out.dim() == 4 and out.shape[1] == Cc, (n, len(srcs), out.shape, Cc)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.is_cuda and all(s.is_cuda for s in srcs)
+        fh, fw = out.shape[2], out.shape[3]
+        table, nbytes = self.u8_batch_table(items_host, srcs, Cc, guard)
+        self.u8_batch_check(table, Cc, fh, fw, nbytes)
+        if tmp is None:
+            tmp = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+        assert tmp.dtype == torch.uint8 and tmp.is_contiguous() and tmp.numel() >= nbytes and tmp.device == out.device
+        staged = torch.empty(C.sizeof(table), dtype=torch.uint8, pin_memory=True)
+        staged.copy_(torch.frombuffer(table, dtype=torch.uint8))
+        dev = staged.to(out.device, non_blocking=True)
+        L.check(self.lib.gs_u8_batch_resample_h(_ptr(dev), n, Cc, _ptr(tmp), max(it.rw for it in items_host),
+                                                max(it.rows for it in items_host), _stream()), "gs_u8_batch_resample_h")
+        L.check(self.lib.gs_u8_batch_resample_v_crop_normalize(_ptr(dev), n, Cc, _ptr(tmp), fh, fw, _ptr(out), _stream()),
+                "gs_u8_batch_resample_v_crop_normalize")
+        return table, tmp
+
     VOL_DTYPES = {torch.float32: 0, torch.int16: 1}
 
     def patch_zscore(self, volume, start, size, out, scale_to_range=(-1.0, 1.0)):

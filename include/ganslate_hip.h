@@ -437,6 +437,37 @@ int gs_u8_resample_v_crop_normalize(const void* tmp, float* out, int32_t tmp_h, 
                                     const int32_t* bounds, const int32_t* kk, int32_t ksize, int32_t top, int32_t left,
                                     int32_t fh, int32_t fw, int32_t flip, void* stream);
 
+/* The same two passes for a whole batch of decoded images of different sizes, one launch per pass (the val / test / infer
+ * engines push folders through at batch sizes where launches, allocations and copies per image dominate). One descriptor
+ * per image, in a device array; the pointers are device pointers. The horizontal pass computes only the input rows
+ * [row0, row0 + rows) that the vertical pass of the crop rows [top, top + fh) reads (bounds_v[top].first up to
+ * bounds_v[top+fh-1].first + count) into tmp + tmp_off, rows x rw x C bytes; the vertical pass indexes that slice
+ * relative to row0 and writes image i of the fp32 [n][C][fh][fw] batch. Arithmetic, rounding and operation order are those
+ * of the per-image entry points above. */
+typedef struct GsU8BatchItem {
+  const void* src;              /* in_h x in_w x C bytes, HWC */
+  const int32_t* bounds_h;      /* [rw][2], kk_h [rw][ksize_h]: in_w -> rw */
+  const int32_t* kk_h;
+  const int32_t* bounds_v;      /* [rh][2], kk_v [rh][ksize_v]: in_h -> rh */
+  const int32_t* kk_v;
+  int64_t tmp_off;              /* byte offset of this image's slice of the tmp arena */
+  int32_t in_h, in_w, rh, rw;   /* decoded size, resized size */
+  int32_t row0, rows;           /* input rows the horizontal pass computes */
+  int32_t top, left, flip;      /* crop window origin in the resized image; horizontal flip of the window */
+  int32_t ksize_h, ksize_v, pad_;
+} GsU8BatchItem;
+/* Host-side validation of a descriptor table BEFORE it is uploaded (the kernels cannot report a bad descriptor): `items` is
+ * a HOST array here. Every pointer non-null, sizes positive, the fh x fw crop window inside the rh x rw resized image,
+ * [row0, row0 + rows) inside [0, in_h), every tmp slice inside [0, tmp_bytes). */
+int gs_u8_batch_check(const GsU8BatchItem* items, int32_t n, int32_t C, int32_t fh, int32_t fw, int64_t tmp_bytes);
+/* items: DEVICE array of n descriptors; grid_w >= every rw, grid_rows >= every rows (blocks outside their image's extent
+ * return); grid (ceil(grid_w / 256), grid_rows, n). */
+int gs_u8_batch_resample_h(const GsU8BatchItem* items, int32_t n, int32_t C, void* tmp, int32_t grid_w, int32_t grid_rows,
+                           void* stream);
+/* grid (ceil(fw / 256), fh, n): out[i][c][y][x] fp32. */
+int gs_u8_batch_resample_v_crop_normalize(const GsU8BatchItem* items, int32_t n, int32_t C, const void* tmp, int32_t fh,
+                                          int32_t fw, float* out, void* stream);
+
 /* ---- device-side 3-D training patches ------------------------------------------- */
 /* What the 3-D datasets' workers do per sample on the host (projects/brats_mri_sequence_translation/datasets/
  * train_dataset.py:83-86 -> ganslate/data/utils/normalization.py:18-30): out = z_score_normalize(volume[z:z+d, y:y+h,
