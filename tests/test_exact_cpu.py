@@ -17,7 +17,7 @@ import torch
 from ganslate_amd.nn.native.spec import ConvSpec
 from oracle.ops_ref import RefOps
 from tests import exact
-from tests.test_ops_gpu import CONV_CASES, _ids, close_bf16, make_layer
+from tests.test_ops_gpu import CONV_CASES, _ids, close_bf16, make_layer, stats_slots
 
 pytestmark = []          # (test_ops_gpu's module-level gpu mark does not travel with its names)
 
@@ -28,6 +28,28 @@ ROUNDING_CASES = [
     (ConvSpec("convT", 256, 128, 3, 2, 1, 1), 2, 16, 16),                                  # transposed
     (ConvSpec("conv", 256, 256, 3, 1, 1, pad_mode="replicate", dims=3), 1, 8, 8, 8),      # 3-D
 ]
+
+# The persistent kernels of the volume path with MORE THAN ONE unit per workgroup on the 256 CUs of the target, in the slice /
+# accumulate form of slice_case (k5 s1 p2 volumes, seed 61): (kernel, cin, cout, N, sizes, launches that run on that kernel,
+# units the deepest workgroup walks, whether the shares are uneven). test_exact_gpu.py restates each kernel's launch rule and
+# asserts the last two; the smallest shapes that take the branches named.
+WALK_CASES = [
+    # hconv2_kernel (csrc/hconv.hip), 8 x 8 x 8 boxes
+    ("hconv2", 32, 32, 1, (40, 56, 72), ("fwd", "dgrad"), 2, True),     # 315 boxes on 158 workgroups, two chunks per box
+    ("hconv2", 64, 64, 1, (17, 40, 72), ("fwd", "dgrad"), 2, True),     # 135 on 68 x 2 channel groups, ragged depth, four chunks
+    ("hconv2", 16, 32, 1, (49, 64, 80), ("fwd",), 3, True),             # 560 on 187, one chunk: the halo parity flips per box
+    ("hconv2", 32, 16, 1, (49, 64, 80), ("dgrad",), 3, True),           # ... and that walk under the accumulate epilogue
+    # hconv5_kernel (csrc/hconv5.hip): 98 columns x 3 segments of 3, 3 and 1 steps on 147 workgroups
+    ("hconv5", 16, 16, 2, (28, 112, 112), ("fwd", "dgrad"), 2, False),
+]
+WALK_SEED = 61
+# hstripr_kernel<32,64,32> forward WITH statistics (csrc/hstrip.hip): 3 x 7 x 32 = 672 tiles (ragged rows: 200 = 6 * 32 + 8) on
+# 512 workgroups; its data gradient (<64,32,16>) has 3 x 13 x 32 = 1248
+WALK_STRIP_CASE = (ConvSpec("conv", 3, 64, 7, 1, 3, pad_mode="reflect", wfold="in"), 3, 200, 256)
+
+
+def walk_id(case):
+    return "%s-%dto%d-%dx%s" % (case[0], case[1], case[2], case[3], "x".join(map(str, case[4])))
 
 
 def oracle_forward(c, act="none", slope=0.2):
@@ -55,6 +77,49 @@ def oracle_wgrad(c, prefill_w=0.0, prefill_b=0.0):
     db = torch.full((spec.cout_p,), prefill_b, dtype=torch.float32)
     RefOps().bias_grad(c.gy, spec.cout_p, db)
     return dw, db
+
+
+def slice_case(spec, N, sizes, seed):
+    """a narrow volume layer that reads the upper half of a 2 * cin channel buffer and whose data gradient is accumulated into
+    the upper half of an integer-filled one (the V-Net couplings)"""
+    c = exact.make_case(spec, N, sizes, seed=seed, check=("fwd", "dgrad"))
+    g = torch.Generator().manual_seed(seed + 7)
+    d = c.dom
+    x2 = exact.int_act(N, sizes, 2 * spec.cin, 2 * spec.cin, g, d["dx"], d["mag"])
+    x2[..., spec.cin:] = c.xa
+    base = exact.int_act(N, sizes, 2 * spec.cin, 2 * spec.cin, g, 0.5, 3)
+    # accumulate: bf16(gx) + base, both integers; |gx| <= 256 by the precondition, so the sum (<= 259) rounds RNE on both sides
+    return c, x2, base
+
+
+def run_slice(ops, dev, c, x2, base, act="lrelu", slope=0.25):
+    """-> (forward out of the slice, statistics partials summed over slots, the accumulated gradient buffer, slots per image)"""
+    spec, low, N = c.spec, c.low, c.N
+    y = torch.zeros(N, *low.out_dims, spec.cout_p, dtype=torch.bfloat16, device=dev)
+    slots, offs = stats_slots(ops, low, low.fwd, N)
+    part = torch.full((N * slots * 2 * spec.cout_p,), float("nan"), dtype=torch.float32, device=dev)
+    ops.gconv_classes(low.fwd, x2.to(dev), c.fpack.to(dev), c.bias.to(dev), y, in_co=spec.cin, act=act, slope=slope, stats=part,
+                      stats_slots=slots, stats_slot0s=offs)
+    G = base.clone().to(dev)
+    for gc in low.dgrad:
+        ops.gconv(gc, c.gy.to(dev), c.dpack.to(dev), None, G, out_co=spec.cin, accumulate=True)
+    if dev != "cpu":
+        torch.cuda.synchronize()
+    part = part.cpu()
+    assert not torch.isnan(part).any()
+    return y.cpu(), part.view(N, slots, 2, spec.cout_p).double().sum(1), G.cpu(), slots
+
+
+_WALK = {}
+
+
+def walk_slice(case):
+    """(case, 2 * cin input buffer, integer base of the gradient buffer, the oracle's run_slice) of a WALK_CASES entry, built
+    once per process: the pin below and the forced-path runs of test_exact_gpu.py share it"""
+    if case not in _WALK:
+        c, x2, base = slice_case(ConvSpec("conv", case[1], case[2], 5, 1, 2, dims=3), case[3], case[4], WALK_SEED)
+        _WALK[case] = (c, x2, base, run_slice(RefOps(), "cpu", c, x2, base))
+    return _WALK[case]
 
 
 def padded(t64, c_pad, dtype):
@@ -120,6 +185,42 @@ def test_oracle_epilogue_activations_are_exact(act, slope):
     ref = torch.where(ref > 0, ref, ref * (0.0 if act == "relu" else slope))
     y, _ = oracle_forward(c, act, slope)
     exact.assert_identical(y, padded(ref, spec.cout_p, torch.bfloat16), f"oracle forward + {act}({slope}) vs float64")
+
+
+# ---- the cases of the persistent-walk tests ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", WALK_CASES, ids=walk_id)
+def test_oracle_slice_and_accumulate_forms_are_exact(case):
+    """run_slice on the oracle against float64 stated directly: the forward of the UPPER half of the 2 * cin buffer (the lower
+    half is live noise) with bias and lrelu(0.25), statistics of the pre-activation values, and the data gradient plus the
+    integer base in the written half only — one RNE rounding of the exactly known sum"""
+    c, x2, base, (y, stats, G, _) = walk_slice(case)
+    spec, N, cin = c.spec, c.N, c.spec.cin
+    assert spec.cin_p == cin and spec.cout_p == spec.cout and torch.equal(x2[..., cin:], c.xa) and x2[..., :cin].any()
+    ref = exact.conv_ref64(spec, x2[..., cin:], c.w, c.b)
+    exact.assert_identical(y, exact.rne_bf16(torch.where(ref > 0, ref, ref * 0.25)), "oracle forward out of a slice vs float64")
+    want = torch.stack([ref.reshape(N, -1, spec.cout).sum(1), (ref * ref).reshape(N, -1, spec.cout).sum(1)], 1)
+    exact.assert_identical(stats, want, "oracle statistics partials (sum, sum of squares) vs float64")
+    gx = exact.dgrad_ref64(spec, c.sizes, c.gy, c.w)
+    assert base[..., cin:].any() and base[..., :cin].any() and gx.any(), "both halves of the base and the gradient must be live"
+    wantG = base.clone()
+    wantG[..., cin:] = exact.rne_bf16(gx + base[..., cin:].double())
+    exact.assert_identical(G, wantG, "oracle data gradient accumulated into a slice vs float64 + base, other half untouched")
+
+
+def test_oracle_is_exact_on_the_strip_walk_case():
+    """forward with statistics and data gradient of WALK_STRIP_CASE (the folded conv itself, as for CONV_CASES)"""
+    spec, N, sizes = WALK_STRIP_CASE[0], WALK_STRIP_CASE[1], WALK_STRIP_CASE[2:]
+    c = exact.make_case(spec, N, sizes, seed=WALK_SEED, check=("fwd", "dgrad"))
+    y, stats = oracle_forward(c)
+    ref = exact.conv_ref64(spec, c.xa, c.w, c.b)
+    exact.assert_identical(y, padded(ref, spec.cout_p, torch.bfloat16), "oracle forward vs float64")
+    co = exact.cout_of(spec)
+    want = torch.zeros(N, 2, spec.cout_p, dtype=torch.float64)
+    want[:, 0, :co] = ref.reshape(N, -1, co).sum(1)
+    want[:, 1, :co] = (ref * ref).reshape(N, -1, co).sum(1)
+    exact.assert_identical(stats, want, "oracle statistics partials (sum, sum of squares) vs float64")
+    gx = exact.dgrad_ref64(spec, sizes, c.gy, c.w)
+    exact.assert_identical(oracle_dgrad(c), padded(gx, spec.cin_p, torch.bfloat16), "oracle data gradient vs float64")
 
 
 # ---- sensitivity: what the exact comparison sees ----------------------------------------------------------------------------

@@ -23,7 +23,8 @@ from ganslate_amd.nn.native.spec import ConvSpec
 from ganslate_amd.nn.native.twin import Twin
 from oracle.ops_ref import RefOps
 from tests import exact
-from tests.test_exact_cpu import ROUNDING_CASES, oracle_dgrad, oracle_forward, oracle_wgrad
+from tests.test_exact_cpu import (ROUNDING_CASES, WALK_CASES, WALK_SEED, WALK_STRIP_CASE, oracle_dgrad, oracle_forward, oracle_wgrad,
+                                  run_slice as _run_slice, slice_case as _slice_case, walk_id, walk_slice)
 from tests.test_ops_gpu import (CONV_CASES, HWGRAD_FT_CASES, MULTI_CASES, PERSIST_CASES, PERSIST_PARITY_CASES, RING_CASES,
                                 SPLITK_MULTI_CASES, STRIP_CASES, WGRAD_PAIR_CASES, WGRAD_ROWS_CASES, WIDE_HALO_CASES, _ids,
                                 stats_slots)
@@ -170,36 +171,7 @@ def test_boundary_convs_on_the_strip_kernels(hip_ops, case):
             check_dgrad(hip_ops, c, f"hstrip {form}")
 
 
-def _slice_case(spec, N, sizes, seed):
-    """a narrow volume layer that reads the upper half of a 2 * cin channel buffer and whose data gradient is accumulated into
-    the upper half of an integer-filled one (the V-Net couplings)"""
-    c = exact.make_case(spec, N, sizes, seed=seed, check=("fwd", "dgrad"))
-    g = torch.Generator().manual_seed(seed + 7)
-    d = c.dom
-    x2 = exact.int_act(N, sizes, 2 * spec.cin, 2 * spec.cin, g, d["dx"], d["mag"])
-    x2[..., spec.cin:] = c.xa
-    base = exact.int_act(N, sizes, 2 * spec.cin, 2 * spec.cin, g, 0.5, 3)
-    # accumulate: bf16(gx) + base, both integers; |gx| <= 256 by the precondition, so the sum (<= 259) rounds RNE on both sides
-    return c, x2, base
-
-
-def _run_slice(ops, dev, c, x2, base, act="lrelu", slope=0.25):
-    spec, low, N = c.spec, c.low, c.N
-    y = torch.zeros(N, *low.out_dims, spec.cout_p, dtype=torch.bfloat16, device=dev)
-    slots, offs = stats_slots(ops, low, low.fwd, N)
-    part = torch.full((N * slots * 2 * spec.cout_p,), float("nan"), dtype=torch.float32, device=dev)
-    ops.gconv_classes(low.fwd, x2.to(dev), c.fpack.to(dev), c.bias.to(dev), y, in_co=spec.cin, act=act, slope=slope, stats=part,
-                      stats_slots=slots, stats_slot0s=offs)
-    G = base.clone().to(dev)
-    for gc in low.dgrad:
-        ops.gconv(gc, c.gy.to(dev), c.dpack.to(dev), None, G, out_co=spec.cin, accumulate=True)
-    if dev != "cpu":
-        torch.cuda.synchronize()
-    part = part.cpu()
-    assert not torch.isnan(part).any()
-    return y.cpu(), part.view(N, slots, 2, spec.cout_p).double().sum(1), G.cpu(), slots
-
-
+# (the slice / accumulate form — _slice_case, _run_slice — lives in tests/test_exact_cpu.py, which pins it to float64)
 def _check_slice(res, ref, base, cin, what):
     exact.assert_identical(res[0], ref[0], f"{what}: forward out of a channel slice")
     exact.assert_identical(res[1], ref[1], f"{what}: statistics partials")
@@ -231,6 +203,122 @@ def test_persistent_narrow_volume_kernel(hip_ops, case):
     for v in (4, 0):
         with hip_ops.options(hconv2=v):
             _check_slice(_run_slice(hip_ops, hip_ops.device, c, x2, base), ref, base, cin, f"hconv2 = {v}")
+
+
+# ---- persistent kernels walking several units per workgroup -----------------------------------------------------------------------
+# WALK_CASES give every workgroup of hconv2_kernel / hconv5_kernel / hstripr_kernel a share of more than one box / segment /
+# tile on the 256 CUs of the target: the hand-off from one unit to the next (the next unit's staging under the current tap
+# loop, the epilogue between them, buffer parities and statistics scratch reused) is then held bit for bit. Each test restates
+# its kernel's launch rule from the CU count and the slot query and asserts the depth the case claims BEFORE it compares: a
+# case that does not walk must not pass on that footing. On another CU count the volume cases skip with the numbers.
+TARGET_CUS = 256
+
+
+def _assert_walk(what, units, grid, depth, uneven, cus=None):
+    """workgroup i takes units i, i + grid, i + 2 * grid, ...: the deepest walk is ceil(units / grid), the shallowest
+    floor(units / grid). cus: the CU count the grid was derived from, where it was"""
+    got = -(-units // grid)
+    line = f"{what}: {units} units on {grid} workgroups, walk depth {got}, shallowest {units // grid}"
+    if cus is not None and cus != TARGET_CUS:
+        pytest.skip(f"{line} on {cus} CUs; the case is sized for {TARGET_CUS} CUs (depth {depth})")
+    print(line)
+    assert got == depth and (units % grid != 0) == uneven and (uneven or units // grid == depth), line
+
+
+def _hconv2_grid(ops, g, N, cus):
+    """csrc/hconv.hip restated -> (boxes, workgroups per channel group, boxes per workgroup). plan(), `h.TI = ...` to
+    `h.cog = ...`: TI tiles of 16 output channels per workgroup (two; one for <= 16 channels and for the small volumes of
+    option values 3 / 4), cog channel groups over blockIdx.y. gs_hconv_try, `gmax`, `per`, `groups`: one workgroup per CU with
+    the channel groups side by side, equal shares. hconv2_kernel: `for (; box < nboxes; box += gridDim.x)`."""
+    boxes = N * ops.stat_slots(g, N)
+    v = ops.get_option("hconv2")
+    small = (v >= 3 and g.Co == 32 and boxes * 2 <= 256) or (v >= 4 and g.Co == 64 and boxes * 4 <= 256)
+    TI = 1 if g.Co <= 16 or small else 2
+    cog = -(-g.Co // (TI * 16))
+    gmax = max(cus // cog, 1)
+    per = -(-boxes // gmax)
+    return boxes, -(-boxes // per), per
+
+
+@pytest.mark.parametrize("case", [c for c in WALK_CASES if c[0] == "hconv2"], ids=walk_id)
+def test_persistent_volume_kernel_walks_several_boxes(hip_ops, case):
+    """hconv2_kernel with 2 - 3 boxes per workgroup and uneven shares (last_unit differs between workgroups): box -> box with
+    two / four channel chunks per box and with one (the halo buffer parity flips per box), forward with statistics out of a
+    slice and the accumulate epilogue between two boxes' staging; hconv2 = 0, the one-box-per-workgroup kernels, alongside"""
+    _, cin, cout, N, sizes, launches, depth, uneven = case
+    cus = torch.cuda.get_device_properties(hip_ops.device).multi_processor_count
+    c, x2, base, ref = walk_slice(case)
+    under = {"fwd": c.low.fwd[0], "dgrad": c.low.dgrad[0]}
+    grid8 = int(np.prod([(s + 7) // 8 for s in sizes]))
+    with hip_ops.options(hconv2=0):
+        slots0 = {k: hip_ops.stat_slots(under[k], N) for k in launches}
+    with hip_ops.options(hconv2=4):
+        for k in launches:
+            g = under[k]
+            # more than 16 output channels on 8-deep boxes is hconv2_kernel alone (plan(), `h.NW = ...`: hconv_kernel's are 4 deep)
+            assert g.Co > 16 and hip_ops.stat_slots(g, N) == grid8 != slots0[k], "hconv2_kernel must take this launch"
+            boxes, grid, per = _hconv2_grid(hip_ops, g, N, cus)
+            _assert_walk(f"hconv2 {k} {g.Ci} -> {g.Co}", boxes, grid, depth, uneven, cus)
+            assert per == depth
+        on = _run_slice(hip_ops, hip_ops.device, c, x2, base)
+    with hip_ops.options(hconv2=0):
+        off = _run_slice(hip_ops, hip_ops.device, c, x2, base)
+    if "fwd" in launches:
+        assert on[3] == grid8 != off[3], (on[3], off[3])
+    _check_slice(on, ref, base, cin, "hconv2 = 4")
+    _check_slice(off, ref, base, cin, "hconv2 = 0")
+
+
+def test_register_resident_k5_kernel_walks_several_segments(hip_ops):
+    """hconv5_kernel with two work items per workgroup: every workgroup restages all planes for a second segment, of another
+    column, while the first one's stores drain; three segments per column, the middle one with its z halo from real planes on
+    both sides, the last one ragged"""
+    case, = [c for c in WALK_CASES if c[0] == "hconv5"]
+    _, cin, cout, N, (D, H, W), launches, depth, uneven = case
+    cus = torch.cuda.get_device_properties(hip_ops.device).multi_processor_count
+    c, x2, base, ref = walk_slice(case)
+    with hip_ops.options(hconv5_seg=0, hconv5=1):
+        for g in (c.low.fwd[0], c.low.dgrad[0]):
+            assert hip_ops.stat_slots(g, N) == (D // 4) * (H // 16) * (W // 16), "hconv5_kernel must take this launch"
+        # csrc/hconv5.hip gs_hconv5_try, `columns` to `grid`, restated: columns of 16 x 16 voxels walked in steps of 4 planes are
+        # cut into z segments until every CU has a workgroup; equal shares of whole segments. hconv5_kernel: `for (int work =
+        # blockIdx.x; work < p.nwork; work += gridDim.x)`, `seg = b % p.nseg`, `nsteps = min(p.seg_steps, ...)` for the last one
+        columns, steps = N * (H // 16) * (W // 16), D // 4
+        nseg = min(max(-(-cus // columns), 1), steps)
+        seg_steps = -(-steps // nseg)
+        nseg = -(-steps // seg_steps)
+        nwork = columns * nseg
+        per = -(-nwork // cus)
+        grid = -(-nwork // per)
+        _assert_walk(f"hconv5 {columns} columns x {nseg} segments of <= {seg_steps} steps", nwork, grid, depth, uneven, cus)
+        assert per == depth and [min(seg_steps, steps - s * seg_steps) for s in range(nseg)] == [3, 3, 1]
+        assert grid % nseg == 0 and grid // nseg < columns, "a workgroup's second unit is a segment of ANOTHER column"
+        on = _run_slice(hip_ops, hip_ops.device, c, x2, base)
+    with hip_ops.options(hconv5_seg=0, hconv5=0):
+        off = _run_slice(hip_ops, hip_ops.device, c, x2, base)
+    assert on[3] == (D // 4) * (H // 16) * (W // 16) and off[3] != on[3], (on[3], off[3])
+    _check_slice(on, ref, base, cin, "hconv5")
+    _check_slice(off, ref, base, cin, "hconv5 = 0")
+
+
+def test_strip_register_kernel_walks_several_tiles(hip_ops):
+    """hstripr_kernel<32,64,32>'s forward WITH statistics on more tiles than workgroups (160 of the 512 walk two; ragged tile
+    rows), and the <64,32,16> data gradient of the same layer (2 - 3 tiles per workgroup)"""
+    spec, N, sizes = WALK_STRIP_CASE[0], WALK_STRIP_CASE[1], WALK_STRIP_CASE[2:]
+    c = exact.make_case(spec, N, sizes, seed=WALK_SEED, check=("fwd", "dgrad"))
+    with hip_ops.options(hstrip=1, hstrip_regs=2):
+        # csrc/hstrip.hip restated. plan(), `tr = h.ci == 32 ? 32 : 16`: the register form takes 32 -> 64 channels on tiles of
+        # 32 rows x 8 columns and 64 -> 32 on 16 x 8. gs_hstrip_try, `groups = blocks < 512 ? blocks : 512`. hstripr_kernel:
+        # `for (int tile = tile0 + gx; tile < ntiles; tile += gnum)`, gnum = gridDim.x for one network
+        for g, chans, rows, tiles_want, depth, what in ((c.low.fwd[0], (32, 64), 32, 672, 2, "forward with statistics"),
+                                                        (c.low.dgrad[0], (64, 32), 16, 1248, 3, "data gradient")):
+            per_img = ((g.Ho + rows - 1) // rows) * ((g.Wo + 7) // 8)
+            assert (g.Ci, g.Co) == chans and hip_ops.stat_slots(g, N) == per_img, "the register strip kernel must take this launch"
+            tiles = N * per_img
+            assert tiles == tiles_want and tiles > 512 and g.Ho % rows, (tiles, g.Ho)
+            _assert_walk(f"hstripr {what}", tiles, min(tiles, 512), depth, True)
+        check_forward(hip_ops, c, "hstripr walk")
+        check_dgrad(hip_ops, c, "hstripr walk")
 
 
 def test_accumulate_through_split_k(hip_ops):
