@@ -970,6 +970,67 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_ssim_distance(_ptr(x), _ptr(y), NC, H, W, _ptr(out), _ptr(scratch), _stream()),
                 "gs_ssim_distance")
 
+    # ---- MIND structure-consistency loss (mind.hip) ---------------------------------------------------------------
+    MIND_CONFIG = {"non_local_region_size": 9, "patch_size": 7, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
+
+    @staticmethod
+    def _mind_check(*images):
+        """ValueError before any launch: [N, C, H, W] fp32 dense tensors on one device, equal in N, H and W"""
+        for t in images:
+            if t.dim() != 4:
+                raise ValueError(f"the MIND descriptor takes [N, C, H, W] images (volumes are not supported); got {tuple(t.shape)}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"the MIND kernels take fp32 images; got {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError("the MIND kernels take dense (contiguous) images")
+            if t.numel() == 0:
+                raise ValueError(f"empty image batch {tuple(t.shape)}")
+        a = images[0]
+        for t in images[1:]:
+            if (t.shape[0], t.shape[2], t.shape[3]) != (a.shape[0], a.shape[2], a.shape[3]) or t.device != a.device:
+                raise ValueError(f"MIND loss: images differ in batch, extent or device: {tuple(a.shape)} vs {tuple(t.shape)}")
+
+    def _mind_args(self, cfg):
+        cfg = dict(self.MIND_CONFIG, **(cfg or {}))
+        return (int(cfg["non_local_region_size"]), int(cfg["patch_size"]), int(cfg["neighbor_size"]),
+                float(cfg["gaussian_patch_sigma"]))
+
+    def mind_descriptor(self, x, out=None, cfg=None):
+        """[N, C, H, W] fp32 -> [N, 81, H, W] MIND features of the channel mean (gs_mind_descriptor)"""
+        self._mind_check(x)
+        N, Cc, H, W = x.shape
+        if out is None:
+            out = torch.empty((N, 81, H, W), dtype=torch.float32, device=x.device)
+        self._mind_check(out)
+        if tuple(out.shape) != (N, 81, H, W):
+            raise ValueError(f"mind_descriptor: out must be {(N, 81, H, W)}, got {tuple(out.shape)}")
+        L.check(self.lib.gs_mind_descriptor(_ptr(x), N, Cc, H, W, *self._mind_args(cfg), _ptr(out), _stream()),
+                "gs_mind_descriptor")
+        return out
+
+    def mind_l1(self, x, y, out, cfg=None):
+        """out (0-d fp32) = sum |MIND(x) - MIND(y)| / (H W 81): a sum over the batch, unweighted (gs_mind_l1)"""
+        self._mind_check(x, y)
+        if out.dtype != torch.float32 or out.numel() != 1:
+            raise ValueError("mind_l1: out must hold one fp32 value")
+        N, Cx, H, W = x.shape
+        scratch = torch.empty(self.lib.gs_mind_scratch_bytes(N, H, W, 0), dtype=torch.uint8, device=x.device)
+        L.check(self.lib.gs_mind_l1(_ptr(x), _ptr(y), N, Cx, y.shape[1], H, W, *self._mind_args(cfg), _ptr(out),
+                                    _ptr(scratch), _stream()), "gs_mind_l1")
+
+    def mind_l1_backward(self, x, y, grad_y, grad_scale=None, cfg=None):
+        """grad_y = grad_scale * d mind_l1(x, y) / dy; grad_scale is a device scalar (gs_mind_l1_backward)"""
+        self._mind_check(x, y)
+        self._mind_check(grad_y)
+        if grad_y.shape != y.shape:
+            raise ValueError(f"mind_l1_backward: grad_y must have y's shape {tuple(y.shape)}, got {tuple(grad_y.shape)}")
+        if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1):
+            raise ValueError("mind_l1_backward: grad_scale must hold one fp32 value")
+        N, Cx, H, W = x.shape
+        scratch = torch.empty(self.lib.gs_mind_scratch_bytes(N, H, W, 1), dtype=torch.uint8, device=x.device)
+        L.check(self.lib.gs_mind_l1_backward(_ptr(x), _ptr(y), N, Cx, y.shape[1], H, W, *self._mind_args(cfg),
+                                             _ptr(grad_scale), _ptr(grad_y), _ptr(scratch), _stream()), "gs_mind_l1_backward")
+
     # ---- validation / test image metrics (valmetrics.hip) --------------------------------------------------
     VALMETRIC_COLUMNS = ("mae", "mse", "nmse", "psnr", "ssim", "nmi", "histogram_chi2")
 

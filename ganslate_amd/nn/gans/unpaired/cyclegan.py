@@ -23,6 +23,8 @@ class OptimizerConfig(configs.base.BaseOptimizerConfig):
     lambda_BA: float = 10.0
     lambda_identity: float = 0
     proportion_ssim: float = 0.84
+    # weight of the structure-consistency (MIND) loss between real_A / fake_B and real_B / fake_A; 0 = off
+    lambda_structure: float = 0
 
 
 @dataclass
@@ -40,6 +42,8 @@ class CycleGAN(BaseGAN):
         visual_names = ["real_A", "fake_B", "rec_A", "idt_A", "real_B", "fake_A", "rec_B", "idt_B"]
         self.visuals = {name: None for name in visual_names}
         loss_names = ["G_AB", "D_B", "cycle_A", "idt_A", "G_BA", "D_A", "cycle_B", "idt_B"]
+        if getattr(conf.train.gan.optimizer, "lambda_structure", 0) > 0:
+            loss_names += ["structure_AB", "structure_BA"]
         self.losses = {name: None for name in loss_names}
         self.optimizers = {name: None for name in ["G", "D"]}
         network_names = ["G_AB", "G_BA", "D_B", "D_A"] if self.is_train else ["G_AB"]
@@ -47,6 +51,7 @@ class CycleGAN(BaseGAN):
         if self.is_train:
             self.fake_A_pool = ImagePool(conf.train.gan.pool_size)
             self.fake_B_pool = ImagePool(conf.train.gan.pool_size)
+        self._structure_fakes = {}
         self.setup()
         self._init_twins()
 
@@ -121,6 +126,7 @@ class CycleGAN(BaseGAN):
             # each generated image feeds the other generator now and its discriminator in the G step: two aliases whose
             # gradients the library adds (losses/functional.py:fanout) instead of autograd's accumulation
             (fake_B, fake_B2), (fake_A, fake_A2) = fanout(fake_B), fanout(fake_A)
+            fake_B, fake_A = self._structure_aliases(fake_B, fake_A)
             rec_B, rec_A = self.twin_G(fake_A2, fake_B2)
             idt_B, idt_A = self.twin_G(real_B, real_A) if self.criterion_G.is_using_identity() else (None, None)
             self.visuals.update({"fake_B": fake_B, "rec_A": rec_A, "idt_A": idt_A,
@@ -133,9 +139,11 @@ class CycleGAN(BaseGAN):
         idt_B, idt_A = None, None
         self.fork_side_work("cycle_B")
         fake_B, fake_B2 = fanout(self.networks["G_AB"](real_A))
+        fake_B, _ = self._structure_aliases(fake_B, None)
         rec_A = self.networks["G_BA"](fake_B2)
         with self.side_work("cycle_B"):
             fake_A, fake_A2 = fanout(self.networks["G_BA"](real_B))
+            _, fake_A = self._structure_aliases(None, fake_A)
             rec_B = self.networks["G_AB"](fake_A2)
             if use_idt:
                 idt_B = self.networks["G_AB"](real_B)
@@ -144,6 +152,18 @@ class CycleGAN(BaseGAN):
         self.join_side_work("cycle_B", last=False)
         self.visuals.update({"fake_B": fake_B, "rec_A": rec_A, "idt_A": idt_A,
                              "fake_A": fake_A, "rec_B": rec_B, "idt_B": idt_B})
+
+    def _structure_aliases(self, fake_B, fake_A):
+        """With the structure loss on, a generated image has a third consumer that sends a gradient back (the other
+        generator, its discriminator, the structure term): a second, nested fanout, so that this sum too is the library's
+        kernel. The structure term's aliases wait in self._structure_fakes for backward_G. Off: nothing changes."""
+        if not self.criterion_G.is_using_structure():
+            return fake_B, fake_A
+        if fake_B is not None:
+            fake_B, self._structure_fakes["fake_B"] = fanout(fake_B)
+        if fake_A is not None:
+            fake_A, self._structure_fakes["fake_A"] = fanout(fake_A)
+        return fake_B, fake_A
 
     def backward_D(self, discriminator):
         if discriminator == "D_B":
@@ -191,7 +211,8 @@ class CycleGAN(BaseGAN):
         self.fork_side_work()
         self.losses["G_AB"] = self.criterion_adv(pred_B, target_is_real=True)
         self.losses["G_BA"] = self.criterion_adv(pred_A, target_is_real=True)
-        losses_G = self.criterion_G(self.visuals)
+        # (structure loss on: it reads its own aliases of the generated images, see _structure_aliases)
+        losses_G = self.criterion_G(dict(self.visuals, **self._structure_fakes) if self._structure_fakes else self.visuals)
         self.losses.update(losses_G)
         combined_loss_G = scalar_sum(list(losses_G.values()) + [self.losses["G_AB"], self.losses["G_BA"]])
         self.backward(loss=combined_loss_G, optimizer=self.optimizers["G"], loss_id=0)

@@ -1,5 +1,5 @@
 """Autograd entry points of the fused loss kernels (libganslate_hip: gs_l1, gs_mse_const, gs_adv_loss, gs_mean,
-gs_ssim_distance). Each forward is one wavefront-reduced kernel writing a 0-d fp32 tensor; each backward is one
+gs_ssim_distance, gs_mind_l1). Each forward is one wavefront-reduced kernel writing a 0-d fp32 tensor; each backward is one
 elementwise kernel that folds the upstream scalar gradient in (passed as a device pointer — no host sync)."""
 import torch
 
@@ -118,6 +118,48 @@ class _SSIMDistance(torch.autograd.Function):
 def ssim_distance_autograd(X, Y):
     """Differentiable SSIM distance for `proportion_ssim > 0` (cyclegan_losses.py:78-90; SSIMLoss on (x+1)/2)."""
     return _SSIMDistance.apply(X.float(), Y.float())
+
+
+class _MINDL1(torch.autograd.Function):
+    """L1 distance of the MIND descriptors of two image batches, sum |f^X - f^Y| / (H W 81) (a sum over the batch): fused
+    forward (gs_mind_l1, no 81-channel map in memory) and hand-written backward (gs_mind_l1_backward); the distance is
+    symmetric, so the gradient w.r.t. the first image is the same kernel with the arguments swapped, and each side is
+    computed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, X, Y):
+        ops = get_ops()
+        if not hasattr(ops, "mind_l1"):
+            raise NotImplementedError(f"the '{getattr(ops, 'name', type(ops).__name__)}' backend has no MIND structure loss "
+                                      "(mind_l1 / mind_l1_backward)")
+        X, Y = X.contiguous(), Y.contiguous()
+        out = torch.empty((), dtype=torch.float32, device=X.device)
+        ops.mind_l1(X, Y, out)
+        ctx.save_for_backward(X, Y)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, Y = ctx.saved_tensors
+        g = g.contiguous().float()
+        gx = gy = None
+        if ctx.needs_input_grad[1]:
+            gy = torch.empty_like(Y)
+            get_ops().mind_l1_backward(X, Y, gy, grad_scale=g)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(X)
+            get_ops().mind_l1_backward(Y, X, gx, grad_scale=g)
+        return gx, gy
+
+
+def mind_structure_autograd(X, Y):
+    """Differentiable structure-consistency distance sum |MIND(X) - MIND(Y)| / (H W 81) of two [N, C, H, W] batches
+    (StructureLoss of the reference's cleargrasp project, without lambda_structure; a sum over the batch, not a mean).
+    Images with several channels are reduced by their channel mean first; X and Y may differ in channels."""
+    for t in (X, Y):
+        if t.dim() != 4:
+            raise ValueError(f"the structure loss takes [N, C, H, W] images (volumes are not supported); got {tuple(t.shape)}")
+    return _MINDL1.apply(X.float(), Y.float())
 
 
 class _ScalarAffine(torch.autograd.Function):

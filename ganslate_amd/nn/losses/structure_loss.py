@@ -1,0 +1,56 @@
+"""Structure-consistency loss (Yang et al. 2018) between an image and its translation — interface of StructureLoss /
+MINDDescriptor in the reference's projects/cleargrasp_depth_estimation/modules/old/cyclegan_losses_with_structure.py:41-182
+and of its tutorial docs/tutorials_basic/2_new_project.md, on the fused kernels of csrc/mind.hip.
+
+The descriptor is fixed to MIND_DESCRIPTOR_CONFIG (non-local region 9x9, patch 7x7, neighbourhood 3x3, sigma 2). Images
+with several channels are reduced to one plane by the mean over their channels; the project-specific channel slicing of the
+reference's v1 / v2 variants is left to the caller (slice before calling)."""
+import torch
+
+from ..native.backend import get_ops
+from .functional import mind_structure_autograd, scalar_affine
+
+MIND_DESCRIPTOR_CONFIG = {"non_local_region_size": 9, "patch_size": 7, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
+
+
+def _need(ops, method):
+    if not hasattr(ops, method):
+        raise NotImplementedError(f"the '{getattr(ops, 'name', type(ops).__name__)}' backend has no MIND kernels "
+                                  f"(missing ops.{method})")
+
+
+class MINDDescriptor:
+    """image [N, C, H, W] -> features [N, 81, H, W]; channel i is the shift with row offset i % 9 - 4 and column offset
+    i // 9 - 4. No gradient flows through it: the differentiable path is StructureLoss."""
+
+    def __init__(self, **config):
+        unknown = set(config) - set(MIND_DESCRIPTOR_CONFIG)
+        if unknown:
+            raise TypeError(f"unknown MIND descriptor setting(s): {sorted(unknown)}")
+        self.config = dict(MIND_DESCRIPTOR_CONFIG, **config)
+
+    def __call__(self, image):
+        if image.dim() != 4:
+            raise ValueError(f"the MIND descriptor takes [N, C, H, W] images (volumes are not supported); got {tuple(image.shape)}")
+        ops = get_ops()
+        _need(ops, "mind_descriptor")
+        with torch.no_grad():
+            return ops.mind_descriptor(image.detach().contiguous().float(), cfg=self.config)
+
+
+class StructureLoss:
+    """lambda_structure * sum_{n,a,p} |f_a(input) - f_a(fake)| / (H W 81). As in the reference this is a SUM over the
+    batch, not a mean: the loss grows with the batch size."""
+
+    def __init__(self, lambda_structure):
+        self.lambda_structure = lambda_structure
+
+    def terms(self, input_, fake):
+        """[(weight, 0-d loss)] whose weighted sum is the loss"""
+        _need(get_ops(), "mind_l1")
+        _need(get_ops(), "mind_l1_backward")
+        return [(self.lambda_structure, mind_structure_autograd(input_, fake))]
+
+    def __call__(self, input_, fake):
+        (w, x), = self.terms(input_, fake)
+        return scalar_affine([x], [[w]])[0]

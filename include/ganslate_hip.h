@@ -522,6 +522,32 @@ int gs_ssim_distance_backward(const float* x, const float* y, int32_t NC, int32_
                               const float* grad_scale, float* grad_y, float* scratch, void* stream);
 int64_t gs_ssim_backward_scratch_floats(int32_t NC, int32_t H, int32_t W);
 
+/* ---- MIND structure-consistency loss (mind.hip) ----
+ * The reference's MINDDescriptor / StructureLoss of
+ * projects/cleargrasp_depth_estimation/modules/old/cyclegan_losses_with_structure.py (Yang et al. 2018). Images are fp32
+ * NCHW, contiguous; an image with C > 1 channels is reduced to one plane by the mean over its channels first (:69,:81-82).
+ * Only nl_size 9, patch_size 7, neighbor_size 3 (MIND_DESCRIPTOR_CONFIG, :7) are built, anything else is refused; sigma
+ * (gaussian_patch_sigma) is free. The patch weights are exp(-|q|_2 / sigma^2) with the Euclidean distance, not its square,
+ * not normalised (:126-135). No float atomics: results are bitwise reproducible. All launches go to `stream`. */
+/* out = [N, 81, H, W] features, channel i = the shift with row offset i % 9 - 4, column offset i / 9 - 4
+ * (MINDDescriptor.forward, :158-182) */
+int gs_mind_descriptor(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t nl_size, int32_t patch_size,
+                       int32_t neighbor_size, float sigma, float* out, void* stream);
+/* out[0] = sum_{n,a,p} |f_a^x - f_a^y| / (H W 81): StructureLoss.__call__ (:72-74,:89-91) without its lambda_structure; a sum
+ * over the batch, not a mean. x has Cx channels, y has Cy. No 81-channel map is written to memory. scratch =
+ * gs_mind_scratch_bytes(N, H, W, 0) bytes. */
+int gs_mind_l1(const float* x, const float* y, int32_t N, int32_t Cx, int32_t Cy, int32_t H, int32_t W, int32_t nl_size,
+               int32_t patch_size, int32_t neighbor_size, float sigma, float* out, void* scratch, void* stream);
+/* gradient of gs_mind_l1 w.r.t. y (the loss is symmetric: swap x and y for the other one), [N, Cy, H, W], scaled by the
+ * upstream scalar grad_scale[0] (device pointer, NULL = 1): autograd's backward through :72-74,:89-91 and :158-182.
+ * scratch = gs_mind_scratch_bytes(N, H, W, 1) bytes. */
+int gs_mind_l1_backward(const float* x, const float* y, int32_t N, int32_t Cx, int32_t Cy, int32_t H, int32_t W,
+                        int32_t nl_size, int32_t patch_size, int32_t neighbor_size, float sigma, const float* grad_scale,
+                        float* grad_y, void* scratch, void* stream);
+/* bytes of scratch for gs_mind_l1 (backward = 0: one partial per tile) or gs_mind_l1_backward (backward = 1: 171 planes
+ * per sample, in place of the tensors autograd keeps for :172-181) */
+int64_t gs_mind_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t backward);
+
 /* ---- validation / test image metrics (ganslate/utils/metrics/val_test_metrics.py:37-166, valmetrics.hip) ----
  * t (target) and p (prediction): N samples of P planes of H x W fp32, contiguous. table = device [N][7] fp64, one row per
  * sample: mae, mse, nmse (:37-53), psnr = 10 log10(max(t)^2 / mse) (:56-59), ssim = mean over the P planes of skimage
