@@ -205,3 +205,130 @@ extern "C" int gs_image_to_act_backward(const void* g_pad, float* g_img, int32_t
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// ---- channel sources ------------------------------------------------------------------------------------------------------
+// Up to GS_CAT_MAX_SRCS image tensors side by side along the channel axis, each a channel window of a dense [N, C, S] fp32
+// tensor: N blocks of channels * S contiguous floats, `stride` floats from one sample to the next, `ptr` at the window's first
+// element (c0 * S floats into the tensor). torch.cat([fake_Bt, real_A[:, guide]], dim=1) and real_B[:, tB] -> bf16 activation
+// in one pass, no concatenated or sliced tensor in memory. A window base is in general not 16-byte aligned (odd S): every
+// source read is a scalar fp32 load, coalesced along the pixels; rounding and the zeroed pad lanes are image_to_act_kernel's.
+struct ChanSrcs {
+  const float* ptr[GS_CAT_MAX_SRCS];
+  long long stride[GS_CAT_MAX_SRCS];
+  int ch[GS_CAT_MAX_SRCS];
+  int n;
+};
+
+__global__ __launch_bounds__(256) void image_cat_to_act_kernel(const ChanSrcs s, unsigned short* act, long long hw, int Cp) {
+  const int n = blockIdx.y;
+  unsigned short* out = act + (size_t)n * hw * Cp;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
+    for (int c0 = 0; c0 < Cp; c0 += 8) {
+      float f[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        int b = c0 + k;           // channel within source j once 0 <= b < ch[j]
+        float v = 0.f;
+#pragma unroll
+        for (int j = 0; j < GS_CAT_MAX_SRCS; ++j) {
+          if (j < s.n) {
+            if (b >= 0 && b < s.ch[j]) v = s.ptr[j][(size_t)n * s.stride[j] + (size_t)b * hw + p];
+            b -= s.ch[j];
+          }
+        }
+        f[k] = v;
+      }
+      uint4 o;
+      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
+      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = o;
+    }
+  }
+}
+
+// its gradient: the channels of source j, as a dense [N, ch[j], S] fp32 tensor at grad[j]; a null grad[j] is left alone
+struct ChanGrads {
+  float* ptr[GS_CAT_MAX_SRCS];
+  int ch[GS_CAT_MAX_SRCS];
+  int n;
+};
+
+__global__ __launch_bounds__(256) void image_cat_to_act_bwd_kernel(const unsigned short* g, const ChanGrads s, long long hw,
+                                                                   int Cp) {
+  const int n = blockIdx.y;
+  const unsigned short* gp = g + (size_t)n * hw * Cp;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
+    int off = 0;
+#pragma unroll
+    for (int j = 0; j < GS_CAT_MAX_SRCS; ++j) {
+      if (j < s.n) {
+        if (s.ptr[j])
+          for (int c = 0; c < s.ch[j]; ++c) s.ptr[j][((size_t)n * s.ch[j] + c) * hw + p] = bf2f(gp[(size_t)p * Cp + off + c]);
+        off += s.ch[j];
+      }
+    }
+  }
+}
+
+extern "C" int gs_image_cat_to_act(const float* const* src, const int64_t* sample_stride, const int32_t* channels, int32_t K,
+                                   void* act, int32_t N, int64_t S, int32_t Cp, void* stream) {
+  GS_REQUIRE(src && sample_stride && channels && act && K >= 1 && K <= GS_CAT_MAX_SRCS && N > 0 && N <= 65535 && S > 0 &&
+             Cp > 0 && (Cp & 7) == 0, "gs_image_cat_to_act: bad argument");
+  ChanSrcs s{};
+  long long total = 0;
+  for (int j = 0; j < K; ++j) {
+    GS_REQUIRE(src[j] && channels[j] > 0 && sample_stride[j] >= (int64_t)channels[j] * S,
+               "gs_image_cat_to_act: a source needs a pointer, channels > 0 and a sample stride >= channels * S");
+    s.ptr[j] = src[j]; s.stride[j] = sample_stride[j]; s.ch[j] = channels[j];
+    total += channels[j];
+  }
+  GS_REQUIRE(total <= Cp, "gs_image_cat_to_act: the sources hold more channels than the activation");
+  s.n = K;
+  hipLaunchKernelGGL(image_cat_to_act_kernel, img_grid(S, N), dim3(256), 0, static_cast<hipStream_t>(stream), s,
+                     static_cast<unsigned short*>(act), (long long)S, Cp);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gs_image_cat_to_act_backward(const void* g, float* const* grad, const int32_t* channels, int32_t K, int32_t N,
+                                            int64_t S, int32_t Cp, void* stream) {
+  GS_REQUIRE(g && grad && channels && K >= 1 && K <= GS_CAT_MAX_SRCS && N > 0 && N <= 65535 && S > 0 && Cp > 0,
+             "gs_image_cat_to_act_backward: bad argument");
+  ChanGrads s{};
+  long long total = 0;
+  bool any = false;
+  for (int j = 0; j < K; ++j) {
+    GS_REQUIRE(channels[j] > 0, "gs_image_cat_to_act_backward: a source needs channels > 0");
+    s.ptr[j] = grad[j]; s.ch[j] = channels[j];
+    total += channels[j];
+    any = any || grad[j];
+  }
+  GS_REQUIRE(total <= Cp, "gs_image_cat_to_act_backward: the sources hold more channels than the activation gradient");
+  GS_REQUIRE(any, "gs_image_cat_to_act_backward: no source asks for a gradient");
+  s.n = K;
+  hipLaunchKernelGGL(image_cat_to_act_bwd_kernel, img_grid(S, N), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(g), s, (long long)S, Cp);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// dst[N, C, S] = zeros with src[N, t, S] at channels [c0, c0 + t): the generated channels next to zeroed guide channels
+// (the visuals and infer() of the balanced CycleGAN). One workgroup row per (sample, channel); every element of dst is written
+// exactly once, scalar stores (neither plane base need be 16-byte aligned).
+__global__ __launch_bounds__(256) void channel_embed_kernel(const float* src, float* dst, int C, int c0, int t, long long hw) {
+  const int n = blockIdx.y / C, c = blockIdx.y - n * C;
+  float* out = dst + (size_t)blockIdx.y * hw;
+  const bool live = c >= c0 && c < c0 + t;
+  const float* in = live ? src + ((size_t)n * t + (c - c0)) * hw : nullptr;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x)
+    out[p] = live ? in[p] : 0.f;
+}
+
+extern "C" int gs_channel_embed(const float* src, float* dst, int32_t N, int32_t C, int32_t c0, int32_t t, int64_t S,
+                                void* stream) {
+  GS_REQUIRE(src && dst && N > 0 && C > 0 && t > 0 && c0 >= 0 && (int64_t)c0 + t <= C && S > 0 && (int64_t)N * C <= 65535,
+             "gs_channel_embed: bad argument (the window [c0, c0 + t) must lie inside C, N * C <= 65535)");
+  hipLaunchKernelGGL(channel_embed_kernel, img_grid(S, N * C), dim3(256), 0, static_cast<hipStream_t>(stream), src, dst, C,
+                     c0, t, (long long)S);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}

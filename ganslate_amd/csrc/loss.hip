@@ -205,6 +205,51 @@ extern "C" int gs_l1(const float* a, const float* b, int64_t n, float* loss, flo
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
+// gs_l1 with a strided first operand (a channel window of a real image): sample n of `a` is `per` contiguous floats at
+// a + n * stride, b is dense. The flat index i = n * per + r walks the grid-stride loop of l1_kernel (same partial sums, same
+// final order); (n, r) follow it without a division per element. The gradient is the dense operand's: sign(b - a) * k.
+__global__ __launch_bounds__(256) void l1_window_kernel(const float* a, long long stride, const float* b, long long per,
+                                                        long long n, float* ws, float* loss) {
+  __shared__ float sh[4];
+  float s = 0.f;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long smp = i / per, r = i - smp * per;
+  for (; i < n; i += step) {
+    s += fabsf(a[smp * stride + r] - b[i]);
+    r += step;
+    if (r >= per) { const long long q = r / per; smp += q; r -= q * per; }      // (a division only where a sample ends)
+  }
+  s = block_sum(s, sh);
+  finish_reduction(s, ws, 1.0f / (float)n, loss);
+}
+__global__ __launch_bounds__(256) void l1_window_grad_kernel(const float* a, long long stride, const float* b, long long per,
+                                                             long long n, float* grad_b, const float* gscale) {
+  const float k = (gscale ? gscale[0] : 1.f) / (float)n;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long smp = i / per, r = i - smp * per;
+  for (; i < n; i += step) {
+    const float d = a[smp * stride + r] - b[i];
+    grad_b[i] = d > 0.f ? -k : (d < 0.f ? k : 0.f);
+    r += step;
+    if (r >= per) { const long long q = r / per; smp += q; r -= q * per; }      // (a division only where a sample ends)
+  }
+}
+extern "C" int gs_l1_window(const float* a, int64_t a_sample_stride, const float* b, int32_t N, int64_t per, float* loss,
+                            float* grad_b, const float* grad_scale, void* stream) {
+  GS_REQUIRE(a && b && N > 0 && per > 0 && a_sample_stride >= per && (loss || grad_b), "gs_l1_window: bad argument");
+  float* ws = gs_reduce_workspace(stream);
+  if (!ws) { if (!gs_zero_page()) gs_set_error("gs_l1_window: library not initialised (call gs_init)"); return 2; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)N * per;
+  if (loss) hipLaunchKernelGGL(l1_window_kernel, dim3(red_blocks(n)), dim3(256), 0, st, a, (long long)a_sample_stride, b,
+                               (long long)per, n, ws, loss);
+  if (grad_b) hipLaunchKernelGGL(l1_window_grad_kernel, dim3(red_blocks(n)), dim3(256), 0, st, a, (long long)a_sample_stride, b,
+                                 (long long)per, n, grad_b, grad_scale);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 extern "C" int gs_mean(const float* x, int64_t n, float* out, void* stream) {
   GS_REQUIRE(x && out && n > 0, "gs_mean: bad argument");
   float* ws = gs_reduce_workspace(stream);
@@ -241,8 +286,10 @@ __device__ __forceinline__ SsimTerms ssim_terms(float m1, float m2, float xx, fl
   return t;
 }
 
-__global__ __launch_bounds__(256) void ssim_kernel(const float* x, const float* y, int H, int W, int tiles_w,
-                                                   int tiles_h, float* partial) {
+// x may be a channel window: plane p of sample n at x + n * xstride + p * H * W, xpl planes per sample (dense: xpl = all
+// planes, one "sample")
+__global__ __launch_bounds__(256) void ssim_kernel(const float* x, int xpl, long long xstride, const float* y, int H, int W,
+                                                   int tiles_w, int tiles_h, float* partial) {
   __shared__ float sx[SSIM_TH + 10][SSIM_TW + 10];
   __shared__ float sy[SSIM_TH + 10][SSIM_TW + 10];
   __shared__ float hz[5][SSIM_TH + 10][SSIM_TW];
@@ -252,7 +299,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* x, const float* 
   const int th = b % tiles_h; const int plane = b / tiles_h;
   const int Ho = H - 10, Wo = W - 10;
   const int oh0 = th * SSIM_TH, ow0 = tw * SSIM_TW;
-  const float* xp = x + (size_t)plane * H * W;
+  const float* xp = x + (size_t)(plane / xpl) * xstride + (size_t)(plane % xpl) * H * W;
   const float* yp = y + (size_t)plane * H * W;
   for (int e = threadIdx.x; e < (SSIM_TH + 10) * (SSIM_TW + 10); e += 256) {
     const int r = e / (SSIM_TW + 10), c = e % (SSIM_TW + 10);
@@ -319,16 +366,116 @@ extern "C" int64_t gs_ssim_scratch_floats(int32_t NC, int32_t H, int32_t W) {
   const int64_t th = (H - 10 + SSIM_TH - 1) / SSIM_TH, tw = (W - 10 + SSIM_TW - 1) / SSIM_TW;
   return (int64_t)NC * th * tw;
 }
-extern "C" int gs_ssim_distance(const float* x, const float* y, int32_t NC, int32_t H, int32_t W, float* out,
-                                float* scratch, void* stream) {
-  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance: bad argument");
+// The window form's forward in double: the balanced recipe's translated channels are often one small plane per sample (a
+// 3 x 12 x 11 volume has 6 valid pixels), where nothing averages the per-pixel fp32 error of the cancelling variance terms out
+// (measured 6.8e-7 relative on such an input, fp32 in any operation order 5e-9 .. 1.1e-6). Same tiling, same fp32 Gaussian
+// weights (the reference's, ssim.py:22-40) widened exactly; the (x + 1) / 2 mapping, the five blurred moments, S and the sums in
+// double; one double partial per tile, summed in index order. What is left is the weights' rounding (~1.5e-7) and the final
+// rounding of the mean to fp32. The gradient kernels are the dense ones.
+// (no contraction, as in ssim_terms: identical images give S = 0 exactly)
+__device__ __forceinline__ double ssim_s_double(double m1, double m2, double xx, double yy, double xy) {
+#pragma clang fp contract(off)
+  const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+  const double m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
+  const double S1 = (2.0 * m12 + C1) / ((m11 + m22) + C1);
+  const double S2 = (2.0 * (xy - m12) + C2) / (((xx - m11) + (yy - m22)) + C2);
+  return 2.0 - (S1 + S2);
+}
+__global__ __launch_bounds__(256) void ssim_window_kernel(const float* x, int xpl, long long xstride, const float* y, int H,
+                                                          int W, int tiles_w, int tiles_h, double* partial) {
+  __shared__ double sx[SSIM_TH + 10][SSIM_TW + 10];
+  __shared__ double sy[SSIM_TH + 10][SSIM_TW + 10];
+  __shared__ double hz[5][SSIM_TH + 10][SSIM_TW];
+  int b = blockIdx.x;
+  const int tw = b % tiles_w; b /= tiles_w;
+  const int th = b % tiles_h; const int plane = b / tiles_h;
+  const int Ho = H - 10, Wo = W - 10;
+  const int oh0 = th * SSIM_TH, ow0 = tw * SSIM_TW;
+  const float* xp = x + (size_t)(plane / xpl) * xstride + (size_t)(plane % xpl) * H * W;
+  const float* yp = y + (size_t)plane * H * W;
+  for (int e = threadIdx.x; e < (SSIM_TH + 10) * (SSIM_TW + 10); e += 256) {
+    const int r = e / (SSIM_TW + 10), c = e % (SSIM_TW + 10);
+    const int ih = oh0 + r, iw = ow0 + c;
+    double a = 0.0, bb = 0.0;
+    if (ih < H && iw < W) { a = ((double)xp[(size_t)ih * W + iw] + 1.0) * 0.5; bb = ((double)yp[(size_t)ih * W + iw] + 1.0) * 0.5; }
+    sx[r][c] = a; sy[r][c] = bb;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < (SSIM_TH + 10) * SSIM_TW; e += 256) {
+    const int r = e / SSIM_TW, c = e % SSIM_TW;
+    double m1 = 0.0, m2 = 0.0, xx = 0.0, yy = 0.0, xy = 0.0;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) {
+      const double g = (double)c_gauss[k], a = sx[r][c + k], bb = sy[r][c + k];
+      m1 += g * a; m2 += g * bb; xx += g * a * a; yy += g * bb * bb; xy += g * a * bb;
+    }
+    hz[0][r][c] = m1; hz[1][r][c] = m2; hz[2][r][c] = xx; hz[3][r][c] = yy; hz[4][r][c] = xy;
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int e = threadIdx.x; e < SSIM_TH * SSIM_TW; e += 256) {
+    const int r = e / SSIM_TW, c = e % SSIM_TW;
+    if (oh0 + r < Ho && ow0 + c < Wo) {
+      double m1 = 0.0, m2 = 0.0, xx = 0.0, yy = 0.0, xy = 0.0;
+#pragma unroll
+      for (int k = 0; k < 11; ++k) {
+        const double g = (double)c_gauss[k];
+        m1 += g * hz[0][r + k][c]; m2 += g * hz[1][r + k][c]; xx += g * hz[2][r + k][c];
+        yy += g * hz[3][r + k][c]; xy += g * hz[4][r + k][c];
+      }
+      acc += sqrt(fmax(ssim_s_double(m1, m2, xx, yy, xy), 0.0));
+    }
+  }
+  // fixed-shape tree over the 256 threads (sx is free again: every thread is past its last read of it)
+  __syncthreads();
+  double* tree = &sx[0][0];
+  tree[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) tree[threadIdx.x] += tree[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) partial[blockIdx.x] = tree[0];
+}
+__global__ void ssim_window_final_kernel(const double* partial, int n, double scale, float* out) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
+}
+
+static int ssim_forward(const float* x, int xpl, long long xstride, const float* y, int32_t NC, int32_t H, int32_t W,
+                        float* out, float* scratch, void* stream) {
   if (int rc = ssim_init_gauss()) return rc;
   const int th = (H - 10 + SSIM_TH - 1) / SSIM_TH, tw = (W - 10 + SSIM_TW - 1) / SSIM_TW;
   const int blocks = NC * th * tw;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(ssim_kernel, dim3(blocks), dim3(256), 0, st, x, y, H, W, tw, th, scratch);
+  hipLaunchKernelGGL(ssim_kernel, dim3(blocks), dim3(256), 0, st, x, xpl, xstride, y, H, W, tw, th, scratch);
   const double cnt = (double)NC * (H - 10) * (W - 10);
   hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, st, scratch, blocks, (float)(1.0 / cnt), out);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int gs_ssim_distance(const float* x, const float* y, int32_t NC, int32_t H, int32_t W, float* out,
+                                float* scratch, void* stream) {
+  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance: bad argument");
+  return ssim_forward(x, NC, 0, y, NC, H, W, out, scratch, stream);
+}
+extern "C" int gs_ssim_distance_window(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y, int32_t NC,
+                                       int32_t H, int32_t W, float* out, float* scratch, void* stream) {
+  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance_window: bad argument");
+  GS_REQUIRE(x_planes > 0 && NC % x_planes == 0 && x_sample_stride >= (int64_t)x_planes * H * W,
+             "gs_ssim_distance_window: NC must be samples * x_planes and the sample stride >= x_planes * H * W");
+  GS_REQUIRE(((uintptr_t)scratch & 7) == 0, "gs_ssim_distance_window: scratch must be 8-byte aligned (one double per tile)");
+  if (int rc = ssim_init_gauss()) return rc;
+  const int th = (H - 10 + SSIM_TH - 1) / SSIM_TH, tw = (W - 10 + SSIM_TW - 1) / SSIM_TW;
+  const int blocks = NC * th * tw;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* part = reinterpret_cast<double*>(scratch);
+  hipLaunchKernelGGL(ssim_window_kernel, dim3(blocks), dim3(256), 0, st, x, x_planes, (long long)x_sample_stride, y, H, W, tw, th,
+                     part);
+  hipLaunchKernelGGL(ssim_window_final_kernel, dim3(1), dim3(256), 0, st, part, blocks,
+                     1.0 / ((double)NC * (H - 10) * (W - 10)), out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -341,8 +488,8 @@ extern "C" int gs_ssim_distance(const float* x, const float* y, int32_t NC, int3
 //   dS1/dmu2 = (2 mu1 B1 - 2 mu2 A1) / B1^2,  dS2/ds12 = 2 / B2,  dS2/ds2 = -A2 / B2^2   (S1 = A1/B1, S2 = A2/B2)
 // and dL/dY(p) = 1/2 * ( bT(G0)(p) + X(p) bT(G1)(p) + 2 Y(p) bT(G2)(p) ) with bT the transposed (full) Gaussian; the 1/2 is
 // the (y + 1)/2 input mapping (nn/losses/utils/ssim.py:65-99 differentiated; cyclegan_losses.py:78-90 uses it as a loss).
-__global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, const float* y, int H, int W, int tiles_w,
-                                                             int tiles_h, const float* grad_scale, float inv_cnt,
+__global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, int xpl, long long xstride, const float* y, int H,
+                                                             int W, int tiles_w, int tiles_h, const float* grad_scale, float inv_cnt,
                                                              float* maps, size_t map_stride) {
   __shared__ float sx[SSIM_TH + 10][SSIM_TW + 10];
   __shared__ float sy[SSIM_TH + 10][SSIM_TW + 10];
@@ -352,7 +499,7 @@ __global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, con
   const int th = b % tiles_h; const int plane = b / tiles_h;
   const int Ho = H - 10, Wo = W - 10;
   const int oh0 = th * SSIM_TH, ow0 = tw * SSIM_TW;
-  const float* xp = x + (size_t)plane * H * W;
+  const float* xp = x + (size_t)(plane / xpl) * xstride + (size_t)(plane % xpl) * H * W;
   const float* yp = y + (size_t)plane * H * W;
   for (int e = threadIdx.x; e < (SSIM_TH + 10) * (SSIM_TW + 10); e += 256) {
     const int r = e / (SSIM_TW + 10), c = e % (SSIM_TW + 10);
@@ -404,9 +551,9 @@ __global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, con
 }
 
 // transposed separable Gaussian of the three maps + combination with X, Y: one workgroup = 16x32 input pixels
-__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* x, const float* y, const float* maps,
-                                                       size_t map_stride, int H, int W, int tiles_w, int tiles_h,
-                                                       float* grad_y) {
+__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* x, int xpl, long long xstride, const float* y,
+                                                       const float* maps, size_t map_stride, int H, int W, int tiles_w,
+                                                       int tiles_h, float* grad_y) {
   __shared__ float sm[3][SSIM_TH + 10][SSIM_TW + 10];
   __shared__ float hz[3][SSIM_TH + 10][SSIM_TW];
   int b = blockIdx.x;
@@ -437,7 +584,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* x, const flo
     hz[0][r][c] = a0; hz[1][r][c] = a1; hz[2][r][c] = a2;
   }
   __syncthreads();
-  const float* xp = x + (size_t)plane * H * W;
+  const float* xp = x + (size_t)(plane / xpl) * xstride + (size_t)(plane % xpl) * H * W;
   const float* yp = y + (size_t)plane * H * W;
   float* gp = grad_y + (size_t)plane * H * W;
   for (int e = threadIdx.x; e < SSIM_TH * SSIM_TW; e += 256) {
@@ -461,21 +608,33 @@ extern "C" int64_t gs_ssim_backward_scratch_floats(int32_t NC, int32_t H, int32_
   return 3 * (int64_t)NC * (H - 10) * (W - 10);
 }
 
-extern "C" int gs_ssim_distance_backward(const float* x, const float* y, int32_t NC, int32_t H, int32_t W,
-                                         const float* grad_scale, float* grad_y, float* scratch, void* stream) {
-  GS_REQUIRE(x && y && grad_y && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance_backward: bad argument");
+static int ssim_backward(const float* x, int xpl, long long xstride, const float* y, int32_t NC, int32_t H, int32_t W,
+                         const float* grad_scale, float* grad_y, float* scratch, void* stream) {
   if (int rc = ssim_init_gauss()) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int Ho = H - 10, Wo = W - 10;
   const size_t map_stride = (size_t)NC * Ho * Wo;
   const int th = (Ho + SSIM_TH - 1) / SSIM_TH, tw = (Wo + SSIM_TW - 1) / SSIM_TW;
-  hipLaunchKernelGGL(ssim_grad_maps_kernel, dim3(NC * th * tw), dim3(256), 0, st, x, y, H, W, tw, th, grad_scale,
+  hipLaunchKernelGGL(ssim_grad_maps_kernel, dim3(NC * th * tw), dim3(256), 0, st, x, xpl, xstride, y, H, W, tw, th, grad_scale,
                      (float)(1.0 / ((double)NC * Ho * Wo)), scratch, map_stride);
   const int th2 = (H + SSIM_TH - 1) / SSIM_TH, tw2 = (W + SSIM_TW - 1) / SSIM_TW;
-  hipLaunchKernelGGL(ssim_bwd_kernel, dim3(NC * th2 * tw2), dim3(256), 0, st, x, y, scratch, map_stride, H, W, tw2, th2,
-                     grad_y);
+  hipLaunchKernelGGL(ssim_bwd_kernel, dim3(NC * th2 * tw2), dim3(256), 0, st, x, xpl, xstride, y, scratch, map_stride, H, W, tw2,
+                     th2, grad_y);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
+}
+extern "C" int gs_ssim_distance_backward(const float* x, const float* y, int32_t NC, int32_t H, int32_t W,
+                                         const float* grad_scale, float* grad_y, float* scratch, void* stream) {
+  GS_REQUIRE(x && y && grad_y && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance_backward: bad argument");
+  return ssim_backward(x, NC, 0, y, NC, H, W, grad_scale, grad_y, scratch, stream);
+}
+extern "C" int gs_ssim_distance_window_backward(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y,
+                                                int32_t NC, int32_t H, int32_t W, const float* grad_scale, float* grad_y,
+                                                float* scratch, void* stream) {
+  GS_REQUIRE(x && y && grad_y && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance_window_backward: bad argument");
+  GS_REQUIRE(x_planes > 0 && NC % x_planes == 0 && x_sample_stride >= (int64_t)x_planes * H * W,
+             "gs_ssim_distance_window_backward: NC must be samples * x_planes and the sample stride >= x_planes * H * W");
+  return ssim_backward(x, x_planes, x_sample_stride, y, NC, H, W, grad_scale, grad_y, scratch, stream);
 }
 
 // ---- scalar algebra of a recipe's loss assembly ----------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ VM_FLAGS = {"ssim": 1, "hist": 2}     # GS_VM_SSIM, GS_VM_HIST
 VM_BINS = 100
 VM_MAX_LABELS = 8                       # GS_VM_MAX_LABELS
 VIS_MAX_SRCS = 16                       # GS_VIS_MAX_SRCS
+CAT_MAX_SRCS = 4                        # GS_CAT_MAX_SRCS
 
 
 class GConvDesc(C.Structure):
@@ -171,6 +172,11 @@ _PROTOS = {
                                        C.c_int32, C.c_int32, C.c_void_p]),
     "gs_image_pair_to_act_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "gs_image_cat_to_act": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                      C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
+    "gs_image_cat_to_act_backward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                               C.c_int64, C.c_int32, C.c_void_p]),
+    "gs_channel_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "gs_act_to_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_void_p]),
     "gs_act_to_image_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -205,6 +211,8 @@ _PROTOS = {
     "gs_adv_loss": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]),
     "gs_l1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_l1_window": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
     "gs_mean": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gs_scalar_affine": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32,
                                    C.c_void_p, C.c_void_p]),
@@ -234,6 +242,10 @@ _PROTOS = {
     "gs_ssim_distance_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_ssim_backward_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gs_ssim_distance_window": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_ssim_distance_window_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_mind_descriptor": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_float, C.c_void_p, C.c_void_p]),
     "gs_mind_l1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

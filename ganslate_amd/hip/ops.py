@@ -739,6 +739,140 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_image_pair_to_act_backward(_ptr(g), _ptr(ga), Ca, _ptr(gb), Cb, N, H, W, g.shape[-1], _stream()),
                 "gs_image_pair_to_act_backward")
 
+    # ---- channel windows (the balanced CycleGAN: csrc/image.hip, csrc/loss.hip) ------------------------------------------
+    @staticmethod
+    def _dense_f32(t, what):
+        """ValueError before any launch: a dense fp32 [N, C, *spatial] tensor"""
+        if not torch.is_tensor(t) or t.dim() not in (4, 5):
+            raise ValueError(f"{what}: an [N, C, H, W] or [N, C, D, H, W] tensor expected, got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: fp32 expected, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: a dense (contiguous) tensor expected, got strides {t.stride()} for shape {tuple(t.shape)}")
+        if t.numel() == 0:
+            raise ValueError(f"{what}: empty tensor {tuple(t.shape)}")
+
+    @classmethod
+    def _window(cls, t, c0, c1, what):
+        """(pointer to channel c0 of sample 0, sample stride in floats, channels, S) of the window [c0, c1) of dense `t`"""
+        cls._dense_f32(t, what)
+        c0, c1 = int(c0), int(c1)
+        if not 0 <= c0 < c1 <= t.shape[1]:
+            raise ValueError(f"{what}: the channel window [{c0}, {c1}) does not lie inside the {t.shape[1]} channels")
+        S = t.numel() // (t.shape[0] * t.shape[1])
+        return C.c_void_p(t.data_ptr() + c0 * S * 4), t.shape[1] * S, c1 - c0, S
+
+    @staticmethod
+    def _same_extent(a, b, what):
+        if a.shape[0] != b.shape[0] or tuple(a.shape[2:]) != tuple(b.shape[2:]) or a.device != b.device:
+            raise ValueError(f"{what}: the tensors differ in batch, spatial extent or device: {tuple(a.shape)} vs "
+                             f"{tuple(b.shape)}")
+
+    def image_cat_to_act(self, srcs, act_t):
+        """srcs = [(dense fp32 tensor, c0, c1)] (1..4): torch.cat([t[:, c0:c1] for ...], dim=1) -> channels-last act_t in one pass,
+        neither the slices nor the concatenation exist in memory (gs_image_cat_to_act)"""
+        K = len(srcs)
+        if not 1 <= K <= L.CAT_MAX_SRCS:
+            raise ValueError(f"image_cat_to_act: 1..{L.CAT_MAX_SRCS} channel sources, got {K}")
+        win = [self._window(t, c0, c1, f"image_cat_to_act: source {k}") for k, (t, c0, c1) in enumerate(srcs)]
+        for t, _, _ in srcs[1:]:
+            self._same_extent(srcs[0][0], t, "image_cat_to_act")
+        t0 = srcs[0][0]
+        if not act_t.is_contiguous() or act_t.dtype != self.act_dtype:
+            raise ValueError("image_cat_to_act: the activation must be a dense channels-last buffer of the activation dtype")
+        if act_t.shape[0] != t0.shape[0] or tuple(act_t.shape[1:-1]) != tuple(t0.shape[2:]):
+            raise ValueError(f"image_cat_to_act: activation {tuple(act_t.shape)} does not match the sources {tuple(t0.shape)}")
+        if sum(w[2] for w in win) > act_t.shape[-1] or act_t.shape[-1] % 8:
+            raise ValueError(f"image_cat_to_act: {sum(w[2] for w in win)} source channels do not fit the activation's "
+                             f"{act_t.shape[-1]} (a multiple of 8)")
+        ptrs = (C.c_void_p * K)(*[w[0] for w in win])
+        strides = (C.c_int64 * K)(*[w[1] for w in win])
+        chans = (C.c_int32 * K)(*[w[2] for w in win])
+        L.check(self.lib.gs_image_cat_to_act(ptrs, strides, chans, K, _ptr(act_t), t0.shape[0], win[0][3], act_t.shape[-1],
+                                             _stream()), "gs_image_cat_to_act")
+
+    def image_cat_to_act_backward(self, g, grads, channels):
+        """gradient of image_cat_to_act: grads[k] = dense fp32 [N, channels[k], *spatial] or None (left alone)"""
+        K = len(channels)
+        if len(grads) != K or not 1 <= K <= L.CAT_MAX_SRCS:
+            raise ValueError(f"image_cat_to_act_backward: one gradient slot per source (1..{L.CAT_MAX_SRCS}), got {len(grads)} "
+                             f"for {K} sources")
+        ref = next((t for t in grads if t is not None), None)
+        if ref is None:
+            raise ValueError("image_cat_to_act_backward: no source asks for a gradient")
+        for k, t in enumerate(grads):
+            if t is None:
+                continue
+            self._dense_f32(t, f"image_cat_to_act_backward: gradient {k}")
+            self._same_extent(ref, t, "image_cat_to_act_backward")
+            if t.shape[1] != channels[k]:
+                raise ValueError(f"image_cat_to_act_backward: gradient {k} has {t.shape[1]} channels, its source {channels[k]}")
+        if not g.is_contiguous() or g.shape[0] != ref.shape[0] or tuple(g.shape[1:-1]) != tuple(ref.shape[2:]) or \
+                sum(channels) > g.shape[-1]:
+            raise ValueError(f"image_cat_to_act_backward: activation gradient {tuple(g.shape)} does not match "
+                             f"{tuple(ref.shape)} / {sum(channels)} channels")
+        ptrs = (C.c_void_p * K)(*[(t.data_ptr() if t is not None else None) for t in grads])
+        chans = (C.c_int32 * K)(*[int(c) for c in channels])
+        S = ref.numel() // (ref.shape[0] * ref.shape[1])
+        L.check(self.lib.gs_image_cat_to_act_backward(_ptr(g), ptrs, chans, K, ref.shape[0], S, g.shape[-1], _stream()),
+                "gs_image_cat_to_act_backward")
+
+    def channel_embed(self, src, dst, c0):
+        """dst [N, C, *spatial] = zeros with src [N, t, *spatial] at channels [c0, c0 + t), one pass (gs_channel_embed)"""
+        self._dense_f32(src, "channel_embed: src")
+        self._dense_f32(dst, "channel_embed: dst")
+        self._same_extent(src, dst, "channel_embed")
+        c0, t, Cd = int(c0), src.shape[1], dst.shape[1]
+        if not 0 <= c0 <= c0 + t <= Cd:
+            raise ValueError(f"channel_embed: the channel window [{c0}, {c0 + t}) does not lie inside the {Cd} channels")
+        if dst.shape[0] * Cd > 65535:
+            raise ValueError(f"channel_embed: N * C = {dst.shape[0] * Cd} exceeds 65535")
+        S = dst.numel() // (dst.shape[0] * Cd)
+        L.check(self.lib.gs_channel_embed(_ptr(src), _ptr(dst), dst.shape[0], Cd, c0, t, S, _stream()), "gs_channel_embed")
+
+    def l1_window(self, a, c0, c1, b, loss=None, grad_b=None, grad_scale=None):
+        """gs_l1 of a[:, c0:c1] (a window of a dense tensor, never materialised) and dense b; grad_b = d/db, dense like b"""
+        pa, stride, ch, S = self._window(a, c0, c1, "l1_window: a")
+        self._dense_f32(b, "l1_window: b")
+        self._same_extent(a, b, "l1_window")
+        if b.shape[1] != ch:
+            raise ValueError(f"l1_window: b has {b.shape[1]} channels, the window [{c0}, {c1}) {ch}")
+        if grad_b is not None:
+            self._dense_f32(grad_b, "l1_window: grad_b")
+            if grad_b.shape != b.shape:
+                raise ValueError(f"l1_window: grad_b {tuple(grad_b.shape)} must have b's shape {tuple(b.shape)}")
+        L.check(self.lib.gs_l1_window(pa, stride, _ptr(b), a.shape[0], ch * S, _ptr(loss), _ptr(grad_b), _ptr(grad_scale),
+                                      _stream()), "gs_l1_window")
+
+    def _ssim_window_args(self, x, c0, c1, y, what):
+        px, stride, ch, S = self._window(x, c0, c1, f"{what}: x")
+        self._dense_f32(y, f"{what}: y")
+        self._same_extent(x, y, what)
+        if y.shape[1] != ch:
+            raise ValueError(f"{what}: y has {y.shape[1]} channels, the window [{c0}, {c1}) {ch}")
+        H, W = y.shape[-2], y.shape[-1]
+        if H <= 10 or W <= 10:
+            raise ValueError(f"{what}: planes of more than 10 x 10 pixels needed (11-tap window), got {H} x {W}")
+        return px, stride, ch * S // (H * W), y.numel() // (H * W), H, W
+
+    def ssim_distance_window(self, x, c0, c1, y, out):
+        """gs_ssim_distance of x[:, c0:c1] (a window, never materialised) and dense y; evaluated in double, rounded once"""
+        px, stride, planes, NC, H, W = self._ssim_window_args(x, c0, c1, y, "ssim_distance_window")
+        scratch = torch.empty(self.lib.gs_ssim_scratch_floats(NC, H, W), dtype=torch.float64, device=y.device)   # one per tile
+        L.check(self.lib.gs_ssim_distance_window(px, stride, planes, _ptr(y), NC, H, W, _ptr(out), _ptr(scratch), _stream()),
+                "gs_ssim_distance_window")
+
+    def ssim_distance_window_backward(self, x, c0, c1, y, grad_y, grad_scale=None):
+        """gradient of ssim_distance_window w.r.t. the dense image y"""
+        px, stride, planes, NC, H, W = self._ssim_window_args(x, c0, c1, y, "ssim_distance_window_backward")
+        self._dense_f32(grad_y, "ssim_distance_window_backward: grad_y")
+        if grad_y.shape != y.shape:
+            raise ValueError(f"ssim_distance_window_backward: grad_y {tuple(grad_y.shape)} must have y's shape {tuple(y.shape)}")
+        scratch = torch.empty(self.lib.gs_ssim_backward_scratch_floats(NC, H, W), dtype=torch.float32, device=y.device)
+        L.check(self.lib.gs_ssim_distance_window_backward(px, stride, planes, _ptr(y), NC, H, W, _ptr(grad_scale), _ptr(grad_y),
+                                                          _ptr(scratch), _stream()), "gs_ssim_distance_window_backward")
+
     def act_to_image(self, act_t, img, act="none"):
         N, Cc, H, W = self._img_dims(img)
         L.check(self.lib.gs_act_to_image(_ptr(act_t), _ptr(img), N, Cc, H, W, act_t.shape[-1], L.ACT[act],

@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import torch
 
 from .... import configs
-from ...native.net import NativeNet, Node
+from ...native.net import ChannelSources, NativeNet, Node
 from ...native.spec import ConvSpec, lower
 from ...utils import is_bias_before_norm, require_instance_norm
 
@@ -76,6 +76,9 @@ class Unet2D(NativeNet):
             words = words.pin_memory()
         self._seed_dev.copy_(words, non_blocking=True)
 
+    def supports_channel_sources(self):
+        return True          # the image enters through gs_image_to_act (see _forward)
+
     def _down(self, k):
         return k - 1
 
@@ -134,7 +137,10 @@ class Unet2D(NativeNet):
                 self.prepare_host_state()
             s.seed_dev = self._seed_dev
         a0 = self._new(N, sizes, self.nodes[0].spec.cin_p)
-        ops.image_to_act(x, a0)
+        if isinstance(x, ChannelSources):      # channel windows side by side (NativeNet.forward_sources): no cat, no slice
+            ops.image_cat_to_act(list(x), a0)
+        else:
+            ops.image_to_act(x, a0)
         s.L = {0: a0}          # L[k]: LeakyReLU(h_k), the input of down_{k+1}
         s.cat, s.yd, s.mrd, s.yu, s.mru = {}, {}, {}, {}, {}
         for k in range(1, D + 1):
@@ -255,6 +261,8 @@ class Unet2D(NativeNet):
                 self._early_step_at(i)
         if not need_input_grad:
             return None
+        if isinstance(s.x_img, ChannelSources):
+            return s.x_img.write_grads(ops, gL, getattr(self, "_cat_need", None) or (True,) * len(s.x_img))
         g_in = torch.empty_like(s.x_img)
         ops.image_to_act_backward(gL, g_in, fold=0)
         return g_in

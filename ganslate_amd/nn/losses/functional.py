@@ -1,6 +1,6 @@
 """Autograd entry points of the fused loss kernels (libganslate_hip: gs_l1, gs_mse_const, gs_adv_loss, gs_mean,
-gs_ssim_distance, gs_mind_l1). Each forward is one wavefront-reduced kernel writing a 0-d fp32 tensor; each backward is one
-elementwise kernel that folds the upstream scalar gradient in (passed as a device pointer — no host sync)."""
+gs_ssim_distance, gs_mind_l1, and the channel-window forms gs_l1_window / gs_ssim_distance_window). Each forward is one
+wavefront-reduced kernel writing a 0-d fp32 tensor; each backward is one elementwise kernel that folds the upstream scalar gradient in (passed as a device pointer — no host sync)."""
 import torch
 
 from ..native.backend import get_ops
@@ -118,6 +118,71 @@ class _SSIMDistance(torch.autograd.Function):
 def ssim_distance_autograd(X, Y):
     """Differentiable SSIM distance for `proportion_ssim > 0` (cyclegan_losses.py:78-90; SSIMLoss on (x+1)/2)."""
     return _SSIMDistance.apply(X.float(), Y.float())
+
+
+class _L1Window(torch.autograd.Function):
+    """mean(|real[:, c0:c1] - x|): `real` a dense image that takes no gradient, read through its channel window (gs_l1_window:
+    no slice is materialised), `x` dense with the window's channels; the gradient goes to x."""
+
+    @staticmethod
+    def forward(ctx, real, c0, c1, x):
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        get_ops().l1_window(real, c0, c1, x, loss=loss)
+        ctx.save_for_backward(real, x)
+        ctx.win = (c0, c1)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        real, x = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        get_ops().l1_window(real, *ctx.win, x, grad_b=gx, grad_scale=g.contiguous().float())
+        return None, None, None, gx
+
+
+class _SSIMWindow(torch.autograd.Function):
+    """SSIM distance of real[:, c0:c1] (constant side, a channel window read in place) and dense x (gs_ssim_distance_window
+    and its backward); the gradient goes to x."""
+
+    @staticmethod
+    def forward(ctx, real, c0, c1, x):
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        get_ops().ssim_distance_window(real, c0, c1, x, out)
+        ctx.save_for_backward(real, x)
+        ctx.win = (c0, c1)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        real, x = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        get_ops().ssim_distance_window_backward(real, *ctx.win, x, gx, grad_scale=g.contiguous().float())
+        return None, None, None, gx
+
+
+def _window_operands(real, window, x):
+    c0, c1 = int(window[0]), int(window[1])
+    if real.requires_grad:
+        raise ValueError("the windowed operand is a real image: it takes no gradient")
+    return real.detach().contiguous().float(), c0, c1, x.contiguous().float()
+
+
+def l1_window_loss(real, window, x):
+    """nn.L1Loss(x, real[:, c0:c1]) without the slice (the balanced CycleGAN's cycle loss on the translated channels)"""
+    return _L1Window.apply(*_window_operands(real, window, x))
+
+
+def ssim_distance_window_autograd(real, window, x):
+    """ssim_distance_autograd(x, real[:, c0:c1]) without the slice"""
+    return _SSIMWindow.apply(*_window_operands(real, window, x))
+
+
+def channel_embed(x, channels, c0):
+    """zeros [N, channels, *spatial] with x at channels [c0, c0 + x.shape[1]) (gs_channel_embed, one pass; no gradient)"""
+    x = x.detach().contiguous().float()
+    out = torch.empty((x.shape[0], int(channels)) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    get_ops().channel_embed(x, out, int(c0))
+    return out
 
 
 class _MINDL1(torch.autograd.Function):

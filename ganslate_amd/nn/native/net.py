@@ -571,6 +571,48 @@ class NativeNet:
             return _split_parts(out, pairs_shape(pairs))
         return _CatPartsFn.apply(self._token, self, *flat)
 
+    def supports_channel_sources(self):
+        """True when images enter this network through the plain image conversion (gs_image_to_act), which the channel-source
+        conversion replaces; False for a W-folded stem (Resnet2D's k7 stem) and for executors with their own boundary code"""
+        return type(self)._forward is NativeNet._forward and self.nodes[0].spec.wfold != "in"
+
+    def forward_sources(self, parts):
+        """forward_parts for batches that are each a torch.cat of channel windows, parts = [[(tensor, c0, c1), ...], ...]: batch
+        p is torch.cat([t[:, c0:c1] for (t, c0, c1) in parts[p]], dim=1) (the balanced CycleGAN's splice of generated and
+        real guide channels; a discriminator's real input real_B[:, tB]) converted straight into the first activation — neither
+        a slice nor a concatenation exists in memory -> one output per batch. Only a source that is a whole tensor
+        (c0 = 0, c1 = C) can take a gradient; it comes back dense, through gs_image_cat_to_act_backward."""
+        if not self.supports_channel_sources():
+            raise NotImplementedError(f"{type(self).__name__}: images do not enter through the plain image conversion; "
+                                      "channel sources are not supported")
+        parts = [[(t, int(c0), int(c1)) for t, c0, c1 in part] for part in parts]
+        if not parts or any(not part for part in parts):
+            raise ValueError("forward_sources: every batch needs at least one channel source")
+        if len(parts) > 1 and type(self)._forward is not NativeNet._forward:
+            raise NotImplementedError(f"{type(self).__name__} takes one batch per pass")
+        flat, layout = [], []
+        for part in parts:
+            for t, c0, c1 in part:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError("forward_sources: dense fp32 tensors expected (a window is given by its channel range, "
+                                     f"not by a slice); got {t.dtype}, strides {t.stride()}")
+                if not 0 <= c0 < c1 <= t.shape[1]:
+                    raise ValueError(f"forward_sources: the channel window [{c0}, {c1}) does not lie inside {t.shape[1]} channels")
+                if t.requires_grad and torch.is_grad_enabled() and (c0, c1) != (0, t.shape[1]):
+                    raise ValueError("forward_sources: only a whole tensor can take a gradient, not a channel window")
+            if sum(c1 - c0 for _, c0, c1 in part) != self.in_channels:
+                raise ValueError(f"forward_sources: the sources hold {sum(c1 - c0 for _, c0, c1 in part)} channels, "
+                                 f"{type(self).__name__} takes {self.in_channels}")
+            flat += [t for t, _, _ in part]
+            layout.append(tuple((c0, c1) for _, c0, c1 in part))
+        layout = tuple(layout)
+        record = torch.is_grad_enabled() and (self.requires_grad or any(t.requires_grad for t in flat))
+        if not record:
+            xs = _sources(layout, [t.detach() for t in flat])
+            out, _ = self._forward(xs if type(self)._forward is NativeNet._forward else xs[0], save=False)
+            return _split_parts(out, xs)
+        return _SourcesFn.apply(self._token, self, layout, *flat)
+
     def forward_taps(self, x, taps, ids):
         """sampled features of intermediate nodes: taps = [("x"|"y", node)], ids = [LongTensor[P]] (pixel indices);
         returns a tuple of [N, P, C] fp32 tensors that autograd can differentiate into the network"""
@@ -615,7 +657,10 @@ class NativeNet:
         for xh in xs:
             ah = a[n0:n0 + xh.shape[0]]
             n0 += xh.shape[0]
-            if isinstance(xh, ChannelCat):
+            if isinstance(xh, ChannelSources):
+                assert sp0.wfold != "in", "channel sources enter through the plain image conversion"
+                ops.image_cat_to_act(list(xh), ah)
+            elif isinstance(xh, ChannelCat):
                 assert sp0.wfold != "in", "channel pairs enter through the plain image conversion"
                 ops.image_pair_to_act(xh[0], xh[1], ah)
             elif sp0.wfold == "in":      # the W taps of the stem become channels while the image is converted
@@ -864,6 +909,12 @@ class NativeNet:
         for xh in x_imgs:
             gxh = gx[n0:n0 + xh.shape[0]]
             n0 += xh.shape[0]
+            if isinstance(xh, ChannelSources):           # (fold is 0 here too)
+                assert f == 0
+                want = need[k:k + len(xh)] if need is not None else (True,) * len(xh)
+                k += len(xh)
+                g_ins.append(xh.write_grads(ops, gxh, want))
+                continue
             if isinstance(xh, ChannelCat):               # (fold is 0 here: the pair form has no padded stem)
                 assert f == 0
                 want = need[k:k + 2] if need is not None else (True, True)
@@ -1063,6 +1114,71 @@ class ChannelCat(tuple):
     def shape(self):
         a, b = self
         return torch.Size((a.shape[0], a.shape[1] + b.shape[1]) + tuple(a.shape[2:]))
+
+
+class ChannelSources(tuple):
+    """((tensor, c0, c1), ...): channel windows of dense image batches that enter a network side by side along the channel
+    axis — torch.cat([t[:, c0:c1] for ...], dim=1) without a launch of torch's (NativeNet.forward_sources); looks like the
+    concatenated tensor where the executor asks for a shape"""
+
+    @property
+    def shape(self):
+        t = self[0][0]
+        return torch.Size((t.shape[0], sum(c1 - c0 for _, c0, c1 in self)) + tuple(t.shape[2:]))
+
+    def write_grads(self, ops, g_act, want):
+        """the input gradients of the sources that want one (whole tensors only), dense, one launch -> tuple, None elsewhere"""
+        grads = tuple(torch.empty_like(t) if w else None for (t, _, _), w in zip(self, want))
+        if any(g is not None for g in grads):
+            ops.image_cat_to_act_backward(g_act, list(grads), [c1 - c0 for _, c0, c1 in self])
+        return grads
+
+
+def _sources(layout, tensors):
+    out, k = [], 0
+    for part in layout:
+        out.append(ChannelSources(tuple((tensors[k + j], c0, c1) for j, (c0, c1) in enumerate(part))))
+        k += len(part)
+    return tuple(out)
+
+
+class _SourcesFn(torch.autograd.Function):
+    """forward_parts over batches given as channel sources: the tensors come flattened, `layout` holds their windows"""
+
+    @staticmethod
+    def forward(ctx, token, net, layout, *ts):
+        xs = _sources(layout, [t.detach() for t in ts])
+        ctx.parts = type(net)._forward is NativeNet._forward        # (an executor of its own takes the one batch itself)
+        out, saved = net._forward(xs if ctx.parts else xs[0], save=True)
+        ctx.net, ctx.saved = net, saved
+        ctx.need = tuple(ctx.needs_input_grad[3:])
+        ctx.want_w = net.requires_grad
+        if ctx.want_w:
+            net._fw_pending += 1
+        ctx.set_materialize_grads(False)
+        return _split_parts(out, xs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        net = ctx.net
+        if ctx.want_w:
+            net._fw_pending -= 1
+            net._order_backward_begin()
+        for g in grads:
+            if g is not None and g.is_cuda:
+                g.record_stream(torch.cuda.current_stream())
+        net._cat_need = ctx.need                       # which sources want a gradient (the executor's _backward reads it)
+        try:
+            gx = net._backward(ctx.saved, grads if ctx.parts else grads[0], any(ctx.need), ctx.want_w)
+        finally:
+            net._cat_need = None
+        if ctx.want_w:
+            net._order_backward_end()
+        ctx.saved = None
+        if gx is None:
+            return (None,) * (3 + len(ctx.need))
+        flat = [t for part in (gx if ctx.parts else (gx,)) for t in part]
+        return (None, None, None) + tuple(g if need else None for g, need in zip(flat, ctx.need))
 
 
 class _CatPartsFn(torch.autograd.Function):

@@ -379,6 +379,21 @@ int gs_image_pair_to_act(const float* a, int32_t Ca, const float* b, int32_t Cb,
                          int32_t Cp, void* stream);
 int gs_image_pair_to_act_backward(const void* g, float* ga, int32_t Ca, float* gb, int32_t Cb, int32_t N, int32_t H, int32_t W,
                                   int32_t Cp, void* stream);
+/* Channel sources: K (1..GS_CAT_MAX_SRCS) image tensors side by side along the channel axis -> act in one pass. Source k is a
+ * channel window of a dense fp32 [N][C_k][S] tensor (S = D*H*W): src[k] points at the window's first element (c0 * S floats
+ * into the tensor), sample_stride[k] = C_k * S floats lead from one sample to the next, channels[k] is the window's width.
+ * src, sample_stride and channels are HOST arrays of K that reach the kernel by value; no source needs any alignment. Rounding
+ * and the zeroed pad lanes are gs_image_to_act's. One windowed source is a discriminator's real input real_B[:, tB], two are
+ * the splice torch.cat([fake_Bt, real_A[:, guide]], dim=1) of the balanced CycleGAN. */
+#define GS_CAT_MAX_SRCS 4
+int gs_image_cat_to_act(const float* const* src, const int64_t* sample_stride, const int32_t* channels, int32_t K, void* act,
+                        int32_t N, int64_t S, int32_t Cp, void* stream);
+/* its gradient: for every source with grad[k] != NULL its channels of g as a dense fp32 [N][channels[k]][S] tensor; a NULL
+ * grad[k] is skipped (nothing of it is written), at least one must be given */
+int gs_image_cat_to_act_backward(const void* g, float* const* grad, const int32_t* channels, int32_t K, int32_t N, int64_t S,
+                                 int32_t Cp, void* stream);
+/* dst [N][C][S] = zeros with src [N][t][S] at channels [c0, c0 + t); every element of dst is written once. N * C <= 65535 */
+int gs_channel_embed(const float* src, float* dst, int32_t N, int32_t C, int32_t c0, int32_t t, int64_t S, void* stream);
 /* act -> NCHW fp32, optional tanh (resnet2d.py:65) */
 int gs_act_to_image(const void* act, float* img, int32_t N, int32_t C, int32_t H, int32_t W, int32_t Cp,
                     int32_t act_kind, void* stream);
@@ -500,6 +515,11 @@ int gs_adv_loss(const float* x, int64_t n, int32_t rows, int32_t mode, int32_t t
  * (nn.L1Loss, cyclegan_losses.py:64,75,97-101) */
 int gs_l1(const float* a, const float* b, int64_t n, float* loss, float* grad_a, const float* grad_scale,
           void* stream);
+/* gs_l1 with a channel window as the first operand: sample n of `a` is the `per` contiguous floats at a + n * a_sample_stride,
+ * `b` is dense [N][per]. loss[0] = mean(|a-b|) over the N * per elements, summed in gs_l1's order; if grad_b != NULL:
+ * grad_b = grad_scale * sign(b-a) / (N * per), dense like b (grad_scale: device scalar, NULL = 1). `a` needs no alignment. */
+int gs_l1_window(const float* a, int64_t a_sample_stride, const float* b, int32_t N, int64_t per, float* loss, float* grad_b,
+                 const float* grad_scale, void* stream);
 /* out[0] = mean(x)  (train_metrics.py:27-33) */
 int gs_mean(const float* x, int64_t n, float* out, void* stream);
 /* out[r] = c[r] + sum_k m[r*K + k] * x[k][0], r < R <= 8, k < K <= 16: the scalar algebra of a recipe's loss assembly
@@ -521,6 +541,18 @@ int64_t gs_ssim_scratch_floats(int32_t NC, int32_t H, int32_t W);
 int gs_ssim_distance_backward(const float* x, const float* y, int32_t NC, int32_t H, int32_t W,
                               const float* grad_scale, float* grad_y, float* scratch, void* stream);
 int64_t gs_ssim_backward_scratch_floats(int32_t NC, int32_t H, int32_t W);
+/* The same two with a channel window as the constant image x: plane p (0 <= p < x_planes) of sample n sits at
+ * x + n * x_sample_stride + p * H * W; NC = samples * x_planes planes in all, y (and grad_y) dense [NC][H][W]. The gradient
+ * is the dense entry point's (same kernels, scratch size, arithmetic and summation order: the dense form is the
+ * x_sample_stride = x_planes * H * W case). The forward evaluates the same formula with the same fp32 Gaussian weights in double
+ * and rounds the mean once — the windows of this recipe are often single small planes, where a handful of valid pixels does not
+ * average the fp32 error of the variance terms out; its scratch is one DOUBLE per tile: 2 * gs_ssim_scratch_floats(NC, H, W)
+ * floats, 8-byte aligned. */
+int gs_ssim_distance_window(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y, int32_t NC, int32_t H,
+                            int32_t W, float* out, float* scratch, void* stream);
+int gs_ssim_distance_window_backward(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y, int32_t NC,
+                                     int32_t H, int32_t W, const float* grad_scale, float* grad_y, float* scratch,
+                                     void* stream);
 
 /* ---- MIND structure-consistency loss (mind.hip) ----
  * The reference's MINDDescriptor / StructureLoss of
