@@ -51,23 +51,37 @@ __device__ __forceinline__ void finish_reduction(float partial, float* ws, float
   }
 }
 
-__global__ __launch_bounds__(256) void mse_const_kernel(const float* x, long long n, float target, float* ws,
-                                                        float* loss) {
+// ---- pointwise losses --------------------------------------------------------------------------------------------------------
+// Every pointwise loss is one term functor: term(i) is element i's summand, grad(i, k) its derivative times k = upstream * gain / n.
+// The two kernels below are the only grid-stride walks; a term is handed its indices in ascending order, seek(i, step) first.
+struct DenseTerm { __device__ void seek(long long, long long) {} };      // (a term indexed by i alone keeps no cursor)
+
+template <typename F>
+__global__ __launch_bounds__(256) void reduce_kernel(F f, long long n, float* ws, float* out) {
   __shared__ float sh[4];
   float s = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float d = x[i] - target;
-    s += d * d;
-  }
+  const long long step = (long long)gridDim.x * blockDim.x;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  f.seek(i, step);
+  for (; i < n; i += step) s += f.term(i);
   s = block_sum(s, sh);
-  finish_reduction(s, ws, 1.0f / (float)n, loss);
+  finish_reduction(s, ws, 1.0f / (float)n, out);
 }
-__global__ __launch_bounds__(256) void mse_const_grad_kernel(const float* x, long long n, float target, float* grad,
-                                                             const float* gscale) {
-  const float k = (gscale ? gscale[0] : 1.f) * 2.0f / (float)n;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    grad[i] = k * (x[i] - target);
+template <typename F>
+__global__ __launch_bounds__(256) void map_kernel(F f, long long n, float* grad, const float* gscale) {
+  const float k = (gscale ? gscale[0] : 1.f) * F::gain / (float)n;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  f.seek(i, step);
+  for (; i < n; i += step) grad[i] = f.grad(i, k);
 }
+
+struct MseConstTerm : DenseTerm {
+  const float* x; float target;
+  static constexpr float gain = 2.f;
+  __device__ float term(long long i) const { const float d = x[i] - target; return d * d; }
+  __device__ float grad(long long i, float k) const { return k * (x[i] - target); }
+};
 
 // The other GAN objectives of AdversarialLoss (adversarial_loss.py:26-34,60-73) as one pointwise function per mode:
 //   vanilla       nn.BCEWithLogitsLoss vs the expanded label t: f = max(x,0) - x t + log1p(exp(-|x|)), f' = sigmoid(x) - t
@@ -92,22 +106,12 @@ __device__ __forceinline__ float adv_point_grad(float x, float label, float sgn)
   return z > 20.f ? sgn : sgn / (1.f + expf(-z));
 }
 template <int MODE>
-__global__ __launch_bounds__(256) void adv_loss_kernel(const float* x, long long n, float label, float sgn, float* ws,
-                                                       float* loss) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    s += adv_point<MODE>(x[i], label, sgn);
-  s = block_sum(s, sh);
-  finish_reduction(s, ws, 1.0f / (float)n, loss);
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void adv_loss_grad_kernel(const float* x, long long n, float label, float sgn,
-                                                            float* grad, const float* gscale) {
-  const float k = (gscale ? gscale[0] : 1.f) / (float)n;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    grad[i] = k * adv_point_grad<MODE>(x[i], label, sgn);
-}
+struct AdvTerm : DenseTerm {
+  const float* x; float label, sgn;
+  static constexpr float gain = 1.f;
+  __device__ float term(long long i) const { return adv_point<MODE>(x[i], label, sgn); }
+  __device__ float grad(long long i, float k) const { return k * adv_point_grad<MODE>(x[i], label, sgn); }
+};
 // nonsaturating: one workgroup per sample, fixed-shape sum
 __global__ __launch_bounds__(256) void adv_rows_kernel(const float* x, long long per, float sgn, float* loss) {
   __shared__ float sh[4];
@@ -125,30 +129,33 @@ __global__ __launch_bounds__(256) void adv_rows_grad_kernel(const float* x, long
     grad[base + i] = k * adv_point_grad<ADV_NONSAT>(x[base + i], 0.f, sgn);
 }
 
-__global__ __launch_bounds__(256) void l1_kernel(const float* a, const float* b, long long n, float* ws, float* loss) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    s += fabsf(a[i] - b[i]);
-  s = block_sum(s, sh);
-  finish_reduction(s, ws, 1.0f / (float)n, loss);
-}
-__global__ __launch_bounds__(256) void l1_grad_kernel(const float* a, const float* b, long long n, float* grad,
-                                                      const float* gscale) {
-  const float k = (gscale ? gscale[0] : 1.f) / (float)n;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float d = a[i] - b[i];
-    grad[i] = d > 0.f ? k : (d < 0.f ? -k : 0.f);
+struct L1Term : DenseTerm {
+  const float* a; const float* b;
+  static constexpr float gain = 1.f;
+  __device__ float term(long long i) const { return fabsf(a[i] - b[i]); }
+  __device__ float grad(long long i, float k) const { const float d = a[i] - b[i]; return d > 0.f ? k : (d < 0.f ? -k : 0.f); }
+};
+struct MeanTerm : DenseTerm {
+  const float* x;
+  __device__ float term(long long i) const { return x[i]; }
+};
+// L1 with a strided first operand (a channel window of a real image): sample n of `a` is `per` contiguous floats at
+// a + n * stride, b is dense. The flat index i = n * per + r walks the same grid-stride loop as L1Term (same partial sums, same
+// final order); the cursor (smp, r) follows it without a division per element. The gradient is the dense operand's: sign(b - a) * k.
+struct L1WindowTerm {
+  const float* a; long long stride; const float* b; long long per;
+  long long smp, r, step;
+  static constexpr float gain = 1.f;
+  __device__ void seek(long long i, long long step_) { smp = i / per; r = i - smp * per; step = step_; }
+  __device__ float diff(long long i) {
+    const float d = a[smp * stride + r] - b[i];
+    r += step;
+    if (r >= per) { const long long q = r / per; smp += q; r -= q * per; }      // (a division only where a sample ends)
+    return d;
   }
-}
-__global__ __launch_bounds__(256) void mean_kernel(const float* x, long long n, float* ws, float* out) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    s += x[i];
-  s = block_sum(s, sh);
-  finish_reduction(s, ws, 1.0f / (float)n, out);
-}
+  __device__ float term(long long i) { return fabsf(diff(i)); }
+  __device__ float grad(long long i, float k) { const float d = diff(i); return d > 0.f ? -k : (d < 0.f ? k : 0.f); }
+};
 
 static inline unsigned red_blocks(long long n) {
   long long b = (n + 256 * 8 - 1) / (256 * 8);
@@ -156,105 +163,62 @@ static inline unsigned red_blocks(long long n) {
   if (b > 1024) b = 1024;
   return (unsigned)b;
 }
+// this stream's partial-sum workspace, or null with the error set (gs_reduce_workspace's own "more than %d streams" stands)
+static float* reduce_workspace(const char* entry, void* stream) {
+  float* ws = gs_reduce_workspace(stream);
+  if (!ws && !gs_zero_page()) gs_set_error("%s: library not initialised (call gs_init)", entry);
+  return ws;
+}
+// loss = mean of f.term over n elements, then grad = its derivative (either may be null)
+template <typename F>
+static int pointwise_loss(const char* entry, F f, long long n, float* loss, float* grad, const float* gscale, void* stream) {
+  float* ws = reduce_workspace(entry, stream);
+  if (!ws) return 2;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (loss) hipLaunchKernelGGL(reduce_kernel<F>, dim3(red_blocks(n)), dim3(256), 0, st, f, n, ws, loss);
+  if (grad) hipLaunchKernelGGL(map_kernel<F>, dim3(red_blocks(n)), dim3(256), 0, st, f, n, grad, gscale);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
 extern "C" int gs_mse_const(const float* x, int64_t n, float target, float* loss, float* grad,
                             const float* grad_scale, void* stream) {
   GS_REQUIRE(x && n > 0 && (loss || grad), "gs_mse_const: bad argument");
-  float* ws = gs_reduce_workspace(stream);
-  if (!ws) { if (!gs_zero_page()) gs_set_error("gs_mse_const: library not initialised (call gs_init)"); return 2; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (loss) hipLaunchKernelGGL(mse_const_kernel, dim3(red_blocks(n)), dim3(256), 0, st, x, (long long)n, target, ws, loss);
-  if (grad) hipLaunchKernelGGL(mse_const_grad_kernel, dim3(red_blocks(n)), dim3(256), 0, st, x, (long long)n, target, grad, grad_scale);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-template <int MODE>
-static void adv_launch(const float* x, long long n, float label, float sgn, float* ws, float* loss, float* grad,
-                       const float* gscale, hipStream_t st) {
-  if (loss) hipLaunchKernelGGL(adv_loss_kernel<MODE>, dim3(red_blocks(n)), dim3(256), 0, st, x, n, label, sgn, ws, loss);
-  if (grad) hipLaunchKernelGGL(adv_loss_grad_kernel<MODE>, dim3(red_blocks(n)), dim3(256), 0, st, x, n, label, sgn, grad, gscale);
+  return pointwise_loss("gs_mse_const", MseConstTerm{{}, x, target}, n, loss, grad, grad_scale, stream);
 }
 extern "C" int gs_adv_loss(const float* x, int64_t n, int32_t rows, int32_t mode, int32_t target_is_real, float label,
                            float* loss, float* grad, const float* grad_scale, void* stream) {
   GS_REQUIRE(x && n > 0 && (loss || grad) && mode >= ADV_LSGAN && mode <= ADV_NONSAT, "gs_adv_loss: bad argument");
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const float sgn = target_is_real ? -1.f : 1.f;
   if (mode == ADV_NONSAT) {
     GS_REQUIRE(rows > 0 && n % rows == 0, "gs_adv_loss: nonsaturating needs n divisible by rows (the batch)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (loss) hipLaunchKernelGGL(adv_rows_kernel, dim3(rows), dim3(256), 0, st, x, (long long)(n / rows), sgn, loss);
     if (grad) hipLaunchKernelGGL(adv_rows_grad_kernel, dim3(rows), dim3(256), 0, st, x, (long long)(n / rows), sgn, grad, grad_scale);
     GS_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  float* ws = gs_reduce_workspace(stream);
-  if (!ws) { if (!gs_zero_page()) gs_set_error("gs_adv_loss: library not initialised (call gs_init)"); return 2; }
-  if (mode == ADV_LSGAN) adv_launch<ADV_LSGAN>(x, n, label, sgn, ws, loss, grad, grad_scale, st);
-  else if (mode == ADV_VANILLA) adv_launch<ADV_VANILLA>(x, n, label, sgn, ws, loss, grad, grad_scale, st);
-  else adv_launch<ADV_WGANGP>(x, n, label, sgn, ws, loss, grad, grad_scale, st);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
+  if (mode == ADV_LSGAN) return pointwise_loss("gs_adv_loss", AdvTerm<ADV_LSGAN>{{}, x, label, sgn}, n, loss, grad, grad_scale, stream);
+  if (mode == ADV_VANILLA) return pointwise_loss("gs_adv_loss", AdvTerm<ADV_VANILLA>{{}, x, label, sgn}, n, loss, grad, grad_scale, stream);
+  return pointwise_loss("gs_adv_loss", AdvTerm<ADV_WGANGP>{{}, x, label, sgn}, n, loss, grad, grad_scale, stream);
 }
 extern "C" int gs_l1(const float* a, const float* b, int64_t n, float* loss, float* grad_a, const float* grad_scale,
                      void* stream) {
   GS_REQUIRE(a && b && n > 0 && (loss || grad_a), "gs_l1: bad argument");
-  float* ws = gs_reduce_workspace(stream);
-  if (!ws) { if (!gs_zero_page()) gs_set_error("gs_l1: library not initialised (call gs_init)"); return 2; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (loss) hipLaunchKernelGGL(l1_kernel, dim3(red_blocks(n)), dim3(256), 0, st, a, b, (long long)n, ws, loss);
-  if (grad_a) hipLaunchKernelGGL(l1_grad_kernel, dim3(red_blocks(n)), dim3(256), 0, st, a, b, (long long)n, grad_a, grad_scale);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-// gs_l1 with a strided first operand (a channel window of a real image): sample n of `a` is `per` contiguous floats at
-// a + n * stride, b is dense. The flat index i = n * per + r walks the grid-stride loop of l1_kernel (same partial sums, same
-// final order); (n, r) follow it without a division per element. The gradient is the dense operand's: sign(b - a) * k.
-__global__ __launch_bounds__(256) void l1_window_kernel(const float* a, long long stride, const float* b, long long per,
-                                                        long long n, float* ws, float* loss) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  const long long step = (long long)gridDim.x * blockDim.x;
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  long long smp = i / per, r = i - smp * per;
-  for (; i < n; i += step) {
-    s += fabsf(a[smp * stride + r] - b[i]);
-    r += step;
-    if (r >= per) { const long long q = r / per; smp += q; r -= q * per; }      // (a division only where a sample ends)
-  }
-  s = block_sum(s, sh);
-  finish_reduction(s, ws, 1.0f / (float)n, loss);
-}
-__global__ __launch_bounds__(256) void l1_window_grad_kernel(const float* a, long long stride, const float* b, long long per,
-                                                             long long n, float* grad_b, const float* gscale) {
-  const float k = (gscale ? gscale[0] : 1.f) / (float)n;
-  const long long step = (long long)gridDim.x * blockDim.x;
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  long long smp = i / per, r = i - smp * per;
-  for (; i < n; i += step) {
-    const float d = a[smp * stride + r] - b[i];
-    grad_b[i] = d > 0.f ? -k : (d < 0.f ? k : 0.f);
-    r += step;
-    if (r >= per) { const long long q = r / per; smp += q; r -= q * per; }      // (a division only where a sample ends)
-  }
+  return pointwise_loss("gs_l1", L1Term{{}, a, b}, n, loss, grad_a, grad_scale, stream);
 }
 extern "C" int gs_l1_window(const float* a, int64_t a_sample_stride, const float* b, int32_t N, int64_t per, float* loss,
                             float* grad_b, const float* grad_scale, void* stream) {
   GS_REQUIRE(a && b && N > 0 && per > 0 && a_sample_stride >= per && (loss || grad_b), "gs_l1_window: bad argument");
-  float* ws = gs_reduce_workspace(stream);
-  if (!ws) { if (!gs_zero_page()) gs_set_error("gs_l1_window: library not initialised (call gs_init)"); return 2; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long n = (long long)N * per;
-  if (loss) hipLaunchKernelGGL(l1_window_kernel, dim3(red_blocks(n)), dim3(256), 0, st, a, (long long)a_sample_stride, b,
-                               (long long)per, n, ws, loss);
-  if (grad_b) hipLaunchKernelGGL(l1_window_grad_kernel, dim3(red_blocks(n)), dim3(256), 0, st, a, (long long)a_sample_stride, b,
-                                 (long long)per, n, grad_b, grad_scale);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
+  return pointwise_loss("gs_l1_window", L1WindowTerm{a, (long long)a_sample_stride, b, (long long)per, 0, 0, 0},
+                        (long long)N * per, loss, grad_b, grad_scale, stream);
 }
 extern "C" int gs_mean(const float* x, int64_t n, float* out, void* stream) {
   GS_REQUIRE(x && out && n > 0, "gs_mean: bad argument");
-  float* ws = gs_reduce_workspace(stream);
-  if (!ws) { if (!gs_zero_page()) gs_set_error("gs_mean: library not initialised (call gs_init)"); return 2; }
-  hipLaunchKernelGGL(mean_kernel, dim3(red_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long long)n, ws, out);
+  float* ws = reduce_workspace("gs_mean", stream);
+  if (!ws) return 2;
+  hipLaunchKernelGGL(reduce_kernel<MeanTerm>, dim3(red_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), MeanTerm{{}, x},
+                     (long long)n, ws, out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -286,86 +250,6 @@ __device__ __forceinline__ SsimTerms ssim_terms(float m1, float m2, float xx, fl
   return t;
 }
 
-// x may be a channel window: plane p of sample n at x + n * xstride + p * H * W, xpl planes per sample (dense: xpl = all
-// planes, one "sample")
-__global__ __launch_bounds__(256) void ssim_kernel(const float* x, int xpl, long long xstride, const float* y, int H, int W,
-                                                   int tiles_w, int tiles_h, float* partial) {
-  __shared__ float sx[SSIM_TH + 10][SSIM_TW + 10];
-  __shared__ float sy[SSIM_TH + 10][SSIM_TW + 10];
-  __shared__ float hz[5][SSIM_TH + 10][SSIM_TW];
-  __shared__ float sh[4];
-  int b = blockIdx.x;
-  const int tw = b % tiles_w; b /= tiles_w;
-  const int th = b % tiles_h; const int plane = b / tiles_h;
-  const int Ho = H - 10, Wo = W - 10;
-  const int oh0 = th * SSIM_TH, ow0 = tw * SSIM_TW;
-  const float* xp = x + (size_t)(plane / xpl) * xstride + (size_t)(plane % xpl) * H * W;
-  const float* yp = y + (size_t)plane * H * W;
-  for (int e = threadIdx.x; e < (SSIM_TH + 10) * (SSIM_TW + 10); e += 256) {
-    const int r = e / (SSIM_TW + 10), c = e % (SSIM_TW + 10);
-    const int ih = oh0 + r, iw = ow0 + c;
-    float a = 0.f, bb = 0.f;
-    if (ih < H && iw < W) { a = (xp[(size_t)ih * W + iw] + 1.f) * 0.5f; bb = (yp[(size_t)ih * W + iw] + 1.f) * 0.5f; }
-    sx[r][c] = a; sy[r][c] = bb;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < (SSIM_TH + 10) * SSIM_TW; e += 256) {
-    const int r = e / SSIM_TW, c = e % SSIM_TW;
-    float m1 = 0.f, m2 = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const float g = c_gauss[k], a = sx[r][c + k], bb = sy[r][c + k];
-      m1 += g * a; m2 += g * bb; xx += g * a * a; yy += g * bb * bb; xy += g * a * bb;
-    }
-    hz[0][r][c] = m1; hz[1][r][c] = m2; hz[2][r][c] = xx; hz[3][r][c] = yy; hz[4][r][c] = xy;
-  }
-  __syncthreads();
-  float acc = 0.f;
-  for (int e = threadIdx.x; e < SSIM_TH * SSIM_TW; e += 256) {
-    const int r = e / SSIM_TW, c = e % SSIM_TW;
-    if (oh0 + r < Ho && ow0 + c < Wo) {
-      float m1 = 0.f, m2 = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const float g = c_gauss[k];
-        m1 += g * hz[0][r + k][c]; m2 += g * hz[1][r + k][c]; xx += g * hz[2][r + k][c];
-        yy += g * hz[3][r + k][c]; xy += g * hz[4][r + k][c];
-      }
-      const SsimTerms t = ssim_terms(m1, m2, xx, yy, xy);
-      const float S = fmaxf(2.f - (t.A1 / t.B1 + t.A2 / t.B2), 0.f);
-      acc += sqrtf(S);
-    }
-  }
-  acc = block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-__global__ void ssim_final_kernel(const float* partial, int n, float scale, float* out) {
-  __shared__ double sh[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] * (double)scale);
-}
-
-static int ssim_init_gauss() {
-  static bool init = false;
-  if (!init) {
-    // fp32 restatement of _fspecial_gauss_1d(11, 1.5) (ssim.py:22-40)
-    float g[11], s = 0.f;
-    for (int i = 0; i < 11; ++i) { const float c = (float)(i - 5); g[i] = expf(-(c * c) / (2.f * 1.5f * 1.5f)); s += g[i]; }
-    for (int i = 0; i < 11; ++i) g[i] /= s;
-    GS_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g)));
-    init = true;
-  }
-  return 0;
-}
-
-extern "C" int64_t gs_ssim_scratch_floats(int32_t NC, int32_t H, int32_t W) {
-  const int64_t th = (H - 10 + SSIM_TH - 1) / SSIM_TH, tw = (W - 10 + SSIM_TW - 1) / SSIM_TW;
-  return (int64_t)NC * th * tw;
-}
 // The window form's forward in double: the balanced recipe's translated channels are often one small plane per sample (a
 // 3 x 12 x 11 volume has 6 valid pixels), where nothing averages the per-pixel fp32 error of the cancelling variance terms out
 // (measured 6.8e-7 relative on such an input, fp32 in any operation order 5e-9 .. 1.1e-6). Same tiling, same fp32 Gaussian
@@ -381,119 +265,29 @@ __device__ __forceinline__ double ssim_s_double(double m1, double m2, double xx,
   const double S2 = (2.0 * (xy - m12) + C2) / (((xx - m11) + (yy - m22)) + C2);
   return 2.0 - (S1 + S2);
 }
-__global__ __launch_bounds__(256) void ssim_window_kernel(const float* x, int xpl, long long xstride, const float* y, int H,
-                                                          int W, int tiles_w, int tiles_h, double* partial) {
-  __shared__ double sx[SSIM_TH + 10][SSIM_TW + 10];
-  __shared__ double sy[SSIM_TH + 10][SSIM_TW + 10];
-  __shared__ double hz[5][SSIM_TH + 10][SSIM_TW];
-  int b = blockIdx.x;
-  const int tw = b % tiles_w; b /= tiles_w;
-  const int th = b % tiles_h; const int plane = b / tiles_h;
-  const int Ho = H - 10, Wo = W - 10;
-  const int oh0 = th * SSIM_TH, ow0 = tw * SSIM_TW;
-  const float* xp = x + (size_t)(plane / xpl) * xstride + (size_t)(plane % xpl) * H * W;
-  const float* yp = y + (size_t)plane * H * W;
-  for (int e = threadIdx.x; e < (SSIM_TH + 10) * (SSIM_TW + 10); e += 256) {
-    const int r = e / (SSIM_TW + 10), c = e % (SSIM_TW + 10);
-    const int ih = oh0 + r, iw = ow0 + c;
-    double a = 0.0, bb = 0.0;
-    if (ih < H && iw < W) { a = ((double)xp[(size_t)ih * W + iw] + 1.0) * 0.5; bb = ((double)yp[(size_t)ih * W + iw] + 1.0) * 0.5; }
-    sx[r][c] = a; sy[r][c] = bb;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < (SSIM_TH + 10) * SSIM_TW; e += 256) {
-    const int r = e / SSIM_TW, c = e % SSIM_TW;
-    double m1 = 0.0, m2 = 0.0, xx = 0.0, yy = 0.0, xy = 0.0;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const double g = (double)c_gauss[k], a = sx[r][c + k], bb = sy[r][c + k];
-      m1 += g * a; m2 += g * bb; xx += g * a * a; yy += g * bb * bb; xy += g * a * bb;
-    }
-    hz[0][r][c] = m1; hz[1][r][c] = m2; hz[2][r][c] = xx; hz[3][r][c] = yy; hz[4][r][c] = xy;
-  }
-  __syncthreads();
-  double acc = 0.0;
-  for (int e = threadIdx.x; e < SSIM_TH * SSIM_TW; e += 256) {
-    const int r = e / SSIM_TW, c = e % SSIM_TW;
-    if (oh0 + r < Ho && ow0 + c < Wo) {
-      double m1 = 0.0, m2 = 0.0, xx = 0.0, yy = 0.0, xy = 0.0;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const double g = (double)c_gauss[k];
-        m1 += g * hz[0][r + k][c]; m2 += g * hz[1][r + k][c]; xx += g * hz[2][r + k][c];
-        yy += g * hz[3][r + k][c]; xy += g * hz[4][r + k][c];
-      }
-      acc += sqrt(fmax(ssim_s_double(m1, m2, xx, yy, xy), 0.0));
-    }
-  }
-  // fixed-shape tree over the 256 threads (sx is free again: every thread is past its last read of it)
-  __syncthreads();
-  double* tree = &sx[0][0];
-  tree[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) tree[threadIdx.x] += tree[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) partial[blockIdx.x] = tree[0];
-}
-__global__ void ssim_window_final_kernel(const double* partial, int n, double scale, float* out) {
-  __shared__ double sh[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
-}
 
-static int ssim_forward(const float* x, int xpl, long long xstride, const float* y, int32_t NC, int32_t H, int32_t W,
-                        float* out, float* scratch, void* stream) {
-  if (int rc = ssim_init_gauss()) return rc;
-  const int th = (H - 10 + SSIM_TH - 1) / SSIM_TH, tw = (W - 10 + SSIM_TW - 1) / SSIM_TW;
-  const int blocks = NC * th * tw;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(ssim_kernel, dim3(blocks), dim3(256), 0, st, x, xpl, xstride, y, H, W, tw, th, scratch);
-  const double cnt = (double)NC * (H - 10) * (W - 10);
-  hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, st, scratch, blocks, (float)(1.0 / cnt), out);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-extern "C" int gs_ssim_distance(const float* x, const float* y, int32_t NC, int32_t H, int32_t W, float* out,
-                                float* scratch, void* stream) {
-  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance: bad argument");
-  return ssim_forward(x, NC, 0, y, NC, H, W, out, scratch, stream);
-}
-extern "C" int gs_ssim_distance_window(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y, int32_t NC,
-                                       int32_t H, int32_t W, float* out, float* scratch, void* stream) {
-  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance_window: bad argument");
-  GS_REQUIRE(x_planes > 0 && NC % x_planes == 0 && x_sample_stride >= (int64_t)x_planes * H * W,
-             "gs_ssim_distance_window: NC must be samples * x_planes and the sample stride >= x_planes * H * W");
-  GS_REQUIRE(((uintptr_t)scratch & 7) == 0, "gs_ssim_distance_window: scratch must be 8-byte aligned (one double per tile)");
-  if (int rc = ssim_init_gauss()) return rc;
-  const int th = (H - 10 + SSIM_TH - 1) / SSIM_TH, tw = (W - 10 + SSIM_TW - 1) / SSIM_TW;
-  const int blocks = NC * th * tw;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  double* part = reinterpret_cast<double*>(scratch);
-  hipLaunchKernelGGL(ssim_window_kernel, dim3(blocks), dim3(256), 0, st, x, x_planes, (long long)x_sample_stride, y, H, W, tw, th,
-                     part);
-  hipLaunchKernelGGL(ssim_window_final_kernel, dim3(1), dim3(256), 0, st, part, blocks,
-                     1.0 / ((double)NC * (H - 10) * (W - 10)), out);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-
-// ---- SSIM distance: gradient w.r.t. the second image (the distance is symmetric, swap the arguments for the first) ----
+// The gradient w.r.t. the second image (the distance is symmetric, swap the arguments for the first):
 // L = mean(D), D = sqrt(relu(2 - S1 - S2)) with mu1 = b(X), mu2 = b(Y), e11 = b(XX), e22 = b(YY), e12 = b(XY) (b = the
 // separable 11-tap Gaussian, valid region). Per output pixel o, with gD = -dL/(2 D n):
 //   G0 = gD * (dS1/dmu2 - mu1 * dS2/ds12 - 2 mu2 * dS2/ds2),  G1 = gD * dS2/ds12,  G2 = gD * dS2/ds2
 //   dS1/dmu2 = (2 mu1 B1 - 2 mu2 A1) / B1^2,  dS2/ds12 = 2 / B2,  dS2/ds2 = -A2 / B2^2   (S1 = A1/B1, S2 = A2/B2)
 // and dL/dY(p) = 1/2 * ( bT(G0)(p) + X(p) bT(G1)(p) + 2 Y(p) bT(G2)(p) ) with bT the transposed (full) Gaussian; the 1/2 is
 // the (y + 1)/2 input mapping (nn/losses/utils/ssim.py:65-99 differentiated; cyclegan_losses.py:78-90 uses it as a loss).
-__global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, int xpl, long long xstride, const float* y, int H,
-                                                             int W, int tiles_w, int tiles_h, const float* grad_scale, float inv_cnt,
-                                                             float* maps, size_t map_stride) {
-  __shared__ float sx[SSIM_TH + 10][SSIM_TW + 10];
-  __shared__ float sy[SSIM_TH + 10][SSIM_TW + 10];
-  __shared__ float hz[5][SSIM_TH + 10][SSIM_TW];
+//
+// One 16x32 tile of one plane in the arithmetic type T (the fp32 Gaussian weights are widened per use), shared by the forward
+// kernels and the gradient maps: which tile of which plane this workgroup is, the (16+10)x(32+10) patch of both images staged
+// with the (v + 1) / 2 mapping (zero past the plane), the horizontal 11-tap pass of the five moments X, Y, XX, YY, XY, then per
+// valid output pixel the vertical pass and either the distance, summed per thread and returned, or (MAPS) G0, G1, G2.
+// x may be a channel window: plane p of sample n at x + n * xstride + p * H * W, xpl planes per sample (dense: xpl = all
+// planes, one "sample"). The three tails stay inside this one body, after the vertical pass: with the pass behind a call of its
+// own, hipcc pairs its taps differently and contracts other products to fmas, and the gradient maps change in the last bit.
+template <typename T> __shared__ T ssim_sx[SSIM_TH + 10][SSIM_TW + 10];
+template <typename T> __shared__ T ssim_sy[SSIM_TH + 10][SSIM_TW + 10];
+template <typename T> __shared__ T ssim_hz[5][SSIM_TH + 10][SSIM_TW];
+template <typename T, bool MAPS>
+__device__ __forceinline__ T ssim_tile(const float* x, int xpl, long long xstride, const float* y, int H, int W, int tiles_w,
+                                       int tiles_h, const float* grad_scale = nullptr, float inv_cnt = 0.f, float* maps = nullptr,
+                                       size_t map_stride = 0) {
   int b = blockIdx.x;
   const int tw = b % tiles_w; b /= tiles_w;
   const int th = b % tiles_h; const int plane = b / tiles_h;
@@ -504,50 +298,157 @@ __global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, int
   for (int e = threadIdx.x; e < (SSIM_TH + 10) * (SSIM_TW + 10); e += 256) {
     const int r = e / (SSIM_TW + 10), c = e % (SSIM_TW + 10);
     const int ih = oh0 + r, iw = ow0 + c;
-    float a = 0.f, bb = 0.f;
-    if (ih < H && iw < W) { a = (xp[(size_t)ih * W + iw] + 1.f) * 0.5f; bb = (yp[(size_t)ih * W + iw] + 1.f) * 0.5f; }
-    sx[r][c] = a; sy[r][c] = bb;
+    T a = 0, bb = 0;
+    if (ih < H && iw < W) { a = ((T)xp[(size_t)ih * W + iw] + (T)1) * (T)0.5; bb = ((T)yp[(size_t)ih * W + iw] + (T)1) * (T)0.5; }
+    ssim_sx<T>[r][c] = a; ssim_sy<T>[r][c] = bb;
   }
   __syncthreads();
   for (int e = threadIdx.x; e < (SSIM_TH + 10) * SSIM_TW; e += 256) {
     const int r = e / SSIM_TW, c = e % SSIM_TW;
-    float m1 = 0.f, m2 = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
+    T m1 = 0, m2 = 0, xx = 0, yy = 0, xy = 0;
 #pragma unroll
     for (int k = 0; k < 11; ++k) {
-      const float g = c_gauss[k], a = sx[r][c + k], bb = sy[r][c + k];
+      const T g = (T)c_gauss[k], a = ssim_sx<T>[r][c + k], bb = ssim_sy<T>[r][c + k];
       m1 += g * a; m2 += g * bb; xx += g * a * a; yy += g * bb * bb; xy += g * a * bb;
     }
-    hz[0][r][c] = m1; hz[1][r][c] = m2; hz[2][r][c] = xx; hz[3][r][c] = yy; hz[4][r][c] = xy;
+    ssim_hz<T>[0][r][c] = m1; ssim_hz<T>[1][r][c] = m2; ssim_hz<T>[2][r][c] = xx; ssim_hz<T>[3][r][c] = yy; ssim_hz<T>[4][r][c] = xy;
   }
   __syncthreads();
-  const float up = (grad_scale ? grad_scale[0] : 1.f) * inv_cnt;
-  float* mp = maps + (size_t)plane * Ho * Wo;
+  const float up = MAPS ? (grad_scale ? grad_scale[0] : 1.f) * inv_cnt : 0.f;
+  float* mp = MAPS ? maps + (size_t)plane * Ho * Wo : nullptr;
+  T acc = 0;
   for (int e = threadIdx.x; e < SSIM_TH * SSIM_TW; e += 256) {
     const int r = e / SSIM_TW, c = e % SSIM_TW;
     if (oh0 + r < Ho && ow0 + c < Wo) {
-      float m1 = 0.f, m2 = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
+      T m1 = 0, m2 = 0, xx = 0, yy = 0, xy = 0;
 #pragma unroll
       for (int k = 0; k < 11; ++k) {
-        const float g = c_gauss[k];
-        m1 += g * hz[0][r + k][c]; m2 += g * hz[1][r + k][c]; xx += g * hz[2][r + k][c];
-        yy += g * hz[3][r + k][c]; xy += g * hz[4][r + k][c];
+        const T g = (T)c_gauss[k];
+        m1 += g * ssim_hz<T>[0][r + k][c]; m2 += g * ssim_hz<T>[1][r + k][c]; xx += g * ssim_hz<T>[2][r + k][c];
+        yy += g * ssim_hz<T>[3][r + k][c]; xy += g * ssim_hz<T>[4][r + k][c];
       }
-      const SsimTerms t = ssim_terms(m1, m2, xx, yy, xy);
-      const float A1 = t.A1, B1 = t.B1, A2 = t.A2, B2 = t.B2;
-      const float S = 2.f - (A1 / B1 + A2 / B2);
-      float g0 = 0.f, g1 = 0.f, g2 = 0.f;
-      if (S > 0.f) {
-        const float gD = -up / (2.f * sqrtf(S));
-        const float dS1 = (2.f * m1 * B1 - 2.f * m2 * A1) / (B1 * B1);
-        const float dS2_12 = 2.f / B2, dS2_2 = -A2 / (B2 * B2);
-        g0 = gD * (dS1 - m1 * dS2_12 - 2.f * m2 * dS2_2);
-        g1 = gD * dS2_12;
-        g2 = gD * dS2_2;
+      if constexpr (std::is_same<T, double>::value) {
+        acc += sqrt(fmax(ssim_s_double(m1, m2, xx, yy, xy), 0.0));
+      } else {
+        const SsimTerms t = ssim_terms(m1, m2, xx, yy, xy);
+        const float A1 = t.A1, B1 = t.B1, A2 = t.A2, B2 = t.B2;
+        if constexpr (!MAPS) {
+          const float S = fmaxf(2.f - (A1 / B1 + A2 / B2), 0.f);
+          acc += sqrtf(S);
+        } else {
+          const float S = 2.f - (A1 / B1 + A2 / B2);
+          float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+          if (S > 0.f) {
+            const float gD = -up / (2.f * sqrtf(S));
+            const float dS1 = (2.f * m1 * B1 - 2.f * m2 * A1) / (B1 * B1);
+            const float dS2_12 = 2.f / B2, dS2_2 = -A2 / (B2 * B2);
+            g0 = gD * (dS1 - m1 * dS2_12 - 2.f * m2 * dS2_2);
+            g1 = gD * dS2_12;
+            g2 = gD * dS2_2;
+          }
+          const size_t o = (size_t)(oh0 + r) * Wo + (ow0 + c);
+          mp[o] = g0; mp[map_stride + o] = g1; mp[2 * map_stride + o] = g2;
+        }
       }
-      const size_t o = (size_t)(oh0 + r) * Wo + (ow0 + c);
-      mp[o] = g0; mp[map_stride + o] = g1; mp[2 * map_stride + o] = g2;
     }
   }
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void ssim_kernel(const float* x, int xpl, long long xstride, const float* y, int H, int W,
+                                                   int tiles_w, int tiles_h, float* partial) {
+  __shared__ float sh[4];
+  float acc = ssim_tile<float, false>(x, xpl, xstride, y, H, W, tiles_w, tiles_h);
+  acc = block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+__global__ __launch_bounds__(256) void ssim_window_kernel(const float* x, int xpl, long long xstride, const float* y, int H,
+                                                          int W, int tiles_w, int tiles_h, double* partial) {
+  const double acc = ssim_tile<double, false>(x, xpl, xstride, y, H, W, tiles_w, tiles_h);
+  // fixed-shape tree over the 256 threads (ssim_sx is free again: every thread is past its last read of it)
+  __syncthreads();
+  double* tree = &ssim_sx<double>[0][0];
+  tree[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) tree[threadIdx.x] += tree[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) partial[blockIdx.x] = tree[0];
+}
+__global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, int xpl, long long xstride, const float* y, int H,
+                                                             int W, int tiles_w, int tiles_h, const float* grad_scale, float inv_cnt,
+                                                             float* maps, size_t map_stride) {
+  ssim_tile<float, true>(x, xpl, xstride, y, H, W, tiles_w, tiles_h, grad_scale, inv_cnt, maps, map_stride);
+}
+// the per-tile partials (float or double) summed in index order by one workgroup, in double
+template <typename P>
+__global__ void ssim_final_kernel(const P* partial, int n, double scale, float* out) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
+}
+
+static int ssim_init_gauss() {
+  static bool init = false;
+  if (!init) {
+    // fp32 restatement of _fspecial_gauss_1d(11, 1.5) (ssim.py:22-40)
+    float g[11], s = 0.f;
+    for (int i = 0; i < 11; ++i) { const float c = (float)(i - 5); g[i] = expf(-(c * c) / (2.f * 1.5f * 1.5f)); s += g[i]; }
+    for (int i = 0; i < 11; ++i) g[i] /= s;
+    GS_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g)));
+    init = true;
+  }
+  return 0;
+}
+
+// tiles of 16 x 32 covering rows x cols pixels
+static inline void ssim_tiles(int rows, int cols, int* th, int* tw) {
+  *th = (rows + SSIM_TH - 1) / SSIM_TH;
+  *tw = (cols + SSIM_TW - 1) / SSIM_TW;
+}
+// the arguments of a window entry point: as the dense ones, plus the window's layout
+static int ssim_window_check(const char* entry, const float* x, const float* y, const float* out, const float* scratch, int32_t NC,
+                             int32_t H, int32_t W, int32_t x_planes, int64_t x_sample_stride) {
+  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "%s: bad argument", entry);
+  GS_REQUIRE(x_planes > 0 && NC % x_planes == 0 && x_sample_stride >= (int64_t)x_planes * H * W,
+             "%s: NC must be samples * x_planes and the sample stride >= x_planes * H * W", entry);
+  return 0;
+}
+
+extern "C" int64_t gs_ssim_scratch_floats(int32_t NC, int32_t H, int32_t W) {
+  int th, tw;
+  ssim_tiles(H - 10, W - 10, &th, &tw);
+  return (int64_t)NC * th * tw;
+}
+// one partial of type P per tile by `kernel`, then their mean over the valid pixels
+template <typename P>
+static int ssim_forward(void (*kernel)(const float*, int, long long, const float*, int, int, int, int, P*), const float* x, int xpl,
+                        long long xstride, const float* y, int32_t NC, int32_t H, int32_t W, float* out, P* partial, void* stream) {
+  if (int rc = ssim_init_gauss()) return rc;
+  int th, tw;
+  ssim_tiles(H - 10, W - 10, &th, &tw);
+  const int blocks = NC * th * tw;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, x, xpl, xstride, y, H, W, tw, th, partial);
+  double scale = 1.0 / ((double)NC * (H - 10) * (W - 10));
+  if (std::is_same<P, float>::value) scale = (double)(float)scale;      // the fp32 path has always rounded its scale to fp32
+  hipLaunchKernelGGL(ssim_final_kernel<P>, dim3(1), dim3(256), 0, st, partial, blocks, scale, out);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int gs_ssim_distance(const float* x, const float* y, int32_t NC, int32_t H, int32_t W, float* out,
+                                float* scratch, void* stream) {
+  GS_REQUIRE(x && y && out && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance: bad argument");
+  return ssim_forward(ssim_kernel, x, NC, 0, y, NC, H, W, out, scratch, stream);
+}
+extern "C" int gs_ssim_distance_window(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y, int32_t NC,
+                                       int32_t H, int32_t W, float* out, float* scratch, void* stream) {
+  if (int rc = ssim_window_check("gs_ssim_distance_window", x, y, out, scratch, NC, H, W, x_planes, x_sample_stride)) return rc;
+  GS_REQUIRE(((uintptr_t)scratch & 7) == 0, "gs_ssim_distance_window: scratch must be 8-byte aligned (one double per tile)");
+  return ssim_forward(ssim_window_kernel, x, x_planes, (long long)x_sample_stride, y, NC, H, W, out,
+                      reinterpret_cast<double*>(scratch), stream);
 }
 
 // transposed separable Gaussian of the three maps + combination with X, Y: one workgroup = 16x32 input pixels
@@ -614,10 +515,11 @@ static int ssim_backward(const float* x, int xpl, long long xstride, const float
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int Ho = H - 10, Wo = W - 10;
   const size_t map_stride = (size_t)NC * Ho * Wo;
-  const int th = (Ho + SSIM_TH - 1) / SSIM_TH, tw = (Wo + SSIM_TW - 1) / SSIM_TW;
+  int th, tw, th2, tw2;
+  ssim_tiles(Ho, Wo, &th, &tw);
   hipLaunchKernelGGL(ssim_grad_maps_kernel, dim3(NC * th * tw), dim3(256), 0, st, x, xpl, xstride, y, H, W, tw, th, grad_scale,
                      (float)(1.0 / ((double)NC * Ho * Wo)), scratch, map_stride);
-  const int th2 = (H + SSIM_TH - 1) / SSIM_TH, tw2 = (W + SSIM_TW - 1) / SSIM_TW;
+  ssim_tiles(H, W, &th2, &tw2);
   hipLaunchKernelGGL(ssim_bwd_kernel, dim3(NC * th2 * tw2), dim3(256), 0, st, x, xpl, xstride, y, scratch, map_stride, H, W, tw2,
                      th2, grad_y);
   GS_CHECK_HIP(hipGetLastError());
@@ -631,9 +533,8 @@ extern "C" int gs_ssim_distance_backward(const float* x, const float* y, int32_t
 extern "C" int gs_ssim_distance_window_backward(const float* x, int64_t x_sample_stride, int32_t x_planes, const float* y,
                                                 int32_t NC, int32_t H, int32_t W, const float* grad_scale, float* grad_y,
                                                 float* scratch, void* stream) {
-  GS_REQUIRE(x && y && grad_y && scratch && NC > 0 && H > 10 && W > 10, "gs_ssim_distance_window_backward: bad argument");
-  GS_REQUIRE(x_planes > 0 && NC % x_planes == 0 && x_sample_stride >= (int64_t)x_planes * H * W,
-             "gs_ssim_distance_window_backward: NC must be samples * x_planes and the sample stride >= x_planes * H * W");
+  if (int rc = ssim_window_check("gs_ssim_distance_window_backward", x, y, grad_y, scratch, NC, H, W, x_planes, x_sample_stride))
+    return rc;
   return ssim_backward(x, x_planes, x_sample_stride, y, NC, H, W, grad_scale, grad_y, scratch, stream);
 }
 
