@@ -1894,7 +1894,8 @@ def test_patchnce_forward_backward(hip_ops, batch, patches, channels):
     """gs_patchnce_forward / gs_patchnce_backward (FeaturePatchMLP + PatchNCELoss of CUT, all levels in one launch per
     stage) against torch autograd of the reference composition (oracle/ops_ref.patchnce_reference). bf16 operands with
     fp32 accumulate (the logit GEMM with hi + lo split operands: the logits are divided by T = 0.07): loss within 5e-3
-    relative; gradients — three chained bf16 GEMMs behind a soft-max — within 4e-2 relative L2 (measured 1.5e-2 .. 3.1e-2)."""
+    relative; gradients — three chained bf16 GEMMs behind a soft-max — within 4e-2 relative L2 (measured 1.5e-2 .. 3.1e-2).
+    The per-element check of every stage against float64 is tests/test_nce_stages_gpu.py."""
     g = torch.Generator().manual_seed(41)
     nc = 256
     # a tuple: patches per level — FeaturePatchMLP draws min(num_patches, pixels of the level) ids (cut.py:262-268), so the
@@ -1950,7 +1951,8 @@ def test_self_attention_block_forward_backward(hip_ops, B, dims, C):
     torch autograd of the reference composition (oracle/ops_ref.attention_reference = ganslate/nn/attention.py:26-47) on the
     same bf16 input: output within one bf16 ulp of the largest value; dx, and the parameter gradients (accumulated into
     pre-filled tensors), within 3e-2 relative L2 (bf16 q / k / v / attention / gradient tensors between fp32-accumulating
-    GEMMs). Shapes: the discriminator's two blocks at 128^3 inputs (10^3 x 256, 9^3 x 512), a V-Net level, ragged tiles."""
+    GEMMs). Shapes: the discriminator's two blocks at 128^3 inputs (10^3 x 256, 9^3 x 512), a V-Net level, ragged tiles.
+    The per-element check of every stage against float64 is tests/test_attn_stages_gpu.py."""
     from oracle.ops_ref import attention_reference
     g = torch.Generator().manual_seed(91)
     N = 1
