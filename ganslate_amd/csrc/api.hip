@@ -1,5 +1,5 @@
 // Library lifecycle + error plumbing for libganslate_hip.so (see include/ganslate_hip.h).
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>

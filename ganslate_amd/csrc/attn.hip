@@ -14,11 +14,7 @@
 // (2 N^2 (C/8 + C) forward) is a few GFLOP per block, so the launches are bandwidth / latency bound, not MFMA bound.
 // Backward: dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(P o dP)), dQ = dS K, dK = dS^T Q, then the projections'
 // data / weight / bias gradients; dgamma = sum(dout o O) reduced in a fixed order (deterministic).
-#include "common.hpp"
-
-// wgrad.hip: dst[e] += slab 0 [e] + slab 1 [e] + ... in slab order
-void gs_launch_slab_reduce(const float* ws, float* dst, long long n4, int slabs, long long stride4, hipStream_t st, int nets,
-                           long long ws_y4, long long dw_y4);
+#include "internal.hpp"
 
 namespace {
 constexpr int GT = 64;                 // output tile per workgroup (GT x GT), 4 waves of 32 x 32

@@ -6,7 +6,7 @@
 // row (each input pixel is loaded once per kernel row) and reduces over its lanes: v_dot2c_f32_bf16, fp32 accumulation.
 // The weight gradient walks the INPUT pixels instead: x[q] (8 channels per lane) times the 4 x 4 patch of dy around q into
 // 16 x 8 accumulators per lane, per-workgroup slabs added in a fixed order (no atomics).
-#include "common.hpp"
+#include "internal.hpp"
 
 typedef __attribute__((ext_vector_type(2))) __bf16 gs_bf2;
 __device__ __forceinline__ float dot8(const uint4 a, const uint4 b, float acc) {
@@ -203,9 +203,6 @@ static int cout1_wgs_per_img(const gs_wgrad_desc* d) { return (d->Hg + kCout1Row
 extern "C" int64_t gs_wgrad_cout1_ws_floats(const gs_wgrad_desc* d) {
   return gs_wgrad_cout1_eligible(d) ? (int64_t)d->N * cout1_wgs_per_img(d) * 16 * d->Q : -1;
 }
-// wgrad.hip: dst[e] += slab 0 [e] + slab 1 [e] + ... in slab order (nets = 2: the second network's slabs / buffer as well)
-void gs_launch_slab_reduce(const float* ws, float* dst, long long n4, int slabs, long long stride4, hipStream_t st, int nets,
-                           long long ws_y4, long long dw_y4);
 extern "C" int gs_wgrad_cout1_ws(const gs_wgrad_desc* d, const void* a, const void* g, float* dw, float* ws, int64_t ws_floats,
                                  const gs_twin* tw, void* stream) {
   GS_REQUIRE(d && a && g && dw && ws, "gs_wgrad_cout1_ws: null argument");

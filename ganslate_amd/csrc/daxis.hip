@@ -14,7 +14,7 @@
 // then hold the same octets and pick different window slots.
 // Epilogue: bias, activation, InstanceNorm partial sums — one slot of [2][Co] floats per workgroup, summed over the
 // workgroup's lanes and waves in a fixed order (no atomics: two runs give the same bits).
-#include "common.hpp"
+#include "internal.hpp"
 
 namespace {
 struct DaxK {

@@ -17,7 +17,7 @@
 // (128 B), and the bank swizzle (16-B slot ^= row&7) is applied on the per-lane SOURCE address and again on
 // the ds_read_b128 address. The im2col gather happens in that per-lane source address (reflect / replicate /
 // zero borders; out-of-range lanes read a zero page). Two LDS stages, one barrier per K-step of 64.
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 
 #include "gconv.hpp"
@@ -601,16 +601,20 @@ TileCfg pick_tile(const gs_gconv_desc* d) {
 // Split-K plan: layers whose output tiles cannot fill the chip but whose K loop is long (U-Net bottleneck convs with
 // 2..128 pixels and K = 16*1024, the PatchGAN 512->1 tail) are latency-bound on a handful of workgroups that each
 // stream megabytes of weights through a 2-stage ring; splitting K spreads that stream over all CUs. Returns 1 = no split.
-int splitk_plan(const gs_gconv_desc* d, const TileCfg& tc, bool fused) {
-  const bool enabled = gs_opt(GS_OPT_SPLITK) != 0;
-  if (!enabled || fused || (tc.bm != 128 && tc.bn != 16)) return 1;
+// count > 1: the merged launch of a layer's parity classes (option splitk_multi). The U-Net's bottleneck transposed convs /
+// data gradients are four classes of 1-128 pixels with K = 4 x 1024..2048 each; one class at a time they are four launches of
+// a few K-steps per workgroup plus four finalize passes, and each launch pays its fixed cost (tables, first DMA latency, drain)
+// for 8 MB of weights. Merged, the classes fill the chip with a quarter of the splits each: their tiles count together and
+// the shortest K loop bounds the splits.
+int splitk_plan(const gs_gconv_desc* const* descs, int count, const TileCfg& tc, bool fused) {
+  const gs_gconv_desc* d = descs[0];
+  if (!gs_opt(GS_OPT_SPLITK) || fused || (count > 1 && !gs_opt(GS_OPT_SPLITK_MULTI)) || (tc.bm != 128 && tc.bn != 16)) return 1;
   const long long pix = (long long)d->Dc * d->Hc * d->Wc;
-  const long long blocks = (long long)d->N * ((pix + tc.bm - 1) / tc.bm) * ((d->Co + tc.bn - 1) / tc.bn);
-  const int nk = d->Kp >> 6;
-  const int max_blocks = gs_opt(GS_OPT_SPLITK_MAX_BLOCKS);
-  if (blocks > max_blocks || nk < 16) return 1;
-  const int target = gs_opt(GS_OPT_SPLITK_TARGET);
-  long long splits = target / blocks;
+  const long long blocks = (long long)count * d->N * ((pix + tc.bm - 1) / tc.bm) * ((d->Co + tc.bn - 1) / tc.bn);
+  int nk = d->Kp >> 6;
+  for (int c = 1; c < count; ++c) nk = std::min(nk, descs[c]->Kp >> 6);
+  if (blocks > gs_opt(GS_OPT_SPLITK_MAX_BLOCKS) || nk < 16) return 1;
+  long long splits = gs_opt(GS_OPT_SPLITK_TARGET) / blocks;
   if (splits > nk / 4) splits = nk / 4;
   const long long out_floats = (long long)d->N * d->Do * d->Ho * d->Wo * d->Co;
   while (splits > 1 && splits * out_floats > (64LL << 20)) --splits;     // <= 256 MiB of partial sums
@@ -621,12 +625,7 @@ template <int BM, int BN, int WM, int WN, int NSTAGE>
 int launch(const GConvK& k, int blocks, hipStream_t st) {
   const int lds = NSTAGE * (BM + BN) * 128 + GS_MAX_TAPS * 2 + BM * (k.nh + k.nw) * 2;
   GS_REQUIRE(lds <= 160 * 1024, "gs_gconv_forward: gather tables do not fit in LDS (T=%d)", k.d.T);
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gconv_kernel<BM, BN, WM, WN, NSTAGE>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&gconv_kernel<BM, BN, WM, WN, NSTAGE>>(160 * 1024)) return rc;
   hipLaunchKernelGGL((gconv_kernel<BM, BN, WM, WN, NSTAGE>), dim3(blocks), dim3(WM * WN * 64), lds, st, k);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -646,51 +645,119 @@ int launch_tile(const TileCfg& tc, const GConvK& k, int blocks, hipStream_t st) 
   if (tc.bm == 256) return launch<256, 128, 4, 4, 3>(k, blocks, st);   // 16 waves: best measured (8 and 4 lose)
   return launch<128, 128, 4, 4, 2>(k, blocks, st);
 }
-}  // namespace
+// The split-K launch (k.splits > 1: workgroups write raw sums to k.partial) and its finalize pass, which adds the splits and
+// applies bias / activation / statistics — for every class of a merged launch (k.n_cls > 0) in the one pass.
+int launch_splitk(const TileCfg& tc, const GConvK& k, int blocks, hipStream_t st) {
+  const bool ring = gs_opt(GS_OPT_SPLITK_RING) != 0;
+  if (int rc = tc.bn == 16 ? launch<256, 16, 8, 1, 2>(k, blocks, st)
+             : tc.bn == 64 ? (ring ? launch<128, 64, 4, 2, 4>(k, blocks, st) : launch<128, 64, 4, 2, 2>(k, blocks, st))
+             : ring ? launch<128, 128, 4, 4, 4>(k, blocks, st) : launch<128, 128, 4, 4, 2>(k, blocks, st))
+    return rc;
+  SplitFinK f;
+  f.partial = k.partial; f.bias = k.bias; f.out = k.out; f.stats = k.stats;
+  f.split_stride = k.split_stride; f.splits = k.splits; f.tiles_m = k.tiles_m; f.bm = tc.bm;
+  f.rcp_wc = k.rcp_wc; f.rcp_hc = k.rcp_hc; f.d = k.d; f.n_cls = k.n_cls;
+  for (int c = 0; c < k.n_cls; ++c) {
+    f.cpz[c] = k.cls[c].pz; f.cpy[c] = k.cls[c].py; f.cpx[c] = k.cls[c].px; f.cslot0[c] = k.cls[c].stats_slot0;
+  }
+  const int fblocks = std::max(k.n_cls, 1) * k.d.N * k.tiles_m * ((k.d.Co + 15) / 16);
+  hipLaunchKernelGGL(gconv_splitk_finalize_kernel, dim3(fblocks), dim3(256), 0, st, f);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
-// hconv.hip: halo-resident kernel for narrow stride-1 layers
-int gs_hconv_slots(const gs_gconv_desc* d);
-int gs_pwise_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, void* stream,
-                 int* handled);                   // (pwise.hip)
-int gs_pwise_multi_try(const gs_gconv_desc* const* descs, int count, const void* in, const void* const* w_packs, const float* bias,
-                       void* out, float* stats, void* stream, int* handled);
-int gs_hconv_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
-                 void* stream, int* handled);
-// daxis.hip: streaming kernel for layers whose taps all lie on the row axis (the (k,1,1) half of a separable volume conv)
-int gs_daxis_slots(const gs_gconv_desc* d);
-int gs_daxis_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
-                 void* stream, int* handled);
-// hconvw.hip: halo-resident forward kernel for the wide 3x3 stride-1 layers
-int gs_hconvw_slots(const gs_gconv_desc* d);
-int gs_hconvw_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
-                  const gs_twin* tw, void* stream, int* handled);
-int gs_hconvw_ring(const gs_gconv_desc* d, const void* in, const void* w_pack, void* out, const gs_gconv_fuse* fuse,
-                   const gs_twin* tw, void* stream);
-// hstrip.hip: W-folded k7 boundary convs (vertical taps, <= 64 channels) out of a resident input strip
-int gs_hstrip_slots(const gs_gconv_desc* d);
-int gs_hstrip_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
-                  void* stream, int* handled, const gs_twin* tw);
-// hconvt.hip: the four parity classes of a stride-2 layer out of one halo-resident pass
-int gs_hconvt_pattern(const gs_gconv_desc* const* descs, int count);
-int gs_hconvt_launch(const gs_gconv_desc* const* descs, int pat, const void* in, const void* const* w_packs,
-                     const float* bias, void* out, float* stats, const gs_gconv_fuse* fuse, void* stream,
-                     const gs_twin* tw = nullptr);
-// pconv.hip: persistent form of the 256 x 128 im2col tile for launches of several tiles per CU with a short K loop
-bool gs_pconv_eligible(const GConvK& k, bool fused);
-int gs_pconv_launch(const GConvK& k, bool fused, hipStream_t st);
+// Statistics slots per image when one of the resident kernels takes the class, asked in the order a launch tries them
+// (daxis -> hconv -> hconvw -> hstrip); 0: the class runs on the im2col kernel.
+int resident_slots(const gs_gconv_desc* d) {
+  if (const int s = gs_daxis_slots(d)) return s;
+  if (const int s = gs_hconv_slots(d)) return s;
+  if (const int s = gs_hconvw_slots(d)) return s;
+  return gs_hstrip_slots(d);
+}
+
+// what every im2col launch requires of a class; `who`: the entry point the message names
+int check_desc(const gs_gconv_desc* d, const float* bias, const float* stats, const char* who) {
+  GS_REQUIRE(d->Ci >= 8 && (d->Ci & 7) == 0 && ((d->Ci >> 3) & ((d->Ci >> 3) - 1)) == 0, "%s: Ci=%d must be 8*2^k", who, d->Ci);
+  GS_REQUIRE((d->Co & 7) == 0 && d->Co > 0, "%s: Co=%d must be a multiple of 8", who, d->Co);
+  GS_REQUIRE(d->T >= 1 && d->T <= GS_MAX_TAPS, "%s: T=%d out of range", who, d->T);
+  GS_REQUIRE(d->Kp % 64 == 0 && d->Kp >= d->T * d->Ci, "%s: bad Kp=%d", who, d->Kp);
+  GS_REQUIRE((d->in_cs & 7) == 0 && (d->in_co & 7) == 0 && (d->out_cs & 7) == 0 && (d->out_co & 7) == 0,
+             "%s: channel strides/offsets must be multiples of 8 (16-B accesses)", who);
+  GS_REQUIRE(d->Di >= 1 && d->Do >= 1 && d->Dc >= 1, "%s: depths must be >= 1 (1 for 2-D tensors)", who);
+  GS_REQUIRE((long long)d->Dc * d->Hc * d->Wc < (1 << 24) && (long long)d->Di * d->Hi < 32768 && d->Wi < 32768 &&
+                 (long long)d->Di * d->Hi * d->Wi * d->in_cs * 2 < (1LL << 32),
+             "%s: class extent too large", who);
+  GS_REQUIRE(d->stats_slots == 0 || stats, "%s: stats requested without buffer", who);
+  GS_REQUIRE(!d->accumulate || (d->stats_slots == 0 && d->act == GS_ACT_NONE && !bias),
+             "%s: accumulate excludes bias, activation and statistics", who);
+  return 0;
+}
+
+// Factor d's taps into distinct (depth, row) pairs and distinct columns (every lowering produces a product grid of taps).
+// K: GConvK or GConvCls — the table members share their names, and the arrays being filled give the capacities.
+template <class K>
+int factor_taps(K& k, const gs_gconv_desc* d, const char* who) {
+  constexpr int max_h = (int)sizeof(K::uh), max_w = (int)sizeof(K::uw);
+  static_assert(sizeof(K::ud) == sizeof(K::uh) && sizeof(K::tap_h) == sizeof(K::tap_w), "tap tables of one size");
+  GS_REQUIRE(d->T <= (int)sizeof(K::tap_h), "%s: T=%d out of range", who, d->T);
+  k.nh = k.nw = 0;
+  for (int t = 0; t < d->T; ++t) {
+    int h = 0, w = 0;
+    while (h < k.nh && (k.uh[h] != d->dh[t] || k.ud[h] != d->dd[t])) ++h;
+    if (h == k.nh) {
+      GS_REQUIRE(k.nh < max_h, "%s: more than %d distinct tap (depth,row) pairs", who, max_h);
+      k.ud[k.nh] = d->dd[t];
+      k.uh[k.nh++] = d->dh[t];
+    }
+    while (w < k.nw && k.uw[w] != d->dw[t]) ++w;
+    if (w == k.nw) { GS_REQUIRE(k.nw < max_w, "%s: more than %d distinct tap columns", who, max_w); k.uw[k.nw++] = d->dw[t]; }
+    k.tap_h[t] = (unsigned char)h;
+    k.tap_w[t] = (unsigned char)w;
+  }
+  return 0;
+}
+
+// The kernel arguments a single-class and a merged launch set the same way, from the (first) class d: tensors, tiling, twin
+// batch, and no split-K yet. Left to the caller: the fuse fields, n_cls and the tap tables.
+int fill_args(GConvK& k, const gs_gconv_desc* d, const TileCfg& tc, const void* in, const void* w_pack, const float* bias,
+              void* out, float* stats, const gs_twin* tw, const char* who) {
+  k.in = static_cast<const char*>(in);
+  k.w = static_cast<const char*>(w_pack);
+  k.bias = bias;
+  k.out = static_cast<char*>(out);
+  k.stats = stats;
+  k.zero = static_cast<const char*>(gs_zero_page());
+  GS_REQUIRE(k.zero, "%s: library not initialised (call gs_init)", who);
+  k.tiles_m = (d->Dc * d->Hc * d->Wc + tc.bm - 1) / tc.bm;
+  k.tiles_n = (d->Co + tc.bn - 1) / tc.bn;
+  int sh = 0;
+  while ((8 << sh) < d->Ci) ++sh;
+  k.ci_shift = sh;
+  k.rcp_wc = 1.0f / (float)d->Wc;
+  k.rcp_hc = 1.0f / (float)d->Hc;
+  k.d = *d;
+  k.nsplit = tw ? tw->n_split : 0x7fffffff;
+  k.w_delta = tw ? tw->w_delta : 0;
+  k.bias_delta = tw ? tw->bias_delta : 0;
+  k.splits = 1;
+  k.partial = nullptr;
+  k.split_stride = (long long)d->N * d->Do * d->Ho * d->Wo * d->Co;
+  return 0;
+}
+// split K when the plan says so and the caller's workspace holds the partial sums
+void plan_splitk(GConvK& k, const gs_gconv_desc* const* descs, int count, const TileCfg& tc, bool fused, float* ws,
+                 int64_t ws_floats) {
+  if (!ws) return;
+  const int splits = splitk_plan(descs, count, tc, fused);
+  if (splits > 1 && ws_floats >= (int64_t)splits * k.split_stride) { k.splits = splits; k.partial = ws; }
+}
+}  // namespace
 
 extern "C" int gs_tile_m(const gs_gconv_desc* d) { return pick_tile(d).bm; }
 
 extern "C" int gs_gconv_stat_slots(const gs_gconv_desc* d) {
   if (!d || d->Dc < 1 || d->Hc < 1 || d->Wc < 1) return 0;
-  const int as = gs_daxis_slots(d);
-  if (as) return as;
-  const int hs = gs_hconv_slots(d);
-  if (hs) return hs;
-  const int ws = gs_hconvw_slots(d);
-  if (ws) return ws;
-  const int ss = gs_hstrip_slots(d);
-  if (ss) return ss;
+  if (const int rs = resident_slots(d)) return rs;
   const long long pix = (long long)d->Dc * d->Hc * d->Wc;
   const int bm = pick_tile(d).bm;
   return (int)((pix + bm - 1) / bm);
@@ -708,9 +775,8 @@ extern "C" int gs_gconv_forward(const gs_gconv_desc* d, const void* in, const vo
 // floats of workspace gs_gconv_forward_ws wants for this launch (0: the launch does not split K)
 extern "C" int64_t gs_gconv_splitk_ws_floats(const gs_gconv_desc* d) {
   if (!d || d->Dc < 1 || d->Hc < 1 || d->Wc < 1 || d->Co < 1) return 0;
-  if (gs_daxis_slots(d) || gs_hconv_slots(d) || gs_hconvw_slots(d) || gs_hstrip_slots(d)) return 0;
-  const TileCfg tc = pick_tile(d);
-  const int splits = splitk_plan(d, tc, false);
+  if (resident_slots(d)) return 0;
+  const int splits = splitk_plan(&d, 1, pick_tile(d), false);
   return splits > 1 ? (int64_t)splits * d->N * d->Do * d->Ho * d->Wo * d->Co : 0;
 }
 
@@ -733,6 +799,9 @@ extern "C" int gs_gconv_twin_native(const gs_gconv_desc* d, const gs_gconv_fuse*
     if (fuse->fold > 0 && d->Do == fuse->Dy && d->Ho == fuse->Hy && d->Wo == fuse->Wy) return gs_gconv_ring_slots(d) > 0;
     return gs_opt(GS_OPT_GCONV_TWIN) != 0;        // padded-domain fused launch: always the im2col kernel (no split-K there)
   }
+  // Not resident_slots(): the question is not whether a resident kernel runs the class but whether the kernel that runs it has
+  // a twin form, and the answer differs per kernel — daxis and hconv have none, hconvw has one, and hstrip is asked only after
+  // `accumulate`, in the order a twin launch meets them (gconv_forward_impl with tw tries hconvw, then hstrip).
   if (gs_daxis_slots(d) || gs_hconv_slots(d)) return 0;
   if (gs_hconvw_slots(d) > 0) return 1;
   // the im2col kernel picks the weight set per tile (tiles never straddle images) — unless the halves would run split-K (few
@@ -742,7 +811,8 @@ extern "C" int gs_gconv_twin_native(const gs_gconv_desc* d, const gs_gconv_fuse*
   if (!gs_opt(GS_OPT_GCONV_TWIN)) return 0;
   gs_gconv_desc half = *d;
   half.N = d->N / 2;
-  return splitk_plan(&half, pick_tile(&half), false) <= 1;
+  const gs_gconv_desc* hp = &half;
+  return splitk_plan(&hp, 1, pick_tile(hp), false) <= 1;
 }
 extern "C" int gs_gconv_forward_twin(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out,
                                      float* stats, const gs_gconv_fuse* fuse, const gs_twin* tw, void* stream) {
@@ -774,21 +844,9 @@ static int gconv_forward_fused_impl(const gs_gconv_desc* d, const void* in, cons
 static int gconv_forward_impl(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out,
                               float* stats, const gs_gconv_fuse* fuse, float* ws, int64_t ws_floats, void* stream,
                               const gs_twin* tw) {
+  const char* const who = "gs_gconv_forward";
   GS_REQUIRE(d && in && w_pack && out, "gs_gconv_forward: null argument");
-  GS_REQUIRE(d->Ci >= 8 && (d->Ci & 7) == 0 && ((d->Ci >> 3) & ((d->Ci >> 3) - 1)) == 0,
-             "gs_gconv_forward: Ci=%d must be 8*2^k", d->Ci);
-  GS_REQUIRE((d->Co & 7) == 0 && d->Co > 0, "gs_gconv_forward: Co=%d must be a multiple of 8", d->Co);
-  GS_REQUIRE(d->T >= 1 && d->T <= GS_MAX_TAPS, "gs_gconv_forward: T=%d out of range", d->T);
-  GS_REQUIRE(d->Kp % 64 == 0 && d->Kp >= d->T * d->Ci, "gs_gconv_forward: bad Kp=%d", d->Kp);
-  GS_REQUIRE((d->in_cs & 7) == 0 && (d->in_co & 7) == 0 && (d->out_cs & 7) == 0 && (d->out_co & 7) == 0,
-             "gs_gconv_forward: channel strides/offsets must be multiples of 8 (16-B accesses)");
-  GS_REQUIRE(d->Di >= 1 && d->Do >= 1 && d->Dc >= 1, "gs_gconv_forward: depths must be >= 1 (1 for 2-D tensors)");
-  GS_REQUIRE((long long)d->Dc * d->Hc * d->Wc < (1 << 24) && (long long)d->Di * d->Hi < 32768 && d->Wi < 32768 &&
-                 (long long)d->Di * d->Hi * d->Wi * d->in_cs * 2 < (1LL << 32),
-             "gs_gconv_forward: class extent too large");
-  GS_REQUIRE(d->stats_slots == 0 || stats, "gs_gconv_forward: stats requested without buffer");
-  GS_REQUIRE(!d->accumulate || (d->stats_slots == 0 && d->act == GS_ACT_NONE && !bias),
-             "gs_gconv_forward: accumulate excludes bias, activation and statistics");
+  if (int rc = check_desc(d, bias, stats, who)) return rc;
   if (!fuse) {
     int handled = 0;
     if (!tw) {
@@ -807,65 +865,16 @@ static int gconv_forward_impl(const gs_gconv_desc* d, const void* in, const void
   GS_REQUIRE(!tw || !ws, "gs_gconv_forward_twin: the split-K launch has no twin form");
   const TileCfg tc = pick_tile(d);
   GConvK k;
+  if (int rc = fill_args(k, d, tc, in, w_pack, bias, out, stats, tw, who)) return rc;
   if (fuse) k.f = *fuse; else k.f = gs_gconv_fuse{};
   k.fuse_slots = (int)(((long long)d->Dc * d->Hc * d->Wc + tc.bm - 1) / tc.bm);
-  k.in = static_cast<const char*>(in);
-  k.w = static_cast<const char*>(w_pack);
-  k.bias = bias;
-  k.out = static_cast<char*>(out);
-  k.stats = stats;
-  k.zero = static_cast<const char*>(gs_zero_page());
-  GS_REQUIRE(k.zero, "gs_gconv_forward: library not initialised (call gs_init)");
-  k.tiles_m = (d->Dc * d->Hc * d->Wc + tc.bm - 1) / tc.bm;
-  k.tiles_n = (d->Co + tc.bn - 1) / tc.bn;
-  int sh = 0;
-  while ((8 << sh) < d->Ci) ++sh;
-  k.ci_shift = sh;
-  k.rcp_wc = 1.0f / (float)d->Wc;
-  k.rcp_hc = 1.0f / (float)d->Hc;
-  k.d = *d;
-  k.nh = k.nw = 0;
-  for (int t = 0; t < d->T; ++t) {
-    int h = 0, w = 0;
-    while (h < k.nh && (k.uh[h] != d->dh[t] || k.ud[h] != d->dd[t])) ++h;
-    if (h == k.nh) {
-      GS_REQUIRE(k.nh < 64, "gs_gconv_forward: more than 64 distinct tap (depth,row) pairs");
-      k.ud[k.nh] = d->dd[t];
-      k.uh[k.nh++] = d->dh[t];
-    }
-    while (w < k.nw && k.uw[w] != d->dw[t]) ++w;
-    if (w == k.nw) { GS_REQUIRE(k.nw < 16, "gs_gconv_forward: more than 16 distinct tap columns"); k.uw[k.nw++] = d->dw[t]; }
-    k.tap_h[t] = (unsigned char)h;
-    k.tap_w[t] = (unsigned char)w;
-  }
   k.n_cls = 0;
-  k.nsplit = tw ? tw->n_split : 0x7fffffff;
-  k.w_delta = tw ? tw->w_delta : 0;
-  k.bias_delta = tw ? tw->bias_delta : 0;
-  k.splits = 1;
-  k.partial = nullptr;
-  k.split_stride = (long long)d->N * d->Do * d->Ho * d->Wo * d->Co;
-  if (ws) {
-    const int splits = splitk_plan(d, tc, fuse != nullptr);
-    if (splits > 1 && ws_floats >= (int64_t)splits * k.split_stride) { k.splits = splits; k.partial = ws; }
-  }
+  if (int rc = factor_taps(k, d, who)) return rc;
+  plan_splitk(k, &d, 1, tc, fuse != nullptr, ws, ws_floats);
   const long long blocks = (long long)d->N * k.tiles_m * k.tiles_n * k.splits;
   GS_REQUIRE(blocks > 0 && blocks < (1LL << 31), "gs_gconv_forward: bad grid %lld", blocks);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (k.splits > 1) {
-    int rc = tc.bn == 16 ? launch<256, 16, 8, 1, 2>(k, (int)blocks, st)
-           : tc.bn == 64 ? (gs_opt(GS_OPT_SPLITK_RING) ? launch<128, 64, 4, 2, 4>(k, (int)blocks, st) : launch<128, 64, 4, 2, 2>(k, (int)blocks, st))
-           : gs_opt(GS_OPT_SPLITK_RING) ? launch<128, 128, 4, 4, 4>(k, (int)blocks, st) : launch<128, 128, 4, 4, 2>(k, (int)blocks, st);
-    if (rc) return rc;
-    SplitFinK f;
-    f.partial = ws; f.bias = bias; f.out = static_cast<char*>(out); f.stats = stats;
-    f.split_stride = k.split_stride; f.splits = k.splits; f.tiles_m = k.tiles_m; f.bm = tc.bm;
-    f.rcp_wc = k.rcp_wc; f.rcp_hc = k.rcp_hc; f.d = *d; f.n_cls = 0;
-    const int fblocks = d->N * k.tiles_m * ((d->Co + 15) / 16);
-    hipLaunchKernelGGL(gconv_splitk_finalize_kernel, dim3(fblocks), dim3(256), 0, st, f);
-    GS_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
+  if (k.splits > 1) return launch_splitk(tc, k, (int)blocks, st);
   if (tc.bm == 256 && tc.bn == 128 && gs_pconv_eligible(k, fuse != nullptr)) return gs_pconv_launch(k, fuse != nullptr, st);
   return launch_tile(tc, k, (int)blocks, st);
 }
@@ -921,7 +930,9 @@ extern "C" int gs_gconv_forward_multi_twin(const gs_gconv_desc* const* descs, in
 // PatchGAN gradients are 64-256 workgroups of a few K-steps per launch, paid four times with a split-K pass behind each
 // (profiles/r02_conv_table.txt: 100-250 TFLOP/s). Merged, the classes are one grid: fixed costs once, 4x the workgroups.
 namespace {
-// classes of one shape (even extents), short tap lists, at least two of them: they can share a grid
+// classes of one shape (even extents), short tap lists, at least two of them: they can share a grid.
+// Not resident_slots(): only hconv and hconvw are asked. daxis and hstrip take a class only when it is the whole output
+// (Hc == Ho, Wc == Wo, phase 0), which the parity classes of a strided layer never are.
 bool multi_mergeable(const gs_gconv_desc* const* descs, int count) {
   const gs_gconv_desc* d0 = descs[0];
   bool merge = count >= 2 && count <= GS_MULTI_MAX_CLS && gs_opt(GS_OPT_GCONV_MULTI) != 0;
@@ -936,24 +947,7 @@ bool multi_mergeable(const gs_gconv_desc* const* descs, int count) {
   }
   return merge;
 }
-// Split-K plan of the merged launch: the U-Net's bottleneck transposed convs / data gradients are four classes of 1-128
-// pixels with K = 4 x 1024..2048 each; one class at a time they are four launches of a few K-steps per workgroup plus four
-// finalize passes, and each launch pays its fixed cost (tables, first DMA latency, drain) for 8 MB of weights. Merged, the
-// classes fill the chip with a quarter of the splits each. Returns 1 = no split.
-int splitk_plan_multi(const gs_gconv_desc* const* descs, int count, const TileCfg& tc) {
-  const gs_gconv_desc* d = descs[0];
-  if (!gs_opt(GS_OPT_SPLITK) || !gs_opt(GS_OPT_SPLITK_MULTI) || (tc.bm != 128 && tc.bn != 16)) return 1;
-  const long long pix = (long long)d->Dc * d->Hc * d->Wc;
-  const long long blocks = (long long)count * d->N * ((pix + tc.bm - 1) / tc.bm) * ((d->Co + tc.bn - 1) / tc.bn);
-  int nk = descs[0]->Kp >> 6;
-  for (int c = 1; c < count; ++c) nk = std::min(nk, descs[c]->Kp >> 6);
-  if (blocks > gs_opt(GS_OPT_SPLITK_MAX_BLOCKS) || nk < 16) return 1;
-  long long splits = gs_opt(GS_OPT_SPLITK_TARGET) / blocks;
-  if (splits > nk / 4) splits = nk / 4;
-  const long long out_floats = (long long)d->N * d->Do * d->Ho * d->Wo * d->Co;
-  while (splits > 1 && splits * out_floats > (64LL << 20)) --splits;     // <= 256 MiB of partial sums
-  return splits < 2 ? 1 : (int)splits;
-}
+
 int gconv_forward_multi_impl(const gs_gconv_desc* const* descs, int32_t count, const void* in, const void* const* w_packs,
                              const float* bias, void* out, float* stats, float* ws, int64_t ws_floats, void* stream);
 }  // namespace
@@ -972,7 +966,7 @@ extern "C" int64_t gs_gconv_multi_splitk_ws_floats(const gs_gconv_desc* const* d
     if (!descs[c] || descs[c]->Dc < 1 || descs[c]->Hc < 1 || descs[c]->Wc < 1 || descs[c]->Co < 1) return 0;
   if (!multi_mergeable(descs, count) || gs_hconvt_pattern(descs, count) >= 0) return 0;
   const gs_gconv_desc* d = descs[0];
-  const int splits = splitk_plan_multi(descs, count, pick_tile(d));
+  const int splits = splitk_plan(descs, count, pick_tile(d), false);
   return splits > 1 ? (int64_t)splits * d->N * d->Do * d->Ho * d->Wo * d->Co : 0;
 }
 
@@ -988,6 +982,7 @@ extern "C" int gs_gconv_forward_multi_ws(const gs_gconv_desc* const* descs, int3
 namespace {
 int gconv_forward_multi_impl(const gs_gconv_desc* const* descs, int32_t count, const void* in, const void* const* w_packs,
                              const float* bias, void* out, float* stats, float* ws, int64_t ws_floats, void* stream) {
+  const char* const who = "gs_gconv_forward_multi";
   GS_REQUIRE(descs && w_packs && count >= 1 && in && out, "gs_gconv_forward_multi: null argument");
   for (int c = 0; c < count; ++c) GS_REQUIRE(descs[c] && w_packs[c], "gs_gconv_forward_multi: null class %d", c);
   if (!multi_mergeable(descs, count)) {      // classes of different shapes (odd extents), long tap lists, a single class: one launch each
@@ -995,21 +990,9 @@ int gconv_forward_multi_impl(const gs_gconv_desc* const* descs, int32_t count, c
       if (int rc = gconv_forward_impl(descs[c], in, w_packs[c], bias, out, stats, nullptr, ws, ws_floats, stream)) return rc;
     return 0;
   }
-  // validate through the single-class checks, then build the shared arguments from class 0
-  const gs_gconv_desc* d = descs[0];
-  GS_REQUIRE(d->Ci >= 8 && (d->Ci & 7) == 0 && ((d->Ci >> 3) & ((d->Ci >> 3) - 1)) == 0,
-             "gs_gconv_forward_multi: Ci=%d must be 8*2^k", d->Ci);
-  GS_REQUIRE((d->Co & 7) == 0 && d->Co > 0, "gs_gconv_forward_multi: Co=%d must be a multiple of 8", d->Co);
-  GS_REQUIRE((d->in_cs & 7) == 0 && (d->in_co & 7) == 0 && (d->out_cs & 7) == 0 && (d->out_co & 7) == 0,
-             "gs_gconv_forward_multi: channel strides/offsets must be multiples of 8 (16-B accesses)");
-  GS_REQUIRE(d->Di >= 1 && d->Do >= 1 && d->Dc >= 1, "gs_gconv_forward_multi: depths must be >= 1");
-  GS_REQUIRE((long long)d->Dc * d->Hc * d->Wc < (1 << 24) && (long long)d->Di * d->Hi < 32768 && d->Wi < 32768 &&
-                 (long long)d->Di * d->Hi * d->Wi * d->in_cs * 2 < (1LL << 32),
-             "gs_gconv_forward_multi: class extent too large");
-  GS_REQUIRE(d->stats_slots == 0 || stats, "gs_gconv_forward_multi: stats requested without buffer");
+  // the classes differ in taps, Kp, phase and statistics slot only (multi_mergeable): the single-class checks on each
   for (int c = 0; c < count; ++c)
-    GS_REQUIRE(descs[c]->Kp % 64 == 0 && descs[c]->Kp >= descs[c]->T * descs[c]->Ci, "gs_gconv_forward_multi: bad Kp=%d",
-               descs[c]->Kp);
+    if (int rc = check_desc(descs[c], bias, stats, who)) return rc;
   {                                                       // k2 stride-2 volume layers: 8 one-tap classes (pwise.hip)
     int handled = 0;
     if (int rc = gs_pwise_multi_try(descs, count, in, w_packs, bias, out, stats, stream, &handled)) return rc;
@@ -1020,75 +1003,28 @@ int gconv_forward_multi_impl(const gs_gconv_desc* const* descs, int32_t count, c
     if (pat >= 0) return gs_hconvt_launch(descs, pat, in, w_packs, bias, out, stats, nullptr, stream);
   }
   // the tile one class alone would get: the statistics slots (gs_gconv_stat_slots) are counted per class from it
+  const gs_gconv_desc* d = descs[0];
   const TileCfg tc = pick_tile(d);
-  static GConvK k;      // ~3 KB: filled per call, passed by value to the launch
+  GConvK k;      // ~3 KB, passed by value to the launch (a plain local: autograd issues launches from its own host threads)
+  if (int rc = fill_args(k, d, tc, in, w_packs[0], bias, out, stats, nullptr, who)) return rc;   // (no twin form of this launch)
   k.f = gs_gconv_fuse{};
   k.fuse_slots = 0;
-  k.in = static_cast<const char*>(in);
-  k.w = static_cast<const char*>(w_packs[0]);
-  k.bias = bias;
-  k.out = static_cast<char*>(out);
-  k.stats = stats;
-  k.zero = static_cast<const char*>(gs_zero_page());
-  GS_REQUIRE(k.zero, "gs_gconv_forward_multi: library not initialised (call gs_init)");
-  k.tiles_m = (d->Dc * d->Hc * d->Wc + tc.bm - 1) / tc.bm;
-  k.tiles_n = (d->Co + tc.bn - 1) / tc.bn;
-  int sh = 0;
-  while ((8 << sh) < d->Ci) ++sh;
-  k.ci_shift = sh;
-  k.rcp_wc = 1.0f / (float)d->Wc;
-  k.rcp_hc = 1.0f / (float)d->Hc;
-  k.d = *d;
   k.nh = k.nw = 0;
-  k.nsplit = 0x7fffffff;     // (no twin form of the merged class launch)
-  k.w_delta = k.bias_delta = 0;
   k.n_cls = count;
   for (int c = 0; c < count; ++c) {
     const gs_gconv_desc* dc = descs[c];
     GConvCls& cl = k.cls[c];
-    GS_REQUIRE(dc->Kp % 64 == 0 && dc->Kp >= dc->T * dc->Ci, "gs_gconv_forward_multi: bad Kp=%d", dc->Kp);
     cl.w_off = static_cast<const char*>(w_packs[c]) - k.w;
     cl.T = dc->T; cl.Kp = dc->Kp; cl.pz = dc->pz; cl.py = dc->py; cl.px = dc->px; cl.stats_slot0 = dc->stats_slot0;
-    cl.nh = cl.nw = 0;
-    for (int t = 0; t < dc->T; ++t) {
-      int h = 0, w = 0;
-      while (h < cl.nh && (cl.uh[h] != dc->dh[t] || cl.ud[h] != dc->dd[t])) ++h;
-      if (h == cl.nh) { cl.ud[cl.nh] = dc->dd[t]; cl.uh[cl.nh++] = dc->dh[t]; }
-      while (w < cl.nw && cl.uw[w] != dc->dw[t]) ++w;
-      if (w == cl.nw) cl.uw[cl.nw++] = dc->dw[t];
-      cl.tap_h[t] = (unsigned char)h;
-      cl.tap_w[t] = (unsigned char)w;
-    }
+    if (int rc = factor_taps(cl, dc, who)) return rc;
     if (cl.nh > k.nh) k.nh = cl.nh;         // LDS gather tables are sized for the largest class
     if (cl.nw > k.nw) k.nw = cl.nw;
   }
-  k.splits = 1;
-  k.partial = nullptr;
-  k.split_stride = (long long)d->N * d->Do * d->Ho * d->Wo * d->Co;
-  if (ws) {
-    const int splits = splitk_plan_multi(descs, count, tc);
-    if (splits > 1 && ws_floats >= (int64_t)splits * k.split_stride) { k.splits = splits; k.partial = ws; }
-  }
+  plan_splitk(k, descs, count, tc, false, ws, ws_floats);
   const long long blocks = (long long)count * d->N * k.tiles_m * k.tiles_n * k.splits;
   GS_REQUIRE(blocks > 0 && blocks < (1LL << 31), "gs_gconv_forward_multi: bad grid %lld", blocks);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (k.splits > 1) {
-    int rc = tc.bn == 16 ? launch<256, 16, 8, 1, 2>(k, (int)blocks, st)
-           : tc.bn == 64 ? (gs_opt(GS_OPT_SPLITK_RING) ? launch<128, 64, 4, 2, 4>(k, (int)blocks, st) : launch<128, 64, 4, 2, 2>(k, (int)blocks, st))
-           : gs_opt(GS_OPT_SPLITK_RING) ? launch<128, 128, 4, 4, 4>(k, (int)blocks, st) : launch<128, 128, 4, 4, 2>(k, (int)blocks, st);
-    if (rc) return rc;
-    SplitFinK f;
-    f.partial = ws; f.bias = bias; f.out = static_cast<char*>(out); f.stats = stats;
-    f.split_stride = k.split_stride; f.splits = k.splits; f.tiles_m = k.tiles_m; f.bm = tc.bm;
-    f.rcp_wc = k.rcp_wc; f.rcp_hc = k.rcp_hc; f.d = *d; f.n_cls = count;
-    for (int c = 0; c < count; ++c) {
-      f.cpz[c] = descs[c]->pz; f.cpy[c] = descs[c]->py; f.cpx[c] = descs[c]->px; f.cslot0[c] = descs[c]->stats_slot0;
-    }
-    const int fblocks = count * d->N * k.tiles_m * ((d->Co + 15) / 16);
-    hipLaunchKernelGGL(gconv_splitk_finalize_kernel, dim3(fblocks), dim3(256), 0, st, f);
-    GS_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
+  if (k.splits > 1) return launch_splitk(tc, k, (int)blocks, st);
   return launch_tile(tc, k, (int)blocks, st);
 }
 }  // namespace

@@ -42,3 +42,7 @@ struct GConvK {
   gs_gconv_desc d;
 };
 
+// pconv.hip: persistent form of the 256 x 128 im2col tile for launches of several tiles per CU with a short K loop.
+// _eligible: does this single-class launch without split-K run there (k.tiles_m / tiles_n / nh / nw filled in by the caller)?
+bool gs_pconv_eligible(const GConvK& k, bool fused);
+int gs_pconv_launch(const GConvK& k, bool fused, hipStream_t st);

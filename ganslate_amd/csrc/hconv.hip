@@ -11,7 +11,7 @@
 //   D[co][voxel] += W[co][(tap, ci)] * X[voxel + off(tap)][ci],  v_mfma_f32_16x16x32_bf16, fp32 accumulate.
 // Same epilogue contract as gconv_kernel: bias, per-workgroup InstanceNorm partial sums (one slot per box), activation,
 // optional accumulate-into (additive-coupling gradient joins), channel-slice output views.
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -672,12 +672,7 @@ HPlan plan(const gs_gconv_desc* d) {
 
 template <int TI, int CC, int NW>
 int launch_h(const HConvK& k, int blocks, int cog, int lds, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconv_kernel<TI, CC, NW>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 110 * 1024));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hconv_kernel<TI, CC, NW>>(110 * 1024)) return rc;
   hipLaunchKernelGGL((hconv_kernel<TI, CC, NW>), dim3(blocks, cog), dim3(NW * 64), lds, st, k);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -685,10 +680,6 @@ int launch_h(const HConvK& k, int blocks, int cog, int lds, hipStream_t st) {
 }  // namespace
 
 // number of partial-statistics slots per image this class writes if it runs on the halo kernel, 0 if it does not
-int gs_hconv5_slots(const gs_gconv_desc* d);
-int gs_hconv5_try(const gs_gconv_desc* d, const void* in, const void* w_pack, const float* bias, void* out, float* stats,
-                  void* stream, int* handled);
-
 int gs_hconv_slots(const gs_gconv_desc* d) {
   if (const int s5 = gs_hconv5_slots(d)) return s5;       // the 16 -> 16 k5 volume layers: hconv5.hip
   const HPlan h = plan(d);
@@ -731,19 +722,11 @@ int gs_hconv_try(const gs_gconv_desc* d, const void* in, const void* w_pack, con
     const long long gmax = cus / h.cog > 0 ? cus / h.cog : 1;  // one workgroup per CU (channel groups side by side)
     const long long per = (blocks + gmax - 1) / gmax;          // boxes per workgroup: equal shares
     const int groups = (int)((blocks + per - 1) / per);
-    static bool configured2 = false;
-    if (!configured2) {
-      GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconv2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      configured2 = true;
-    }
     if (h.TI == 1) {
-      static bool configured1 = false;
-      if (!configured1) {
-        GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconv2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured1 = true;
-      }
+      if (int rc = gs_allow_lds<&hconv2_kernel<1>>(160 * 1024)) return rc;
       hipLaunchKernelGGL((hconv2_kernel<1>), dim3(groups, h.cog), dim3(512), h.lds, st, k);
     } else {
+      if (int rc = gs_allow_lds<&hconv2_kernel<2>>(160 * 1024)) return rc;
       hipLaunchKernelGGL((hconv2_kernel<2>), dim3(groups, h.cog), dim3(512), h.lds, st, k);
     }
     GS_CHECK_HIP(hipGetLastError());

@@ -21,7 +21,7 @@
 // a fragment feeds is a compile-time register).
 // Epilogue contract of hconv_kernel: bias, per-box InstanceNorm partial sums (one slot per box), activation, accumulate-into,
 // channel-slice views.
-#include "common.hpp"
+#include "internal.hpp"
 #include <type_traits>
 #include <utility>
 
@@ -428,11 +428,7 @@ int gs_hconv5_try(const gs_gconv_desc* d, const void* in, const void* w_pack, co
   const int per = (k.nwork + cus - 1) / cus;               // persistent: equal shares of whole segments
   const int grid = (k.nwork + per - 1) / per;
   constexpr int lds = HALO_BYTES + 512 + 4 * 16 * 2 * 4;
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconv5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hconv5_kernel>(lds)) return rc;
   *handled = 1;
   hipLaunchKernelGGL(hconv5_kernel, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), k);
   GS_CHECK_HIP(hipGetLastError());

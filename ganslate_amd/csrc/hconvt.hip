@@ -12,7 +12,7 @@
 // half-K-step sets ahead of the MFMAs with counted waits (common.hpp). Epilogue: bias, statistics (one slot per box over
 // all classes, the rest of the layer's slots zeroed), activation, class by class through an LDS slab into 128-B stores at
 // out[2i + py][2j + px].
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -500,6 +500,14 @@ bool window(const gs_gconv_desc* const* descs, int* lo) {
     }
   return hi[0] - lo[0] <= 2 && hi[1] - lo[1] <= 2;
 }
+
+template <int PAT, bool FUSED = false, bool PLAIN = false>
+int launch_t(const HConvTK& k, unsigned blocks, int lds, hipStream_t st) {
+  if (int rc = gs_allow_lds<&hconvt_kernel<PAT, FUSED, PLAIN>>(lds)) return rc;
+  hipLaunchKernelGGL((hconvt_kernel<PAT, FUSED, PLAIN>), dim3(blocks), dim3(512), lds, st, k);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 }  // namespace
 
 // pattern of the classes (0: 1/2/2/4 taps, 1: 4/4/4/4) when the layer runs here, -1 when it does not
@@ -577,39 +585,10 @@ int gs_hconvt_launch(const gs_gconv_desc* const* descs, int pat, const void* in,
   if (gs_opt(GS_OPT_HCONVT_PERSIST) && tiles > hconvt_cus() && k.tiles_n <= hconvt_cus())
     blocks = hconvt_cus() / k.tiles_n * k.tiles_n;
   const int lds = 3 * 2 * 64 * 128 + 2 * ((18 * 18 * 10 + 63) / 64) * 1024 + 1024 + 2 * 64 * 4;
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvt_kernel<0>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvt_kernel<1>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    configured = true;
-  }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (fuse) {
-    static bool configured_f = false;
-    if (!configured_f) {
-      GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvt_kernel<0, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvt_kernel<1, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      configured_f = true;
-    }
-    if (pat == 0) hipLaunchKernelGGL((hconvt_kernel<0, true>), dim3((unsigned)blocks), dim3(512), lds, st, k);
-    else hipLaunchKernelGGL((hconvt_kernel<1, true>), dim3((unsigned)blocks), dim3(512), lds, st, k);
-  } else if (!bias && d->stats_slots == 0 && d->act == GS_ACT_NONE) {
-    static bool configured_p = false;
-    if (!configured_p) {
-      GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvt_kernel<0, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvt_kernel<1, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      configured_p = true;
-    }
-    if (pat == 0) hipLaunchKernelGGL((hconvt_kernel<0, false, true>), dim3((unsigned)blocks), dim3(512), lds, st, k);
-    else hipLaunchKernelGGL((hconvt_kernel<1, false, true>), dim3((unsigned)blocks), dim3(512), lds, st, k);
-  } else if (pat == 0) hipLaunchKernelGGL((hconvt_kernel<0>), dim3((unsigned)blocks), dim3(512), lds, st, k);
-  else hipLaunchKernelGGL((hconvt_kernel<1>), dim3((unsigned)blocks), dim3(512), lds, st, k);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
+  const unsigned nb = (unsigned)blocks;
+  if (fuse) return pat == 0 ? launch_t<0, true>(k, nb, lds, st) : launch_t<1, true>(k, nb, lds, st);
+  if (!bias && d->stats_slots == 0 && d->act == GS_ACT_NONE)
+    return pat == 0 ? launch_t<0, false, true>(k, nb, lds, st) : launch_t<1, false, true>(k, nb, lds, st);
+  return pat == 0 ? launch_t<0>(k, nb, lds, st) : launch_t<1>(k, nb, lds, st);
 }

@@ -9,7 +9,7 @@
 // rowbase(j) + tapoff(t); a 144-byte voxel pitch makes 16 consecutive voxels cover all 64 banks.
 // Tile 256 pixels (one 16x16 box) x 128 output channels, 16 waves as 4 x 4, 3-stage weight ring, same epilogue
 // contract as gconv_kernel (bias, one statistics slot per box, activation, dense or sliced output).
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -712,12 +712,7 @@ int gs_hconvw_try(const gs_gconv_desc* d, const void* in, const void* w_pack, co
   k.d = *d;
   k.f = gs_gconv_fuse{};
   const int lds = 160 * 1024;
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvw_kernel<9>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hconvw_kernel<9>>(lds)) return rc;
   *handled = 1;
   hipLaunchKernelGGL((hconvw_kernel<9>), dim3((unsigned)hconvw_grid(d->N, k.tiles_m * k.tiles_n, k.chunks)), dim3(1024), lds,
                      static_cast<hipStream_t>(stream), k);
@@ -769,12 +764,7 @@ int gs_hconvw_ring(const gs_gconv_desc* d, const void* in, const void* w_pack, v
   k.ntiles = (int)blocks;
   hconvw_twin(k, tw);
   const int lds = 160 * 1024;
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hconvw_kernel<9, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hconvw_kernel<9, true>>(lds)) return rc;
   hipLaunchKernelGGL((hconvw_kernel<9, true>), dim3((unsigned)hconvw_grid(d->N, k.tiles_m * k.tiles_n, k.chunks)), dim3(1024), lds,
                      static_cast<hipStream_t>(stream), k);
   GS_CHECK_HIP(hipGetLastError());

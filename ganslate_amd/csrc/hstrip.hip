@@ -10,7 +10,7 @@
 // 4 waves x (64 pixels x Co), 256-pixel tiles (32 x 8), <= 78 KB of LDS: two workgroups per CU overlap each other's
 // load / compute / store phases. Epilogue contract of gconv_kernel: bias, one statistics slot per tile, activation,
 // dense or sliced output.
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -440,24 +440,14 @@ Plan plan(const gs_gconv_desc* d) {
 
 template <int CI, int CO>
 int launch_s(const HStripK& k, long long blocks, int lds, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hstrip_kernel<CI, CO>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hstrip_kernel<CI, CO>>(80 * 1024)) return rc;
   hipLaunchKernelGGL((hstrip_kernel<CI, CO>), dim3((unsigned)blocks), dim3(256), lds, st, k);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
 template <int CI, int CO, int TRr>
 int launch_r(const HStripK& k, long long groups, int lds, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hstripr_kernel<CI, CO, TRr>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hstripr_kernel<CI, CO, TRr>>(80 * 1024)) return rc;
   hipLaunchKernelGGL((hstripr_kernel<CI, CO, TRr>), dim3((unsigned)groups), dim3(256), lds, st, k);
   GS_CHECK_HIP(hipGetLastError());
   return 0;

@@ -11,7 +11,7 @@
 // v_mfma_f32_16x16x32_bf16. Both operands are pixel-major, so fragments come from ds_read_b64_tr_b16: the 8 pixels of a
 // box row shifted by a tap are 8 consecutive halo voxels. The dense fragment is shared by the 16 taps of a wave, so the
 // loop issues 2 transpose reads per MFMA; atomics happen once per workgroup at the end.
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 #include <type_traits>
 
@@ -791,12 +791,7 @@ __global__ __launch_bounds__(512) void hwgrad2_kernel(const HWGradK p) {
 namespace {
 template <int TI, int TPW>
 int launch_hw(const HWGradK& k, dim3 grid, int lds, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hwgrad_kernel<TI, TPW>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&hwgrad_kernel<TI, TPW>>(96 * 1024)) return rc;
   hipLaunchKernelGGL((hwgrad_kernel<TI, TPW>), grid, dim3(512), lds, st, k);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -806,9 +801,6 @@ int launch_hw(const HWGradK& k, dim3 grid, int lds, hipStream_t st) {
 // returns 0 and sets *handled when the layer ran here; *handled = 0 -> the caller falls back to wgrad_kernel
 // ws != nullptr: partial sums go to slabs of ws (see HWGradK) and *handled returns the number of slabs written (the caller
 // runs the reduction); plan_only: nothing is launched, *handled is what a launch would return.
-int gs_hwgrad_try2(const gs_wgrad_desc* d, const void* a, const void* g, const void* a2, const void* g2, float* dw,
-                   float* ws, int plan_only, void* stream, int* handled, const gs_twin* tw);
-
 // a2/g2 != nullptr: a second operand pair of the same layer (only the wide kernel merges; otherwise *handled stays 0).
 // tw != nullptr: twin batch (only the wide kernel takes it; *handled then is the number of slabs PER NETWORK, the second
 // network's slabs follow the first's)
@@ -890,16 +882,11 @@ int gs_hwgrad_try2(const gs_wgrad_desc* d, const void* a, const void* g, const v
       k.nimg = nimg;
       k.gsplit = (int)groups;
       k.dw_delta = tw ? tw->dw_delta / 4 : 0;
-      static bool configured = false;
-      if (!configured) {
-        GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hwgrad_wide_kernel<9>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured = true;
-      }
       k.ws = ws;
       k.ws_stride = ws_stride;
       *handled = ws || plan_only ? (int)groups : 1;
-      if (plan_only) return 0;
+      if (plan_only) return 0;                           // (a plan touches no device: the attribute is the launch's business)
+      if (int rc = gs_allow_lds<&hwgrad_wide_kernel<9>>(160 * 1024)) return rc;
       hipLaunchKernelGGL((hwgrad_wide_kernel<9>), dim3((unsigned)(groups * (tw ? 2 : 1)), (unsigned)tiles), dim3(512), lds,
                          static_cast<hipStream_t>(stream), k);
       GS_CHECK_HIP(hipGetLastError());
@@ -955,12 +942,7 @@ int gs_hwgrad_try2(const gs_wgrad_desc* d, const void* a, const void* g, const v
       k.ws_stride = ws_stride;
       *handled = ws || plan_only ? (int)groups : 1;
       if (plan_only) return 0;
-      static bool configured = false;
-      if (!configured) {
-        GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hwgrad_ft_kernel<8>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        configured = true;
-      }
+      if (int rc = gs_allow_lds<&hwgrad_ft_kernel<8>>(96 * 1024)) return rc;
       hipLaunchKernelGGL((hwgrad_ft_kernel<8>), dim3((unsigned)(groups * (tw ? 2 : 1))), dim3(512), lds,
                          static_cast<hipStream_t>(stream), k);
       GS_CHECK_HIP(hipGetLastError());
@@ -1022,18 +1004,11 @@ int gs_hwgrad_try2(const gs_wgrad_desc* d, const void* a, const void* g, const v
     if (plan_only) return 0;
     const dim3 grid2((unsigned)groups2, (unsigned)per_y);
     hipStream_t st2 = static_cast<hipStream_t>(stream);
-    static bool configured2[2] = {false, false};
     if (TI == 1) {
-      if (!configured2[0]) {
-        GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hwgrad2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured2[0] = true;
-      }
+      if (int rc = gs_allow_lds<&hwgrad2_kernel<1>>(160 * 1024)) return rc;
       hipLaunchKernelGGL((hwgrad2_kernel<1>), grid2, dim3(512), lds2, st2, k);
     } else {
-      if (!configured2[1]) {
-        GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hwgrad2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured2[1] = true;
-      }
+      if (int rc = gs_allow_lds<&hwgrad2_kernel<2>>(160 * 1024)) return rc;
       hipLaunchKernelGGL((hwgrad2_kernel<2>), grid2, dim3(512), lds2, st2, k);
     }
     GS_CHECK_HIP(hipGetLastError());

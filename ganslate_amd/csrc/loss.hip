@@ -3,9 +3,7 @@
 // Replaces nn.MSELoss vs an expanded constant target (ganslate/nn/losses/adversarial_loss.py:28-29,60-62),
 // nn.L1Loss (cyclegan_losses.py:64,75,97-101; pix2pix_losses.py:15-19), tensor.mean() of
 // utils/metrics/train_metrics.py:27-33 and SSIMLoss (nn/losses/utils/ssim.py:65-99).
-#include "common.hpp"
-
-float* gs_reduce_workspace(void* stream);   // 1024 floats + 1 counter, one per launching stream (api.hip)
+#include "internal.hpp"
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   v = wave_sum(v);

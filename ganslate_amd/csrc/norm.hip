@@ -3,7 +3,7 @@
 // Replaces nn.InstanceNorm2d(eps=1e-5, affine=False, track_running_stats=False) + nn.ReLU / nn.LeakyReLU
 // (ganslate/nn/utils.py:53-59; resnet2d.py:26-27,36-37,83-87,93; patchgan2d.py:45-46,58-59) and their
 // autograd backward, including the adjoint of nn.ReflectionPad2d (the `fold`).
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 
 // ---- slot reduction: in [N][slots][R][C] -> per (n, c) totals over the slots ---------------------------------------
@@ -633,7 +633,6 @@ __global__ __launch_bounds__(256) void inorm_bwd_apply_cg_kernel(const uint4* gp
   }
 }
 
-// shared with norm_ex.hip
 int gs_launch_slot_sum3(const float* in, float* out, int N, int slots, int C, float inv_hw, const float* mean_rstd,
                         float* db, hipStream_t st) {
   if (slots > 256 && (long long)N * ((C + 15) / 16) < 128)      // few workgroups, long slot loops: 4x the workgroups

@@ -7,7 +7,7 @@
 // With mean_rstd == NULL there is no norm and `y` holds a sign-preserving activation output (conv epilogue LeakyReLU).
 // HBM-bound streaming kernels: 16 B per lane, fp32 math. Dropout masks come from a counter-based hash of
 // (seed, image, element) so the backward pass regenerates them instead of storing them.
-#include "common.hpp"
+#include "internal.hpp"
 
 struct NormExK {
   gs_norm_ex_desc d;
@@ -233,10 +233,6 @@ __global__ __launch_bounds__(256) void norm_ex_bwd_apply_kernel(const NormExK p,
     dy_n[e] = ex_pack8(o);
   }
 }
-
-// defined in norm.hip
-int gs_launch_slot_sum3(const float* in, float* out, int N, int slots, int C, float inv_hw, const float* mean_rstd,
-                        float* db, hipStream_t st);
 
 static const int kExPixPerBlock = 64;
 

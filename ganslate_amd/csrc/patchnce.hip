@@ -17,7 +17,7 @@
 // memory (W^T, Khat^T, dF^T, H^T, X^T) are transposed while they are staged. The tensors are small (2048 rows x 256):
 // what matters here is the launch count and that nothing leaves the device; row reductions (norms, soft-max) go through
 // DPP row sums + a small LDS exchange, the loss is summed from per-workgroup partials in a fixed order.
-#include "common.hpp"
+#include "internal.hpp"
 
 namespace {
 constexpr int NCE_MAX_LEVELS = 8;
@@ -602,11 +602,6 @@ int fill(NceK& k, const gs_patchnce_desc* d, const float* const* xq, const float
   }
   return 0;
 }
-template <typename Kern>
-int set_lds(Kern kern, int bytes) {
-  GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return 0;
-}
 }  // namespace
 
 extern "C" int64_t gs_patchnce_param_floats(const gs_patchnce_desc* d) {
@@ -631,14 +626,8 @@ extern "C" int gs_patchnce_forward(const gs_patchnce_desc* d, const float* const
   float* part = d ? reinterpret_cast<float*>(static_cast<char*>(work) + 2 * LR * d->nc * 4 + LR * 4 + 3 * LR * d->nc * 2) : nullptr;
   if (int rc = fill(k, d, xq, xk, nullptr, params, nullptr, work, part)) return rc;
   GS_REQUIRE(xq && xk && loss, "gs_patchnce_forward: null argument");
-  static bool configured = false;
-  if (!configured) {
-    if (int rc = set_lds(nce_mlp_fwd_kernel, LDS_FWD)) return rc;
-    if (int rc = set_lds(nce_loss_kernel, LDS_LOSS)) return rc;
-    if (int rc = set_lds(nce_mlp_bwd_kernel, LDS_FWD)) return rc;
-    if (int rc = set_lds(nce_param_grad_kernel, LDS_FWD)) return rc;
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&nce_mlp_fwd_kernel>(LDS_FWD)) return rc;
+  if (int rc = gs_allow_lds<&nce_loss_kernel>(LDS_LOSS)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int row_tiles = (k.R + TM - 1) / TM, img_tiles = (k.P + TM - 1) / TM;
   hipLaunchKernelGGL(nce_mlp_fwd_kernel, dim3(row_tiles, k.L, 2), dim3(512), LDS_FWD, st, k);
@@ -655,6 +644,8 @@ extern "C" int gs_patchnce_backward(const gs_patchnce_desc* d, const float* cons
   if (int rc = fill(k, d, xq, nullptr, dxq, params, grads, work, nullptr)) return rc;
   GS_REQUIRE(xq && dxq && grads, "gs_patchnce_backward: null argument");
   k.gscale = grad_scale;
+  if (int rc = gs_allow_lds<&nce_mlp_bwd_kernel>(LDS_FWD)) return rc;
+  if (int rc = gs_allow_lds<&nce_param_grad_kernel>(LDS_FWD)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int row_tiles = (k.R + TM - 1) / TM;
   hipLaunchKernelGGL(nce_mlp_bwd_kernel, dim3(row_tiles, k.L), dim3(512), LDS_FWD, st, k);

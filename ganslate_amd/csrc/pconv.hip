@@ -15,6 +15,7 @@
 // Same arithmetic, same summation order, same statistics-slot contract as gconv_kernel<256,128,4,4,3>: results are
 // bit-identical (tests/test_ops_gpu.py::test_persistent_im2col_kernel).
 #include "gconv.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 
 namespace {
@@ -452,8 +453,6 @@ int cus() {
 }
 }  // namespace
 
-void* gs_dump_page();
-
 // Does this launch — a single-class 256 x 128 im2col launch without split-K — run on the persistent kernel? (k.tiles_m / tiles_n /
 // nh / nw filled in by the caller)
 bool gs_pconv_eligible(const GConvK& k, bool fused) {
@@ -479,14 +478,7 @@ int gs_pconv_launch(const GConvK& k, bool fused, hipStream_t st) {
   int G = cus() / k.tiles_n * k.tiles_n;                           // one channel tile per workgroup
   if (G > pk.ntiles) G = pk.ntiles;
   const int lds = 3 * STAGE + GS_MAX_TAPS * 2 + 2 * BM * (k.nh + k.nw) * 2 + 2 * BN * 4 + 80 * 4;
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pconv_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pconv_kernel<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    configured = true;
-  }
+  if (int rc = fused ? gs_allow_lds<&pconv_kernel<true>>(160 * 1024) : gs_allow_lds<&pconv_kernel<false>>(160 * 1024)) return rc;
   if (fused) hipLaunchKernelGGL((pconv_kernel<true>), dim3(G), dim3(1024), lds, st, pk);
   else hipLaunchKernelGGL((pconv_kernel<false>), dim3(G), dim3(1024), lds, st, pk);
   GS_CHECK_HIP(hipGetLastError());

@@ -9,11 +9,7 @@
 // coupling y1 = x1 + PReLU(IN(conv(x2))) (norm, mode 2), block tails PReLU(core(x) + x) (no norm, mode 1).
 // HBM-bound streaming kernels: 16 B per lane, fp32 math, deterministic two-level reductions (atomics only for the
 // final per-image accumulation into the parameter-gradient buffer, as in wgrad).
-#include "common.hpp"
-
-// norm.hip: parameter gradients summed over the images in a fixed order
-int gs_launch_norm_param_grads(const float* sums, int R, const float* mean_rstd, float* db, float* dslope, int N, int C,
-                               float inv_hw, hipStream_t st);
+#include "internal.hpp"
 
 struct PNormK {
   gs_pnorm_desc d;

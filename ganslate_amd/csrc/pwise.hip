@@ -10,7 +10,7 @@
 // Weight gradient: vector ALUs (the K dimension is the voxel index, which would want a transposing load): a lane holds the
 // 8 x 8 outer-product sums of one (a octet, g octet) pair, a workgroup adds its lanes in lane order, per-workgroup slabs are
 // added in slab order by the shared reduction (no atomics on the deterministic path).
-#include "common.hpp"
+#include "internal.hpp"
 
 namespace {
 typedef __attribute__((ext_vector_type(4))) float f32x4;

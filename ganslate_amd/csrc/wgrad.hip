@@ -10,7 +10,7 @@
 // memory (NHWC), so MFMA fragments (8 consecutive k per lane) are read with the LDS transpose read
 // ds_read_b64_tr_b16 from [64 pixels][128 channels] tiles staged by LDS-DMA. The pixel range of every image
 // is split over workgroups (split-K); partial tiles are accumulated with fp32 atomics.
-#include "common.hpp"
+#include "internal.hpp"
 #include <cstdlib>
 
 struct WGradK {
@@ -376,12 +376,7 @@ int launch_wgrad_impl(WGradK& k, const gs_wgrad_desc* d, hipStream_t st, int pla
   GS_REQUIRE(!k.adam || (splits == 1 && k.vec && k.rmw && k.nets == 1 && d->dw_ld % 8 == 0),
              "gs_wgrad_adam: not a one-split launch with 16-byte rows (gs_wgrad_adam_eligible)");
   constexpr int lds = 3 * 64 * (BP + BQ) * 2 + GS_MAX_TAPS * 4 + 1024;
-  static bool configured = false;
-  if (!configured) {
-    GS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<BP, BQ, WP, WQ, VOL>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    configured = true;
-  }
+  if (int rc = gs_allow_lds<&wgrad_kernel<BP, BQ, WP, WQ, VOL>>(lds)) return rc;
   hipLaunchKernelGGL((wgrad_kernel<BP, BQ, WP, WQ, VOL>), dim3((unsigned)blocks), dim3(WP * WQ * 64), lds, st, k);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -460,14 +455,6 @@ void gs_launch_slab_reduce(const float* ws, float* dst, long long n4, int slabs,
   launch_slab_reduce(ws, dst, n4, slabs, stride4, st, nets, ws_y4, dw_y4);
 }
 
-// hwgrad.hip: halo-resident kernels for narrow stride-1 layers and the wide 3x3 layers
-int gs_hwgrad_try2(const gs_wgrad_desc* d, const void* a, const void* g, const void* a2, const void* g2, float* dw,
-                   float* ws, int plan_only, void* stream, int* handled, const gs_twin* tw);
-
-// pwise.hip: one-tap layers with 8 channels on one side
-int gs_pwise_wgrad_try(const gs_wgrad_desc* d, const void* a, const void* g, float* dw, float* ws, int plan_only, void* stream,
-                       int* handled);
-
 namespace {
 // the im2col kernel for one operand pair; ws != nullptr: partial tiles to slabs, *slabs = how many
 int wgrad_generic(const gs_wgrad_desc* d, const void* a, const void* g, float* dw, float* ws, int plan_only,
@@ -508,9 +495,17 @@ int wgrad_check(const gs_wgrad_desc* d) {
   return 0;
 }
 
-int wgrad_reduce(const gs_wgrad_desc* d, const float* ws, float* dw, int slabs, void* stream) {
-  const long long n = (long long)d->P * d->dw_ld;          // multiple of 64: P and Q are multiples of 8
-  launch_slab_reduce(ws, dw, n / 4, slabs, n / 4, static_cast<hipStream_t>(stream));
+// dw += the `slabs` slabs of ws (`slab` floats each, a multiple of 64: P and Q are multiples of 8) in slab order. Twin batch: the
+// second network's slabs follow the first's and add to the buffer tw->dw_delta bytes further on — both networks in one launch
+// when the alignment allows, else one launch each.
+int reduce_slabs(const float* ws, float* dw, int slabs, long long slab, const gs_twin* tw, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (tw && tw->dw_delta % 16 == 0 && ((size_t)slabs * slab) % 4 == 0) {
+    launch_slab_reduce(ws, dw, slab / 4, slabs, slab / 4, st, 2, (long long)slabs * slab / 4, tw->dw_delta / 16);
+  } else {
+    launch_slab_reduce(ws, dw, slab / 4, slabs, slab / 4, st);
+    if (tw) launch_slab_reduce(ws + (size_t)slabs * slab, dw + tw->dw_delta / 4, slab / 4, slabs, slab / 4, st);
+  }
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -519,7 +514,7 @@ int wgrad_reduce(const gs_wgrad_desc* d, const float* ws, float* dw, int slabs, 
 int wgrad_impl(const gs_wgrad_desc* d, const void* a1, const void* g1, const void* a2, const void* g2, float* dw,
                float* ws, int64_t ws_floats, int plan_only, void* stream, int64_t* need_floats, const gs_twin* tw = nullptr) {
   if (int rc = wgrad_check(d)) return rc;
-  const long long slab = (long long)d->P * d->dw_ld;
+  const long long slab = (long long)d->P * d->dw_ld;         // floats of one slab = of dw
   const bool det = ws != nullptr || plan_only;
   int handled = 0;
   if (!a2 && !tw)
@@ -532,15 +527,7 @@ int wgrad_impl(const gs_wgrad_desc* d, const void* a1, const void* g1, const voi
     if (plan_only || !det) return 0;
     GS_REQUIRE(ws_floats >= (int64_t)nets * handled * slab, "gs_wgrad_ws: workspace of %lld floats, %lld needed",
                (long long)ws_floats, (long long)nets * handled * slab);
-    if (tw && tw->dw_delta % 16 == 0 && ((size_t)handled * slab) % 4 == 0) {      // both networks in one launch
-      launch_slab_reduce(ws, dw, slab / 4, handled, slab / 4, static_cast<hipStream_t>(stream), 2, (long long)handled * slab / 4,
-                         tw->dw_delta / 16);
-      GS_CHECK_HIP(hipGetLastError());
-      return 0;
-    }
-    if (int rc = wgrad_reduce(d, ws, dw, handled, stream)) return rc;
-    if (tw) return wgrad_reduce(d, ws + (size_t)handled * slab, dw + tw->dw_delta / 4, handled, stream);
-    return 0;
+    return reduce_slabs(ws, dw, handled, slab, tw, stream);
   }
   if (tw) {
     // the im2col kernel splits each network's pixels on its own — unless one of the halo kernels without a twin form
@@ -572,20 +559,23 @@ int wgrad_impl(const gs_wgrad_desc* d, const void* a1, const void* g1, const voi
     if (plan_only || !det) continue;
     GS_REQUIRE(ws_floats >= (int64_t)nets * slabs * slab, "gs_wgrad_ws: workspace of %lld floats, %lld needed",
                (long long)ws_floats, (long long)nets * slabs * slab);
-    if (slabs > 0) {
-      if (tw && tw->dw_delta % 16 == 0 && ((size_t)slabs * slab) % 4 == 0) {       // both networks in one launch
-        launch_slab_reduce(ws, dw, slab / 4, slabs, slab / 4, static_cast<hipStream_t>(stream), 2, (long long)slabs * slab / 4,
-                           tw->dw_delta / 16);
-        GS_CHECK_HIP(hipGetLastError());
-        continue;
-      }
-      if (int rc = wgrad_reduce(d, ws, dw, slabs, stream)) return rc;
-      if (tw)
-        if (int rc = wgrad_reduce(d, ws + (size_t)slabs * slab, dw + tw->dw_delta / 4, slabs, stream)) return rc;
-    }
+    if (slabs > 0)
+      if (int rc = reduce_slabs(ws, dw, slabs, slab, tw, stream)) return rc;
   }
   if (need_floats) *need_floats = need;
   return 0;
+}
+
+// Plan-only run of wgrad_impl (nothing is launched; a dummy byte stands in for the operands): floats of workspace the
+// deterministic launch wants. twin: for the twin batch of d->N images; -1 then also says "no twin form: run the two halves".
+// -1: the descriptor was refused (gs_last_error).
+int64_t wgrad_probe(const gs_wgrad_desc* d, int pair, bool twin) {
+  static const char dummy = 0;
+  const void* second = pair ? &dummy : nullptr;
+  gs_twin t{};
+  t.n_split = d->N / 2;
+  int64_t need = 0;
+  return wgrad_impl(d, &dummy, &dummy, second, second, nullptr, nullptr, 0, 1, nullptr, &need, twin ? &t : nullptr) ? -1 : need;
 }
 }  // namespace
 
@@ -633,12 +623,7 @@ extern "C" int gs_wgrad_pair(const gs_wgrad_desc* d, const void* a1, const void*
 // Deterministic form of both: workgroups that share output elements write partial sums to slabs of the caller's
 // workspace and a second launch adds the slabs in a fixed order (no fp32 atomics: two runs give bit-identical dw).
 extern "C" int64_t gs_wgrad_ws_floats(const gs_wgrad_desc* d, int32_t pair) {
-  if (!d) return 0;
-  int64_t need = 0;
-  static const char dummy = 0;
-  if (wgrad_impl(d, &dummy, &dummy, pair ? &dummy : nullptr, pair ? &dummy : nullptr, nullptr, nullptr, 0, 1, nullptr, &need))
-    return -1;
-  return need;
+  return d ? wgrad_probe(d, pair, false) : 0;
 }
 extern "C" int gs_wgrad_ws(const gs_wgrad_desc* d, const void* a1, const void* g1, const void* a2, const void* g2,
                            float* dw, float* ws, int64_t ws_floats, void* stream) {
@@ -649,24 +634,12 @@ extern "C" int gs_wgrad_ws(const gs_wgrad_desc* d, const void* a1, const void* g
 
 // Twin batches (gs_twin): the wide 3x3 residual convs (hwgrad.hip) take both networks' images in one launch — half the
 // pixel splits per network, so half the slab traffic per gradient, one launch and one prologue instead of two.
-static gs_twin twin_probe(const gs_wgrad_desc* d) { gs_twin t{}; t.n_split = d->N / 2; return t; }
 extern "C" int gs_wgrad_twin_native(const gs_wgrad_desc* d, int32_t pair) {
   if (!d || d->N < 2 || (d->N & 1)) return 0;
-  int64_t need = 0;
-  static const char dummy = 0;
-  const gs_twin t = twin_probe(d);
-  if (wgrad_impl(d, &dummy, &dummy, pair ? &dummy : nullptr, pair ? &dummy : nullptr, nullptr, nullptr, 0, 1, nullptr, &need, &t))
-    return 0;
-  return need >= 0;
+  return wgrad_probe(d, pair, true) >= 0;
 }
 extern "C" int64_t gs_wgrad_ws_floats_twin(const gs_wgrad_desc* d, int32_t pair) {
-  if (!d) return -1;
-  int64_t need = 0;
-  static const char dummy = 0;
-  const gs_twin t = twin_probe(d);
-  if (wgrad_impl(d, &dummy, &dummy, pair ? &dummy : nullptr, pair ? &dummy : nullptr, nullptr, nullptr, 0, 1, nullptr, &need, &t))
-    return -1;
-  return need;
+  return d ? wgrad_probe(d, pair, true) : -1;
 }
 extern "C" int gs_wgrad_ws_twin(const gs_wgrad_desc* d, const void* a1, const void* g1, const void* a2, const void* g2,
                                 float* dw, float* ws, int64_t ws_floats, const gs_twin* tw, void* stream) {
