@@ -1,0 +1,385 @@
+// Device-side sampling of multi-modal training patches (data/multimodal_volumes.py, data/device_volumes.py): the
+// HX4-PET dataset of the reference (projects/maastro_hx4_pet_translation/datasets/train_dataset.py with
+// datasets/utils/patch_samplers.py and basic.py) draws the patch centre ("focal point") inside a body mask — uniformly or
+// weighted by a PET volume — by building a float64 probability map of the whole volume per sample. Here the volumes and
+// masks are RESIDENT in HBM and the draw is a masked prefix sum over the valid zone's box; the uniform u comes from the
+// host's np.random stream, everything else stays on the device.
+//
+// gs_voxel_draw — the selection rule (ganslate_hip.h states it in full): over the zone box in C order,
+//   mask-only:  the k-th non-zero voxel, k = min(floor(u * count), count - 1)         (int64, exact)
+//   weighted:   the first voxel whose inclusive float64 prefix sum exceeds u * total;  fallback: the last positive one
+// restricted to the stochastic-focal box around A's point when that intersection is not empty (flag 0), else
+// unrestricted (flag 1). Three launches, no atomics, no host round trip:
+//   1. NR workgroups, each owning a contiguous C-order range of the box; every thread sums one contiguous run of its range
+//      in index order, thread 0 adds the 256 run sums in index order -> per-range partials for both sets
+//   2. one thread scans the NR partials in index order: picks the set, the owning range and the residual target
+//   3. the owning range repeats pass 1's sums (bitwise the same numbers), thread 0 finds the owning run, and that run's
+//      thread rescans it and stores the voxel
+// Every sum has one fixed order, so a draw is bitwise reproducible; pass 3 re-derives exactly the partial pass 2 compared
+// against, so the owning run always exists. HBM-bound and small: 1 B (mask) or 1 + 4 B (mask + fp32 weight) per voxel of a
+// box of a few MB, read once plus one range. The lanes of a wave read adjacent short runs, i.e. one contiguous span per
+// wave; that and in-order scans are all this kernel needs — it is not tuned further.
+//
+// gs_patch_clip_minmax — crop + per-modality normalisation of all C modalities of one sample in one launch:
+//   v = mask ? (float)x : outside;  v = v / divisor;  v = min(max(v, lo), hi);  v = (v - lo) / (hi - lo);  v = 2 * v - 1
+// one IEEE fp32 operation per step (no contraction), the focal point read from device memory, the start clamped into the
+// volume so that no point can make the kernel read outside it.
+#include <limits>
+#include "common.hpp"
+
+namespace {
+constexpr int NR = 256;      // ranges = workgroups of pass 1
+constexpr int NT = 256;      // threads per workgroup = runs per range
+
+struct DrawK {
+  const uint8_t* mask;
+  const void* weight;
+  int D, H, W;
+  int z0, y0, x0, bd, bh, bw;      // the valid zone's box
+  long long n, L, S;               // voxels of the box, voxels per range, voxels per run
+  double u;
+  const int32_t* focal_a;          // device: the point drawn in A (nullptr: no focal box)
+  int da[3], region[3];            // A's dims; focal region size in voxels of this volume
+};
+
+template <typename V>
+struct Sel {
+  int range, set;
+  V resid;
+};
+
+template <typename T>
+using Vt = typename std::conditional<std::is_void<T>::value, long long, double>::type;
+
+template <typename V>
+__device__ __forceinline__ V never() {
+  if constexpr (std::is_same<V, double>::value) return std::numeric_limits<double>::infinity();
+  else return std::numeric_limits<long long>::max();
+}
+
+// the reference's _sample_focal_point_B / _apply_stochastic_focal_method in float64, one rounding per operation
+__device__ __forceinline__ void focal_box(const DrawK& k, int lo[3], int hi[3]) {
+  const int size[3] = {k.D, k.H, k.W};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = 0;
+    hi[a] = size[a];
+    if (k.focal_a) {
+      const double rel = __ddiv_rn((double)k.focal_a[a], (double)k.da[a]);
+      const double f = __dmul_rn(rel, (double)size[a]);
+      const double half = __ddiv_rn((double)k.region[a], 2.0);
+      const int mn = (int)__dsub_rn(f, half), mx = (int)__dadd_rn(f, half);
+      lo[a] = mn > 0 ? mn : 0;
+      hi[a] = mx < size[a] ? mx : size[a];
+    }
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ Vt<T> weight_at(const DrawK& k, long long off) {
+  using V = Vt<T>;
+  if (!k.mask[off]) return V(0);
+  if constexpr (std::is_void<T>::value) {
+    return V(1);
+  } else {
+    const double w = (double)static_cast<const T*>(k.weight)[off];
+    return w > 0.0 ? w : 0.0;      // negative (and NaN) weights count as 0
+  }
+}
+
+// the run of thread t of range r: [b, e) in box C order
+__device__ __forceinline__ void run_bounds(const DrawK& k, int r, int t, long long& b, long long& e) {
+  const long long rb = (long long)r * k.L;
+  long long re = rb + k.L;
+  if (re > k.n) re = k.n;
+  b = rb + (long long)t * k.S;
+  e = b + k.S;
+  if (e > re) e = re;
+}
+
+// f(z, y, x, weight) in index order over [b, e), volume coordinates; f returns false to stop
+template <typename T, typename F>
+__device__ __forceinline__ void walk_run(const DrawK& k, long long b, long long e, F&& f) {
+  if (b >= e) return;
+  int x = (int)(b % k.bw);
+  const long long row = b / k.bw;
+  int y = (int)(row % k.bh), z = (int)(row / k.bh);
+  for (long long i = b; i < e; ++i) {
+    const long long off = ((long long)(k.z0 + z) * k.H + (k.y0 + y)) * k.W + (k.x0 + x);
+    if (!f(k.z0 + z, k.y0 + y, k.x0 + x, weight_at<T>(k, off))) return;
+    if (++x == k.bw) {
+      x = 0;
+      if (++y == k.bh) { y = 0; ++z; }
+    }
+  }
+}
+
+__device__ __forceinline__ bool inside(const int lo[3], const int hi[3], int z, int y, int x) {
+  return z >= lo[0] && z < hi[0] && y >= lo[1] && y < hi[1] && x >= lo[2] && x < hi[2];
+}
+
+// partial[2 r] = sum over (focal box ∩ range r), partial[2 r + 1] = sum over range r
+template <typename T>
+__global__ __launch_bounds__(NT) void draw_partials_kernel(const DrawK k, Vt<T>* partial) {
+  using V = Vt<T>;
+  __shared__ V sf[NT], sz[NT];
+  int lo[3], hi[3];
+  focal_box(k, lo, hi);
+  long long b, e;
+  run_bounds(k, blockIdx.x, threadIdx.x, b, e);
+  V af = 0, az = 0;
+  walk_run<T>(k, b, e, [&](int z, int y, int x, V w) {
+    az += w;
+    if (inside(lo, hi, z, y, x)) af += w;
+    return true;
+  });
+  sf[threadIdx.x] = af;
+  sz[threadIdx.x] = az;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    V a = 0, c = 0;
+    for (int i = 0; i < NT; ++i) { a += sf[i]; c += sz[i]; }
+    partial[2 * blockIdx.x] = a;
+    partial[2 * blockIdx.x + 1] = c;
+  }
+}
+
+// first index whose entry exceeds what is left of the target, scanning in index order; none: the last positive entry,
+// with a residual nothing exceeds (the rescans then end at their last positive voxel)
+template <typename V, typename G>
+__device__ __forceinline__ int owner_of(int count, V target, V& resid, G&& get) {
+  V before = 0;
+  int lastpos = -1;
+  for (int i = 0; i < count; ++i) {
+    const V p = get(i);
+    if (p > 0) lastpos = i;
+    const V rs = target - before;
+    if (p > rs) { resid = rs; return i; }
+    before += p;
+  }
+  resid = never<V>();
+  return lastpos;
+}
+
+template <typename T>
+__global__ void draw_select_kernel(const DrawK k, const Vt<T>* partial, Sel<Vt<T>>* sel, int32_t* out) {
+  using V = Vt<T>;
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  V tf = 0, tz = 0;
+  for (int r = 0; r < NR; ++r) { tf += partial[2 * r]; tz += partial[2 * r + 1]; }
+  const bool focal = k.focal_a != nullptr;
+  const int set = (focal && tf > 0) ? 0 : 1;
+  const int flag = (focal && !(tf > 0)) ? 1 : 0;
+  const V total = set == 0 ? tf : tz;
+  out[3] = flag;
+  if (!(total > 0)) {                      // empty zone ∩ body, or no positive weight in it
+    out[0] = out[1] = out[2] = -1;
+    sel->range = -1;
+    return;
+  }
+  V target;
+  if constexpr (std::is_void<T>::value) {
+    long long kk = (long long)floor(__dmul_rn(k.u, (double)total));
+    if (kk > total - 1) kk = total - 1;
+    if (kk < 0) kk = 0;
+    target = kk;                           // the k-th non-zero voxel is the first with inclusive count > k
+  } else {
+    target = __dmul_rn(k.u, total);
+  }
+  V resid;
+  sel->range = owner_of<V>(NR, target, resid, [&](int r) { return partial[2 * r + set]; });
+  sel->set = set;
+  sel->resid = resid;
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void draw_locate_kernel(const DrawK k, const Sel<Vt<T>>* sel, int32_t* out) {
+  using V = Vt<T>;
+  __shared__ V s[NT];
+  __shared__ int own_run;
+  __shared__ V own_resid;
+  const int r = sel->range;
+  if (r < 0) return;
+  const bool all = sel->set != 0;
+  int lo[3], hi[3];
+  focal_box(k, lo, hi);
+  long long b, e;
+  run_bounds(k, r, threadIdx.x, b, e);
+  V a = 0;
+  walk_run<T>(k, b, e, [&](int z, int y, int x, V w) {
+    if (all || inside(lo, hi, z, y, x)) a += w;
+    return true;
+  });
+  s[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    V resid;
+    own_run = owner_of<V>(NT, sel->resid, resid, [&](int i) { return s[i]; });
+    own_resid = resid;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x != own_run) return;
+  const V resid = own_resid;
+  V acc = 0;
+  int pz = -1, py = -1, px = -1;
+  walk_run<T>(k, b, e, [&](int z, int y, int x, V w) {
+    if (!(w > 0) || !(all || inside(lo, hi, z, y, x))) return true;
+    pz = z; py = y; px = x;
+    acc += w;
+    return !(acc > resid);
+  });
+  out[0] = pz;
+  out[1] = py;
+  out[2] = px;
+}
+
+template <typename T>
+int launch_draw(const DrawK& k, int32_t* out, void* ws, hipStream_t st) {
+  using V = Vt<T>;
+  V* partial = static_cast<V*>(ws);
+  Sel<V>* sel = reinterpret_cast<Sel<V>*>(partial + 2 * NR);
+  hipLaunchKernelGGL((draw_partials_kernel<T>), dim3(NR), dim3(NT), 0, st, k, partial);
+  hipLaunchKernelGGL((draw_select_kernel<T>), dim3(1), dim3(64), 0, st, k, partial, sel, out);
+  hipLaunchKernelGGL((draw_locate_kernel<T>), dim3(1), dim3(NT), 0, st, k, sel, out);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// the valid zone [floor(p / 2), size - ceil(p / 2)) of one axis
+inline int zone_lo(int p) { return p / 2; }
+inline int zone_hi(int size, int p) { return size - (p + 1) / 2; }
+
+long long range_len(int D, int H, int W, const int32_t* p) {
+  const long long bd = zone_hi(D, p[0]) - zone_lo(p[0]), bh = zone_hi(H, p[1]) - zone_lo(p[1]),
+                  bw = zone_hi(W, p[2]) - zone_lo(p[2]);
+  if (bd <= 0 || bh <= 0 || bw <= 0) return 0;
+  return (bd * bh * bw + NR - 1) / NR;
+}
+
+constexpr int PC_MAX = GS_PATCH_MAX_MODALITIES;
+
+struct ClipK {
+  const void* vol[PC_MAX];
+  int dtype[PC_MAX];
+  float outside[PC_MAX], divisor[PC_MAX], lo[PC_MAX], hi[PC_MAX];
+  const uint8_t* mask;
+  const int32_t* point;
+  int D, H, W, pd, ph, pw;
+  long long n;
+};
+
+__global__ __launch_bounds__(256) void patch_clip_minmax_kernel(const ClipK k, float* out) {
+  const int c = blockIdx.y;
+  const int size[3] = {k.D, k.H, k.W}, patch[3] = {k.pd, k.ph, k.pw};
+  int s[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    int v = k.point[a] - patch[a] / 2;
+    const int top = size[a] - patch[a];
+    v = v > top ? top : v;
+    s[a] = v < 0 ? 0 : v;
+  }
+  const void* vol = k.vol[c];
+  const int dtype = k.dtype[c];
+  const float outside = k.outside[c], divisor = k.divisor[c], lo = k.lo[c], hi = k.hi[c];
+  const float span = __fsub_rn(hi, lo);
+  float* dst = out + (long long)c * k.n;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < k.n; i += (long long)gridDim.x * 256) {
+    const int x = (int)(i % k.pw);
+    const long long row = i / k.pw;
+    const int y = (int)(row % k.ph), z = (int)(row / k.ph);
+    const long long off = ((long long)(s[0] + z) * k.H + (s[1] + y)) * k.W + (s[2] + x);
+    float v = outside;
+    if (k.mask[off])
+      v = dtype == GS_VOL_F32 ? static_cast<const float*>(vol)[off] : (float)static_cast<const short*>(vol)[off];
+    v = __fdiv_rn(v, divisor);
+    v = v < lo ? lo : v;                   // NaN stays NaN, like torch.clamp
+    v = v > hi ? hi : v;
+    v = __fdiv_rn(__fsub_rn(v, lo), span);
+    dst[i] = __fsub_rn(__fmul_rn(2.f, v), 1.f);
+  }
+}
+}  // namespace
+
+extern "C" int64_t gs_voxel_draw_ws_bytes(void) { return (int64_t)(2 * NR) * 8 + 16; }
+
+extern "C" int64_t gs_voxel_draw_range_len(int32_t D, int32_t H, int32_t W, const int32_t* patch) {
+  if (!patch) return 0;
+  return range_len(D, H, W, patch);
+}
+
+extern "C" int gs_voxel_draw(const uint8_t* mask, const void* weight, int32_t wdtype, int32_t D, int32_t H, int32_t W,
+                             const int32_t* patch, double u, const int32_t* focal_a, const int32_t* dims_a,
+                             const double* proportion, int32_t* out, void* ws, void* stream) {
+  GS_REQUIRE(mask && patch && out && ws, "gs_voxel_draw: null argument");
+  GS_REQUIRE(!weight || wdtype == GS_VOL_F32 || wdtype == GS_VOL_I16,
+             "gs_voxel_draw: weight dtype %d (GS_VOL_F32 / GS_VOL_I16)", wdtype);
+  GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
+                 patch[2] <= W,
+             "gs_voxel_draw: patch %d x %d x %d does not fit the %d x %d x %d volume", patch[0], patch[1], patch[2], D, H, W);
+  GS_REQUIRE(u >= 0.0 && u < 1.0, "gs_voxel_draw: u = %.17g is not in [0, 1)", u);
+  GS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "gs_voxel_draw: the workspace must be 8-byte aligned");
+  GS_REQUIRE(!focal_a || (dims_a && proportion), "gs_voxel_draw: a focal point needs A's dims and the proportions");
+  DrawK k;
+  k.mask = mask;
+  k.weight = weight;
+  k.D = D; k.H = H; k.W = W;
+  k.z0 = zone_lo(patch[0]); k.y0 = zone_lo(patch[1]); k.x0 = zone_lo(patch[2]);
+  k.bd = zone_hi(D, patch[0]) - k.z0; k.bh = zone_hi(H, patch[1]) - k.y0; k.bw = zone_hi(W, patch[2]) - k.x0;
+  if (k.bd <= 0 || k.bh <= 0 || k.bw <= 0) { k.bd = k.bh = k.bw = 0; }      // empty zone: every partial is 0, out = -1
+  k.n = (long long)k.bd * k.bh * k.bw;
+  k.L = (k.n + NR - 1) / NR;
+  k.S = (k.L + NT - 1) / NT;
+  if (k.bw == 0) k.bw = k.bh = 1;                                            // never divided by: n == 0 walks nothing
+  k.u = u;
+  k.focal_a = focal_a;
+  const int size[3] = {D, H, W};
+  for (int a = 0; a < 3; ++a) {
+    k.da[a] = 1;
+    k.region[a] = 0;
+    if (focal_a) {
+      GS_REQUIRE(dims_a[a] > 0 && proportion[a] >= 0.0 && proportion[a] <= 1.0,
+                 "gs_voxel_draw: A's dims must be positive and the focal region proportions in [0, 1]");
+      k.da[a] = dims_a[a];
+      k.region[a] = (int)(proportion[a] * (double)size[a]);                 // one rounding, then truncation
+    }
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!weight) return launch_draw<void>(k, out, ws, st);
+  return wdtype == GS_VOL_F32 ? launch_draw<float>(k, out, ws, st) : launch_draw<short>(k, out, ws, st);
+}
+
+extern "C" int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
+                                    int32_t D, int32_t H, int32_t W, const int32_t* patch, const int32_t* point,
+                                    const float* outside, const float* divisor, const float* lo, const float* hi, float* out,
+                                    void* stream) {
+  GS_REQUIRE(vols && dtypes && mask && patch && point && outside && divisor && lo && hi && out,
+             "gs_patch_clip_minmax: null argument");
+  GS_REQUIRE(C >= 1 && C <= PC_MAX, "gs_patch_clip_minmax: between 1 and %d modalities per call; got %d", PC_MAX, C);
+  GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
+                 patch[2] <= W,
+             "gs_patch_clip_minmax: patch %d x %d x %d does not fit the %d x %d x %d volume", patch[0], patch[1], patch[2],
+             D, H, W);
+  ClipK k;
+  for (int c = 0; c < PC_MAX; ++c) {
+    const int s = c < C ? c : 0;
+    GS_REQUIRE(vols[s], "gs_patch_clip_minmax: null volume %d", s);
+    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16,
+               "gs_patch_clip_minmax: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", dtypes[s], s);
+    GS_REQUIRE(hi[s] > lo[s], "gs_patch_clip_minmax: clip range [%g, %g] of volume %d is empty", lo[s], hi[s], s);
+    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "gs_patch_clip_minmax: divisor %g of volume %d", divisor[s], s);
+    k.vol[c] = vols[s];
+    k.dtype[c] = dtypes[s];
+    k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
+  }
+  k.mask = mask;
+  k.point = point;
+  k.D = D; k.H = H; k.W = W;
+  k.pd = patch[0]; k.ph = patch[1]; k.pw = patch[2];
+  k.n = (long long)patch[0] * patch[1] * patch[2];
+  const long long blocks = (k.n + 256 * 4 - 1) / (256 * 4);
+  hipLaunchKernelGGL(patch_clip_minmax_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks), (unsigned)C), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), k, out);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}

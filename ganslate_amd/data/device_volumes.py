@@ -2,6 +2,7 @@
 iteration only patch coordinates arrive from the loader (data/volume_datasets.py RawPatch), crop + z-score + range
 scaling run as gs_patch_zscore (csrc/volproc.hip) and write straight into the fp32 [N, 1, d, h, w] batch `set_input`
 takes. Reference path being replaced: projects/brats_mri_sequence_translation/datasets/train_dataset.py:83-92."""
+import numpy as np
 import torch
 
 
@@ -49,4 +50,94 @@ class DeviceVolumePipeline:
             for n, r in enumerate(items):
                 self.ops.patch_zscore(self.volume(r.domain, r.index), r.start, self.size, dst[n, 0], (-1.0, 1.0))
             out[key] = dst.squeeze(2) if self.squeeze else dst
+        return out
+
+
+class DeviceMultiModalPipeline:
+    """callable(raw batch) -> {"A": fp32 [N, C_A, *patch] on the device, "B": fp32 [N, C_B, *patch]} for
+    MultiModalVolumeDataset (data/multimodal_volumes.py): volumes and body masks resident in HBM, per iteration only case
+    indices and uniforms arrive. Per sample: one gs_voxel_draw per domain when unpaired (B's reads A's point from device
+    memory), one in total when paired, and one gs_patch_clip_minmax per domain writing all of its modalities straight into
+    the batch (csrc/volsample.hip). Nothing synchronises per iteration; the empty-zone check of a case runs once, when its
+    mask is first uploaded. Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
+    train_dataset.py:106-188 with datasets/utils/patch_samplers.py."""
+
+    def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
+        self.dataset = dataset
+        self.device = torch.device(device)
+        self._ops = ops
+        self.size = [int(v) for v in dataset.patch_size]
+        self.resident = {}
+        self.resident_bytes, self.max_resident_bytes = 0, max_resident_bytes
+        self.checked = set()
+        self.points = None          # int32 [N, 2, 4] of the last batch: (z, y, x, fallback_used) per sample and domain
+
+    @property
+    def ops(self):
+        if self._ops is None:
+            from ..nn.native.backend import get_ops
+            self._ops = get_ops()
+        return self._ops
+
+    def volume(self, name, index, mask=False):
+        key = (name, index)
+        v = self.resident.get(key)
+        if v is None:
+            host = torch.from_numpy(np.array(self.dataset.load(name, index)))       # a copy out of the memory map
+            if mask:
+                host = (host != 0).to(torch.uint8)
+            elif host.dtype not in (torch.float32, torch.int16):
+                host = host.float()
+            v = host.to(self.device)
+            nbytes = v.numel() * v.element_size()
+            if self.resident_bytes + nbytes <= self.max_resident_bytes:      # beyond the budget: upload per use
+                self.resident[key] = v
+                self.resident_bytes += nbytes
+        return v
+
+    def case(self, domain, index):
+        """(mask, weight or None, [volumes]) of one case of a domain; on first use the count of the kernel's own draw tells
+        whether the case can be sampled at all — one .item() per case, never per iteration"""
+        ds = self.dataset
+        mask = self.volume(ds.body_mask[domain], index, mask=True)
+        weight = self.volume(ds.weight_modality, index) if domain == "A" and ds.weight_modality else None
+        if (domain, index) not in self.checked and (domain == "A" or not ds.paired):
+            probe = torch.empty(4, dtype=torch.int32, device=self.device)
+            self.ops.voxel_draw(mask, weight, self.size, 0.0, probe)
+            if int(probe[0].item()) < 0:
+                raise ds.empty_zone_error(domain, index)
+            self.checked.add((domain, index))
+        return mask, weight, [self.volume(n, index) for n in ds.modalities[domain]]
+
+    def _patch(self, domain, index, vols, mask, point, dst):
+        ds = self.dataset
+        names = ds.modalities[domain]
+        self.ops.patch_clip_minmax(vols, mask, point, self.size, [ds.outside_value[n] for n in names],
+                                   [ds.divisor(n, index) for n in names], [ds.clip_range[n][0] for n in names],
+                                   [ds.clip_range[n][1] for n in names], dst)
+
+    def __call__(self, batch):
+        from .multimodal_volumes import RawCase
+        items_A, items_B = batch.get("A"), batch.get("B")
+        if not items_A or not isinstance(items_A[0], RawCase):
+            return batch
+        ds, n = self.dataset, len(items_A)
+        out = {k: v for k, v in batch.items() if k not in ("A", "B")}
+        dst = {k: torch.empty((n, len(ds.modalities[k]), *self.size), dtype=torch.float32, device=self.device) for k in "AB"}
+        points = torch.empty((n, 2, 4), dtype=torch.int32, device=self.device)
+        for i, (a, b) in enumerate(zip(items_A, items_B)):
+            mask_A, weight, vols_A = self.case("A", a.index)
+            self.ops.voxel_draw(mask_A, weight, self.size, a.u, points[i, 0])
+            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i])
+            if ds.paired:                                   # the same point, A's mask and A's case
+                points[i, 1].copy_(points[i, 0])
+                self._patch("B", a.index, [self.volume(m, a.index) for m in ds.modalities["B"]], mask_A, points[i, 0],
+                            dst["B"][i])
+            else:
+                mask_B, _, vols_B = self.case("B", b.index)
+                self.ops.voxel_draw(mask_B, None, self.size, b.u, points[i, 1], focal_A=points[i, 0],
+                                    dims_A=tuple(mask_A.shape), proportion=ds.focal_region_proportion)
+                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i])
+        self.points = points
+        out.update(dst)
         return out

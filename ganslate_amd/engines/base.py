@@ -50,14 +50,15 @@ class BaseEngineWithInference(BaseEngine):
         return self._input_pipelines[loader]
 
     def _make_input_pipeline(self, dataset):
+        from ..data.multimodal_volumes import MultiModalVolumeDataset
         from ..data.volume_datasets import UnpairedVolumeDataset
         # where each dataset keeps the switch: the image folders in their transform, the volume folder on itself
         places = ((getattr(dataset, "transform", None), "raw"), (dataset, "raw"), (getattr(dataset, "conf", None), "device_transforms"),
                   (dataset, "device_transforms"))
         flag = any(getattr(owner, name, False) is True for owner, name in places)
         make = getattr(dataset, "device_pipeline", None)
-        if flag and (make is None or isinstance(dataset, UnpairedVolumeDataset)):
-            # UnpairedVolumeDataset's device path holds training patches, not whole volumes
+        if flag and (make is None or isinstance(dataset, (UnpairedVolumeDataset, MultiModalVolumeDataset))):
+            # the volume datasets' device paths hold training patches, not whole volumes
             raise NotImplementedError(f"{self.conf.mode} datasets run the host transform path: set "
                                       f"`{self.conf.mode}.dataset.device_transforms: false` (the device-side "
                                       "pipeline batches training samples only)")

@@ -207,6 +207,15 @@ _PROTOS = {
     "gs_patch_zscore": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "gs_voxel_draw_ws_bytes": (C.c_int64, []),
+    "gs_voxel_draw_range_len": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "gs_voxel_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "gs_patch_clip_minmax": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                       C.c_void_p]),
     "gs_mse_const": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_adv_loss": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]),

@@ -1007,6 +1007,70 @@ class HipOps(TwinSplit):
                                          int(bool(scale_to_range)), float(lo), float(hi), _ptr(out), _ptr(ws), _stream()),
                 "gs_patch_zscore")
 
+    # ---- multi-modal patch sampling (volsample.hip) ---------------------------------------------------------------
+    @staticmethod
+    def _case_volume(name, t, dtypes, shape=None):
+        if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dim() == 3 and t.is_contiguous() and t.dtype in dtypes):
+            got = (tuple(t.shape), t.dtype, str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name}: expected a dense (D, H, W) device tensor of dtype {sorted(str(d) for d in dtypes)}; "
+                             f"got {got}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} differs from the mask's {tuple(shape)}")
+
+    @staticmethod
+    def _point(name, t, n):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n):
+            raise ValueError(f"{name}: expected a contiguous int32 device tensor of at least {n} elements")
+
+    def voxel_draw_range_len(self, dims, patch):
+        """voxels of the valid zone's box owned by each workgroup of gs_voxel_draw's first pass (0: empty zone)"""
+        return int(self.lib.gs_voxel_draw_range_len(*[int(v) for v in dims], (C.c_int32 * 3)(*[int(v) for v in patch])))
+
+    def voxel_draw(self, mask, weight, patch, u, out, focal_A=None, dims_A=None, proportion=None):
+        """gs_voxel_draw: one focal point of a resident case into out (int32[4] on the device: z, y, x, fallback_used;
+        -1s when the valid zone holds no body voxel / no positive weight). mask: uint8 (D, H, W); weight: None or an fp32 /
+        int16 volume of the same shape; u: the host's uniform in [0, 1). focal_A (device int32[3]) + dims_A + proportion make
+        it the stochastic-focal draw of domain B. Enqueued on the current stream; nothing syncs."""
+        self._case_volume("mask", mask, (torch.uint8,))
+        if weight is not None:
+            self._case_volume("weight", weight, tuple(self.VOL_DTYPES), mask.shape)
+        self._point("out", out, 4)
+        if focal_A is not None:
+            self._point("focal_A", focal_A, 3)
+            if dims_A is None or proportion is None:
+                raise ValueError("a focal point needs dims_A and proportion")
+        nws = getattr(self, "_draw_ws", None) or int(self.lib.gs_voxel_draw_ws_bytes())
+        self._draw_ws = nws
+        ws = torch.empty(nws // 8, dtype=torch.float64, device=mask.device)     # per launch: private to it
+        da = (C.c_int32 * 3)(*[int(v) for v in dims_A]) if focal_A is not None else None
+        pr = (C.c_double * 3)(*[float(v) for v in proportion]) if focal_A is not None else None
+        L.check(self.lib.gs_voxel_draw(_ptr(mask), _ptr(weight), self.VOL_DTYPES[weight.dtype] if weight is not None else 0,
+                                       *mask.shape, (C.c_int32 * 3)(*[int(v) for v in patch]), float(u), _ptr(focal_A), da,
+                                       pr, _ptr(out), _ptr(ws), _stream()), "gs_voxel_draw")
+
+    def patch_clip_minmax(self, volumes, mask, point, patch, outside, divisor, lo, hi, out):
+        """gs_patch_clip_minmax: out [C, d, h, w] fp32 = the patch around `point` (device int32[3]) of every volume of one
+        case: where(mask, v, outside) / divisor, clamped to [lo, hi], min-max normalised to [-1, 1]. volumes: C fp32 / int16
+        (D, H, W) device tensors; outside / divisor / lo / hi: C host numbers each."""
+        n = len(volumes)
+        if n < 1:
+            raise ValueError("patch_clip_minmax: at least one volume")
+        self._case_volume("mask", mask, (torch.uint8,))
+        for i, v in enumerate(volumes):
+            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        self._point("point", point, 3)
+        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
+            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == (n, *[int(v) for v in patch])):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *[int(v) for v in patch])}")
+        fl = lambda vals: (C.c_float * max(n, 1))(*[float(v) for v in vals])
+        ptrs = (C.c_void_p * max(n, 1))(*[v.data_ptr() for v in volumes])
+        dts = (C.c_int32 * max(n, 1))(*[self.VOL_DTYPES[v.dtype] for v in volumes])
+        L.check(self.lib.gs_patch_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, (C.c_int32 * 3)(*[int(v) for v in patch]),
+                                              _ptr(point), fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
+                "gs_patch_clip_minmax")
+
     ADV_MODES = {"lsgan": 0, "vanilla": 1, "wgangp": 2, "nonsaturating": 3}
 
     def adv_loss(self, x, mode, target_is_real, label, loss=None, grad=None, grad_scale=None):

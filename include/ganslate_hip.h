@@ -496,6 +496,48 @@ int64_t gs_patch_zscore_ws_floats(void);
 int gs_patch_zscore(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
                     const int32_t* size, int32_t rescale, float lo, float hi, float* out, float* scratch, void* stream);
 
+/* ---- device-side multi-modal patch sampling (csrc/volsample.hip) ---------------------------------- */
+/* The training-patch path of the reference's HX4-PET dataset (projects/maastro_hx4_pet_translation/datasets/
+ * train_dataset.py, datasets/utils/patch_samplers.py, basic.py) on volumes and body masks resident in device memory.
+ *
+ * gs_voxel_draw draws one patch centre ("focal point") of a dense D x H x W case. mask: uint8, non-zero = body.
+ * weight: NULL (uniform schemes) or a volume of dtype GS_VOL_F32 / GS_VOL_I16 (weighted schemes). patch: host {d, h, w}.
+ * The valid zone of an axis is [floor(p / 2), size - ceil(p / 2)), upper bound exclusive; the weight of a voxel of the
+ * zone is (mask != 0) for mask-only draws and (mask != 0) * max(w, 0) for weighted ones (NaN counts as 0). With u in
+ * [0, 1), over the zone in C order:
+ *   mask-only: count = non-zero voxels, k = min((int64)floor(u * count), count - 1) in float64; the k-th non-zero voxel;
+ *   weighted:  C_i = float64 inclusive prefix sums, T their total; the first voxel with C_i > u * T, else the last voxel
+ *              of positive weight.
+ * This picks the voxel np.random.choice(p = map / map.sum()) picks from the same uniform. Mask-only draws are integer
+ * exact; weighted sums are taken in a fixed order (per run, per range, then over ranges), so a draw is bitwise
+ * reproducible, and equal to the C-order rule whenever the sums are exact.
+ * focal_a != NULL makes it the stochastic-focal draw of domain B: focal_a is a DEVICE int32[3] holding the point drawn in
+ * A, dims_a (host int32[3]) A's dims, proportion (host double[3]) the focal region proportions. In float64, per axis:
+ * f = (focal_a / dims_a) * size; region = (int)(proportion * size); box = [max((int)(f - region / 2), 0),
+ * min((int)(f + region / 2), size)). The draw is over zone ∩ body ∩ box; if that is empty, over zone ∩ body and
+ * out[3] = 1.
+ * out: device int32[4] = {z, y, x, fallback_used}; {-1, -1, -1, flag} when the set is empty or its total weight is 0.
+ * ws: gs_voxel_draw_ws_bytes() bytes, 8-byte aligned, private to the launch. No atomics, no host synchronisation.
+ * gs_voxel_draw_range_len: voxels of the zone's box each of the 256 workgroups of the first pass owns (for tests that
+ * aim at range boundaries); 0 for an empty zone. */
+int64_t gs_voxel_draw_ws_bytes(void);
+int64_t gs_voxel_draw_range_len(int32_t D, int32_t H, int32_t W, const int32_t* patch);
+int gs_voxel_draw(const uint8_t* mask, const void* weight, int32_t wdtype, int32_t D, int32_t H, int32_t W,
+                  const int32_t* patch, double u, const int32_t* focal_a, const int32_t* dims_a, const double* proportion,
+                  int32_t* out, void* ws, void* stream);
+/* gs_patch_clip_minmax: crop + normalise all C (1..GS_PATCH_MAX_MODALITIES) modalities of one case in one launch.
+ * vols / dtypes: host tables of C device volumes (all D x H x W) and their GS_VOL_* dtypes; mask: the case's body mask;
+ * point: DEVICE int32[3], the focal point; start = point - floor(patch / 2), clamped to [0, size - patch] per axis, so no
+ * point can make the kernel read outside a volume. outside / divisor / lo / hi: host float[C]. Per voxel, in fp32 with
+ * one IEEE operation per step:
+ *   v = mask ? (float)x : outside;  v = v / divisor;  v = min(max(v, lo), hi);  v = (v - lo) / (hi - lo);  v = 2 * v - 1
+ * (np.where(body_mask, image, fill), the per-case divisor, torch.clamp, min_max_normalize). out: dense [C, d, h, w] fp32.
+ * Shape, pointer, dtype, empty-range and zero-divisor errors are refused before the launch. */
+#define GS_PATCH_MAX_MODALITIES 8
+int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask, int32_t D,
+                         int32_t H, int32_t W, const int32_t* patch, const int32_t* point, const float* outside,
+                         const float* divisor, const float* lo, const float* hi, float* out, void* stream);
+
 /* ---- losses (fp32, on the boundary images / discriminator maps) --------------------------------- */
 /* loss[0] = mean((x-target)^2); if grad != NULL: grad = grad_scale * 2*(x-target)/n
  * (nn.MSELoss vs expanded constant, adversarial_loss.py:28-29,60-62) */
