@@ -507,13 +507,25 @@ __global__ __launch_bounds__(512) void hwgrad_wide_kernel(const HWGradK p) {
     rbk[ks] = ((lz * p.HH + ly) * p.HW + lx0 + 2 * frr) * GPITCH + wq * 32 + fcc * 8;   // byte offset incl. this lane's columns
   }
 
+  // The two waves of a SIMD stage the next box at OPPOSITE ends of the current one. A workgroup's waves go to the SIMDs
+  // cyclically, so waves 0-3 and waves 4-7 each put one wave on every SIMD. Staging is a latency chain, not issue work (box
+  // decode on the scalar unit, kernel arguments re-read through the scalar cache, the border tables' LDS round trip, 12 DMA
+  // issues through the one address unit of the CU): 2.6-3.3k cycles per wave per box whatever the partner does, next to
+  // 3.7k for a wave's 72 units when it has the matrix pipe to itself (in-kernel stamps, profiles/hwgrad_wide_stagger_ab.txt).
+  // With all 8 waves staging right behind the barrier a box was chain + units with both waves of a SIMD on the pipe at once,
+  // and waves 0-3, which win the issue arbitration, then waited 2.3k cycles at the next barrier. Now waves 4-7 stage first
+  // while waves 0-3 run their units alone on the pipe, and waves 0-3 stage AFTER their units, under those of waves 4-7.
+  // Buffer cur ^ 1 is free from the barrier on; whatever either group issued is covered by the vmcnt(0) + barrier at the top
+  // of the next box; the last box stages nothing. The unit stream itself is untouched, so the sums are bit-identical.
+  const bool late = wave < 4;                            // (wave-uniform)
   int cur = 0;
   int box = gx;
   if (box < p.nboxes) issue_box(box, 0);
   for (; box < p.nboxes; box += gnum) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this box landed (nothing else is outstanding)
     __syncthreads();                                     // ... for every wave; the other buffer is fully consumed
-    if (box + gnum < p.nboxes) issue_box(box + gnum, cur ^ 1);
+    const bool has_next = box + gnum < p.nboxes;
+    if (has_next && !late) issue_box(box + gnum, cur ^ 1);
     // ---- 8 K-steps x T taps as a rolling pipeline of "units" (one tap of one K-step = 2 transpose reads of the gathered
     // fragment, plus the 4 reads of the K-step's two dense fragments in front of tap 0; 2 MFMAs) ---------------------
     // The reads go through inline asm (common.hpp, lds_read128 family): with the LDS-DMA in this loop hipcc waits
@@ -553,6 +565,7 @@ __global__ __launch_bounds__(512) void hwgrad_wide_kernel(const HWGradK p) {
       acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, gf, acc[t][0], 0, 0, 0);
       acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, gf, acc[t][1], 0, 0, 0);
     });
+    if (has_next && late) issue_box(box + gnum, cur ^ 1);      // (the pipeline is drained: no fragment read in flight)
     cur ^= 1;
   }
 
