@@ -25,6 +25,20 @@ __device__ __forceinline__ unsigned pack_bf2(float a, float b) {
   return *reinterpret_cast<unsigned*>(&r);
 }
 __device__ __forceinline__ unsigned short f2bf(float a) { return (unsigned short)(pack_bf2(a, 0.f) & 0xffffu); }
+// 16 bytes = 8 bf16 channels <-> eight floats
+__device__ __forceinline__ void unpack_bf8(float* f, const uint4 v) {
+  f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
+  f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
+}
+__device__ __forceinline__ void add_bf8(float* f, const uint4 v) {
+  f[0] += bf_lo(v.x); f[1] += bf_hi(v.x); f[2] += bf_lo(v.y); f[3] += bf_hi(v.y);
+  f[4] += bf_lo(v.z); f[5] += bf_hi(v.z); f[6] += bf_lo(v.w); f[7] += bf_hi(v.w);
+}
+__device__ __forceinline__ uint4 pack_bf8(const float* f) {
+  uint4 o;
+  o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
+  return o;
+}
 
 // 16-byte LDS-DMA: LDS destination = wave-uniform base + lane*16; global source is per lane.
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {

@@ -13,9 +13,7 @@ __global__ __launch_bounds__(256) void image_to_act_kernel(const float* img, uns
       float f[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) f[k] = (c0 + k < C) ? in[(size_t)(c0 + k) * hw + p] : 0.f;
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = o;
+      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
     }
   }
 }
@@ -49,9 +47,7 @@ __global__ __launch_bounds__(256) void act_to_image_bwd_kernel(const float* g_im
         }
         f[k] = v;
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = o;
+      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
     }
   }
 }
@@ -132,9 +128,7 @@ __global__ __launch_bounds__(256) void image_pair_to_act_kernel(const float* a, 
         const int c = c0 + k;
         f[k] = c < Ca ? ia[(size_t)c * hw + p] : (c < C ? ib[(size_t)(c - Ca) * hw + p] : 0.f);
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = o;
+      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
     }
   }
 }
@@ -238,9 +232,7 @@ __global__ __launch_bounds__(256) void image_cat_to_act_kernel(const ChanSrcs s,
         }
         f[k] = v;
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = o;
+      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
     }
   }
 }

@@ -84,6 +84,10 @@ void gs_launch_slab_reduce(const float* ws, float* dst, long long n4, int slabs,
 // mean_rstd: the conv's bias gradient is added there too (shared with norm_ex.hip)
 int gs_launch_slot_sum3(const float* in, float* out, int N, int slots, int C, float inv_hw, const float* mean_rstd,
                         float* db, hipStream_t st);
+// norm.hip: the same for R = 3 or 4 sums per slot (R = 4, prelu.hip: the fourth total is the PReLU slope gradient, added to dslope);
+// narrow: 4 channels per workgroup, not 16. Several images: the parameter gradients go through gs_launch_norm_param_grads.
+int gs_launch_slot_sum(int R, bool narrow, const float* in, float* out, int N, int slots, int C, float inv_hw,
+                       const float* mean_rstd, float* db, float* dslope, hipStream_t st);
 // norm.hip: parameter gradients (bias, PReLU slope) summed over the images in a fixed order (shared with prelu.hip)
 int gs_launch_norm_param_grads(const float* sums, int R, const float* mean_rstd, float* db, float* dslope, int N, int C,
                                float inv_hw, hipStream_t st);

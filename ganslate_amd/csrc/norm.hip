@@ -3,7 +3,7 @@
 // Replaces nn.InstanceNorm2d(eps=1e-5, affine=False, track_running_stats=False) + nn.ReLU / nn.LeakyReLU
 // (ganslate/nn/utils.py:53-59; resnet2d.py:26-27,36-37,83-87,93; patchgan2d.py:45-46,58-59) and their
 // autograd backward, including the adjoint of nn.ReflectionPad2d (the `fold`).
-#include "internal.hpp"
+#include "norm_common.hpp"
 #include <cstdlib>
 
 // ---- slot reduction: in [N][slots][R][C] -> per (n, c) totals over the slots ---------------------------------------
@@ -12,19 +12,26 @@
 //  R == 2 (forward): totals are (sum y, sum y^2)  -> out [N][2][C] = (mean, rstd)
 //  R == 3 (backward): totals are (sum ghat, sum ghat*yhat, sum yhat) -> out [N][3][C]; optionally the bias gradient of
 //           the conv in front of the norm, db[c] += sum_n -rstd * S2 * S3 / hw  (= sum_pixels dy, see norm backward)
-template <int R, int CH = 16>
+//  R == 4 (V-Net backward, prelu.hip): a fourth total, sum g*min(u,0) -> out [N][4][C]; optionally dslope[c] += S4
+// TREE: the lanes of a channel are combined by a fixed-shape tree (R == 2, 3), else one thread per sum adds them in lane order
+// (R == 4). Both are deterministic; each caller keeps the order, and with it the bits, it has always had.
+template <int R, int CH, bool TREE>
 __global__ __launch_bounds__(256) void slot_sum_kernel(const float* in, float* out, int slots, int C, float inv_hw,
-                                                       float eps, const float* mean_rstd, float* db) {
+                                                       float eps, const float* mean_rstd, float* db, float* dslope) {
   constexpr int LANES = 256 / CH;
   __shared__ double red[R][LANES][CH + 1];
+  __shared__ float tot[R][CH];                    // (!TREE) the totals, rounded to float once
+  static_assert(TREE || LANES >= R, "the serial combine takes one lane per sum");
   const int n = blockIdx.y;
   const int tid = threadIdx.x;
   const int col = tid % CH, lane = tid / CH;
   const int c = blockIdx.x * CH + col;
   const float* src = in + (size_t)n * slots * R * C;
-  // all R sums of a channel in one sweep (R x 4 loads in flight per thread, additions in slot order per lane), then a
-  // fixed-shape tree over the lanes: the narrow layers of the V-Nets / Piresnet (8 workgroups of this kernel per launch)
-  // spent 8-16 us here walking R serial phases with a 64-term sum on one thread each
+  // all R sums of a channel in one sweep (the R rows of a slot are neighbours: R x 4 loads in flight per thread, additions per
+  // sum in slot order per lane), then the lanes: the narrow layers of the V-Nets / Piresnet (8 workgroups of this kernel per
+  // launch) spent 8-16 us here walking R serial phases with a 64-term sum on one thread each; for R == 4 the four serial
+  // sweeps cost 16 dependent memory round trips and three workgroup barriers more, 8-12 us per launch, 148 launches per V-Net
+  // step
   double s[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) s[r] = 0.0;
@@ -48,13 +55,24 @@ __global__ __launch_bounds__(256) void slot_sum_kernel(const float* in, float* o
 #pragma unroll
   for (int r = 0; r < R; ++r) red[r][lane][col] = s[r];
   __syncthreads();
-  for (int w = LANES / 2; w > 0; w >>= 1) {
-    if (lane < w) {
+  if constexpr (TREE) {
+    for (int w = LANES / 2; w > 0; w >>= 1) {
+      if (lane < w) {
 #pragma unroll
-      for (int r = 0; r < R; ++r) red[r][lane][col] += red[r][lane + w][col];
+        for (int r = 0; r < R; ++r) red[r][lane][col] += red[r][lane + w][col];
+      }
+      __syncthreads();
+    }
+  } else {
+    if (lane < R) {                                // sum r = lane over the lanes, in lane order
+      double t = 0.0;
+#pragma unroll
+      for (int l = 0; l < LANES; ++l) t += red[lane][l][col];
+      tot[lane][col] = (float)t;
     }
     __syncthreads();
   }
+  auto total = [&](int r) { return TREE ? (float)red[r][0][col] : tot[r][col]; };
   if (lane == 0 && c < C) {
     if (R == 2) {
       const double mean = red[0][0][col] * (double)inv_hw;
@@ -64,12 +82,19 @@ __global__ __launch_bounds__(256) void slot_sum_kernel(const float* in, float* o
       out[(size_t)n * 2 * C + C + c] = (float)(1.0 / sqrt(var + (double)eps));
     } else {
 #pragma unroll
-      for (int r = 0; r < R; ++r) out[((size_t)n * R + r) * C + c] = (float)red[r][0][col];
-      if (R == 3 && gridDim.y == 1 && db && mean_rstd) {
-        // one image: its totals give the bias gradient right here — norm_param_grads_kernel's arithmetic with its sum over one
-        // image (gs_launch_slot_sum3 then skips that launch)
-        const float t1 = (float)red[1][0][col], t2 = (float)red[2][0][col];
-        db[c] = __fadd_rn(db[c], __fmul_rn(__fmul_rn(__fmul_rn(-mean_rstd[C + c], t1), t2), inv_hw));
+      for (int r = 0; r < R; ++r) out[((size_t)n * R + r) * C + c] = total(r);
+      // one image: its totals ARE the parameter gradients — norm_param_grads_kernel's arithmetic with its sum over one image,
+      // here instead of a launch of one workgroup behind this one (184 such launches per V-Net step at batch 1;
+      // gs_launch_slot_sum then skips that launch)
+      // (one condition for R == 3, nested for R == 4, as the two kernels this was had it: each keeps its instruction stream)
+      auto add_db = [&] {
+        db[c] = __fadd_rn(db[c], __fmul_rn(__fmul_rn(__fmul_rn(-mean_rstd[C + c], total(1)), total(2)), inv_hw));
+      };
+      if (R == 3) {
+        if (gridDim.y == 1 && db && mean_rstd) add_db();
+      } else if (gridDim.y == 1) {
+        if (db && mean_rstd) add_db();
+        if (dslope) dslope[c] = __fadd_rn(dslope[c], total(R - 1));
       }
     }
   }
@@ -105,25 +130,44 @@ int gs_launch_norm_param_grads(const float* sums, int R, const float* mean_rstd,
   return 0;
 }
 
-extern "C" int gs_inorm_finalize(const float* partial, int32_t N, int32_t slots, int32_t C, int64_t hw, float eps,
-                                 float* mean_rstd, void* stream) {
-  GS_REQUIRE(partial && mean_rstd && N > 0 && slots > 0 && C > 0 && hw > 0, "gs_inorm_finalize: bad argument");
-  if (slots > 256 && (long long)N * ((C + 15) / 16) < 128)      // few workgroups, long slot loops: 4x the workgroups
-    hipLaunchKernelGGL((slot_sum_kernel<2, 4>), dim3((C + 3) / 4, N), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       partial, mean_rstd, slots, C, 1.0f / (float)hw, eps, (const float*)nullptr, (float*)nullptr);
+// one launch of slot_sum_kernel<R>; narrow: 4 channels per workgroup, not 16 (which layers want that is the callers' knowledge)
+template <int R>
+static int launch_slot_sum(bool narrow, const float* in, float* out, int N, int slots, int C, float inv_hw, float eps,
+                           const float* mean_rstd, float* db, float* dslope, hipStream_t st) {
+  if (narrow)
+    hipLaunchKernelGGL((slot_sum_kernel<R, 4, R != 4>), dim3((C + 3) / 4, N), dim3(256), 0, st, in, out, slots, C, inv_hw, eps,
+                       mean_rstd, db, dslope);
   else
-    hipLaunchKernelGGL((slot_sum_kernel<2>), dim3((C + 15) / 16, N), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       partial, mean_rstd, slots, C, 1.0f / (float)hw, eps, (const float*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL((slot_sum_kernel<R, 16, R != 4>), dim3((C + 15) / 16, N), dim3(256), 0, st, in, out, slots, C, inv_hw,
+                       eps, mean_rstd, db, dslope);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
+// backward totals (R = 3, 4) and the parameter gradients they give: in the kernel for one image, by norm_param_grads else
+int gs_launch_slot_sum(int R, bool narrow, const float* in, float* out, int N, int slots, int C, float inv_hw,
+                       const float* mean_rstd, float* db, float* dslope, hipStream_t st) {
+  if (int rc = R == 4 ? launch_slot_sum<4>(narrow, in, out, N, slots, C, inv_hw, 0.f, mean_rstd, db, dslope, st)
+                      : launch_slot_sum<3>(narrow, in, out, N, slots, C, inv_hw, 0.f, mean_rstd, db, nullptr, st))
+    return rc;
+  if (N == 1) return 0;      // (one image: the parameter gradients were added by the kernel above)
+  return gs_launch_norm_param_grads(out, R, mean_rstd, db, R == 4 ? dslope : nullptr, N, C, inv_hw, st);
+}
+int gs_launch_slot_sum3(const float* in, float* out, int N, int slots, int C, float inv_hw, const float* mean_rstd,
+                        float* db, hipStream_t st) {
+  // few workgroups, long slot loops: 4x the workgroups
+  return gs_launch_slot_sum(3, slots > 256 && (long long)N * ((C + 15) / 16) < 128, in, out, N, slots, C, inv_hw, mean_rstd, db,
+                            nullptr, st);
+}
+
+extern "C" int gs_inorm_finalize(const float* partial, int32_t N, int32_t slots, int32_t C, int64_t hw, float eps,
+                                 float* mean_rstd, void* stream) {
+  GS_REQUIRE(partial && mean_rstd && N > 0 && slots > 0 && C > 0 && hw > 0, "gs_inorm_finalize: bad argument");
+  // few workgroups, long slot loops: 4x the workgroups
+  return launch_slot_sum<2>(slots > 256 && (long long)N * ((C + 15) / 16) < 128, partial, mean_rstd, N, slots, C,
+                            1.0f / (float)hw, eps, nullptr, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
 
 // ---- forward apply -----------------------------------------------------------------------------------
-__device__ __forceinline__ void load8(float* f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
 // A thread keeps its 8-channel group across iterations (the grid stride is a multiple of C8 whenever C8 divides 256: every
 // power-of-two channel count), so mean / rstd are fetched once per thread, and a thread handles several 16-byte elements
 // (one element per thread with four 16-byte statistic loads next to it ran the 256^2 x 64 layers at 2.6 TB/s).
@@ -149,16 +193,12 @@ __global__ __launch_bounds__(256) void inorm_act_fwd_kernel(const uint4* y, cons
       load8(mu, mr + c8 * 8);
       load8(rs, mr + C8 * 8 + c8 * 8);
     }
-    float f[8] = {bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y), bf_lo(v.z), bf_hi(v.z), bf_lo(v.w), bf_hi(v.w)};
+    float f[8];
+    unpack_bf8(f, v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[k] = apply_act_small((f[k] - mu[k]) * rs[k], act, slope);
-    if (rn) {
-      f[0] += bf_lo(r.x); f[1] += bf_hi(r.x); f[2] += bf_lo(r.y); f[3] += bf_hi(r.y);
-      f[4] += bf_lo(r.z); f[5] += bf_hi(r.z); f[6] += bf_lo(r.w); f[7] += bf_hi(r.w);
-    }
-    uint4 o;
-    o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-    xn[e] = o;
+    if (rn) add_bf8(f, r);
+    xn[e] = pack_bf8(f);
   };
   long long e = e0;
   for (; e + stride < per_img; e += 2 * stride) {          // two elements in flight per thread
@@ -269,16 +309,12 @@ __global__ __launch_bounds__(256) void inorm_stats_act_fwd_kernel(const uint4* y
 #pragma unroll
   for (int k = 0; k < 8; ++k) { mu[k] = mrs[0][cl * 8 + k]; rs[k] = mrs[1][cl * 8 + k]; }
   auto finish = [&](const uint4& v, const uint4& r, size_t e) {
-    float f[8] = {bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y), bf_lo(v.z), bf_hi(v.z), bf_lo(v.w), bf_hi(v.w)};
+    float f[8];
+    unpack_bf8(f, v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[k] = apply_act((f[k] - mu[k]) * rs[k], act, slope);
-    if (res) {
-      f[0] += bf_lo(r.x); f[1] += bf_hi(r.x); f[2] += bf_lo(r.y); f[3] += bf_hi(r.y);
-      f[4] += bf_lo(r.z); f[5] += bf_hi(r.z); f[6] += bf_lo(r.w); f[7] += bf_hi(r.w);
-    }
-    uint4 o;
-    o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-    x[e] = o;
+    if (res) add_bf8(f, r);
+    x[e] = pack_bf8(f);
   };
   if (pxa < p1) finish(va, ra, ea);
   if (pxb < p1) finish(vb, rb, eb);
@@ -343,11 +379,6 @@ __device__ __forceinline__ void fold_range(int x, int n, int p, int& lo, int& hi
   hi = x == n - 1 ? n - 1 + 2 * p : x + p;
 }
 
-__device__ __forceinline__ void add_bf8(float* f, const uint4 v) {
-  f[0] += bf_lo(v.x); f[1] += bf_hi(v.x); f[2] += bf_lo(v.y); f[3] += bf_hi(v.y);
-  f[4] += bf_lo(v.z); f[5] += bf_hi(v.z); f[6] += bf_lo(v.w); f[7] += bf_hi(v.w);
-}
-
 // px = (iz*H + ih)*W + iw is the unpadded pixel index; the depth axis is only padded when D > 1
 // FM (compile-time fold mode): 0 = no fold, 1 = reflect 2-D, 2 = reflect 3-D, 3 = replicate
 template <int FM>
@@ -405,12 +436,7 @@ __device__ __forceinline__ size_t padded_pixels(int D, int H, int W, int fold) {
   return (size_t)(D > 1 ? D + 2 * fold : D) * (H + 2 * fold) * (W + 2 * fold);
 }
 
-__device__ __forceinline__ void unpack8(float* f, const uint4 v) {
-  f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
-  f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
-}
-
-// pass 1: per (n, pixel-chunk, column group) partial sums of ghat and ghat*yhat  -> scratch [N][chunks][2][C]
+// pass 1: per (n, pixel-chunk, column group) partial sums of ghat, ghat*yhat and yhat  -> scratch [N][chunks][3][C]
 // 256 threads = COLS 8-channel columns x (256/COLS) pixel lanes; grid (chunks, N, ceil(C8/COLS))
 template <int COLS, int FM>
 __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const uint4* gpad, const uint4* g2, const uint4* y,
@@ -419,8 +445,7 @@ __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const uint4* gpad
                                                                float slope, int pix_per_block, int chunks) {
   constexpr int ROWS = 256 / COLS;
   __shared__ float red[ROWS][COLS][25];
-  const int n = blockIdx.y;
-  const int tid = threadIdx.x;
+  const int n = blockIdx.y, tid = threadIdx.x;
   const int col = tid % COLS, row = tid / COLS;
   const int c8 = blockIdx.z * COLS + col;
   const int HW = D * H * W;
@@ -446,8 +471,8 @@ __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const uint4* gpad
       const uint4 yb = y_n[(size_t)(px + ROWS) * C8 + c8];
       load_folded<FM>(g, gpad_n, g2_n, px, D, H, W, C8, c8, fold);
       load_folded<FM>(g_b, gpad_n, g2_n, px + ROWS, D, H, W, C8, c8, fold);
-      unpack8(yy, ya);
-      unpack8(yy_b, yb);
+      unpack_bf8(yy, ya);
+      unpack_bf8(yy_b, yb);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float yh = (yy[k] - mu[k]) * rs[k];
@@ -462,7 +487,7 @@ __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const uint4* gpad
     for (; px < p1; px += ROWS) {
       float g[8], yy[8];
       load_folded<FM>(g, gpad_n, g2_n, px, D, H, W, C8, c8, fold);
-      unpack8(yy, y_n[(size_t)px * C8 + c8]);
+      unpack_bf8(yy, y_n[(size_t)px * C8 + c8]);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float yh = (yy[k] - mu[k]) * rs[k];
@@ -473,21 +498,7 @@ __global__ __launch_bounds__(256) void inorm_bwd_reduce_kernel(const uint4* gpad
       }
     }
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { red[row][col][k] = a1[k]; red[row][col][8 + k] = a2[k]; red[row][col][16 + k] = a3[k]; }
-  __syncthreads();
-  // COLS*24 outputs, summed over ROWS pixel lanes
-  for (int o = tid; o < COLS * 24; o += 256) {
-    const int cc = o / 24, k = o - cc * 24;
-    const int ch8 = blockIdx.z * COLS + cc;
-    if (ch8 < C8) {
-      float sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) sum += red[r][cc][k];
-      float* out = partial + ((size_t)n * chunks + blockIdx.x) * 3 * C8 * 8;
-      out[(k >> 3) * C8 * 8 + ch8 * 8 + (k & 7)] = sum;
-    }
-  }
+  row_fold(red, partial, n, chunks, C8, a1, a2, a3);
 }
 
 // pass 2: dy = rstd * (ghat - S1/hw - yhat*S2/hw) ; optional gsum = folded gradient (before act')
@@ -533,12 +544,8 @@ __global__ __launch_bounds__(256) void inorm_bwd_apply_kernel(const uint4* gpad,
     } else {
       load_folded<FM>(g, gpad_n, g2_n, (int)px, D, H, W, C8, c8, fold);
     }
-    if (gs_n) {
-      uint4 o;
-      o.x = pack_bf2(g[0], g[1]); o.y = pack_bf2(g[2], g[3]); o.z = pack_bf2(g[4], g[5]); o.w = pack_bf2(g[6], g[7]);
-      gs_n[e] = o;
-    }
-    unpack8(yy, y_n[e]);
+    if (gs_n) gs_n[e] = pack_bf8(g);
+    unpack_bf8(yy, y_n[e]);
     if (mr) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
@@ -550,9 +557,7 @@ __global__ __launch_bounds__(256) void inorm_bwd_apply_kernel(const uint4* gpad,
 #pragma unroll
       for (int k = 0; k < 8; ++k) d[k] = g[k] * act_grad_from_out(yy[k], act, slope);
     }
-    uint4 o;
-    o.x = pack_bf2(d[0], d[1]); o.y = pack_bf2(d[2], d[3]); o.z = pack_bf2(d[4], d[5]); o.w = pack_bf2(d[6], d[7]);
-    dy_n[e] = o;
+    dy_n[e] = pack_bf8(d);
   }
 }
 
@@ -609,20 +614,14 @@ __global__ __launch_bounds__(256) void inorm_bwd_apply_cg_kernel(const uint4* gp
   auto finish = [&](const float* g, const uint4& yv, int px) {
     const size_t e = (size_t)px * C8 + c8;
     float yy[8], d[8];
-    if (gs_n) {
-      uint4 o;
-      o.x = pack_bf2(g[0], g[1]); o.y = pack_bf2(g[2], g[3]); o.z = pack_bf2(g[4], g[5]); o.w = pack_bf2(g[6], g[7]);
-      gs_n[e] = o;
-    }
-    unpack8(yy, yv);
+    if (gs_n) gs_n[e] = pack_bf8(g);
+    unpack_bf8(yy, yv);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float yh = (yy[k] - mu[k]) * rs[k];
       d[k] = inorm_dy(g[k], yh, act_grad_from_out(yh, act, slope), s1[k], s2[k], rs[k]);
     }
-    uint4 o;
-    o.x = pack_bf2(d[0], d[1]); o.y = pack_bf2(d[2], d[3]); o.z = pack_bf2(d[4], d[5]); o.w = pack_bf2(d[6], d[7]);
-    dy_n[e] = o;
+    dy_n[e] = pack_bf8(d);
   };
   if (pxa < p1) finish(ga, ya, pxa);
   if (pxb < p1) finish(gb, yb, pxb);
@@ -631,19 +630,6 @@ __global__ __launch_bounds__(256) void inorm_bwd_apply_cg_kernel(const uint4* gp
     load_folded<FM>(g, gpad_n, g2_n, px, D, H, W, C8, c8, fold);
     finish(g, y_n[(size_t)px * C8 + c8], px);
   }
-}
-
-int gs_launch_slot_sum3(const float* in, float* out, int N, int slots, int C, float inv_hw, const float* mean_rstd,
-                        float* db, hipStream_t st) {
-  if (slots > 256 && (long long)N * ((C + 15) / 16) < 128)      // few workgroups, long slot loops: 4x the workgroups
-    hipLaunchKernelGGL((slot_sum_kernel<3, 4>), dim3((C + 3) / 4, N), dim3(256), 0, st, in, out, slots, C, inv_hw, 0.f,
-                       mean_rstd, db);
-  else
-    hipLaunchKernelGGL((slot_sum_kernel<3>), dim3((C + 15) / 16, N), dim3(256), 0, st, in, out, slots, C, inv_hw, 0.f,
-                       mean_rstd, db);
-  GS_CHECK_HIP(hipGetLastError());
-  if (N == 1) return 0;      // (one image: the bias gradient was added by the kernel above)
-  return gs_launch_norm_param_grads(out, 3, mean_rstd, db, nullptr, N, C, inv_hw, st);
 }
 
 // Bias gradients of the convs in front of InstanceNorms for MANY layers in one launch: item i adds
@@ -681,8 +667,6 @@ extern "C" int gs_norm_bias_grads(const gs_norm_db_item* items, int32_t count, v
   return 0;
 }
 
-// pixels per block of the reduction pass: 64 for 2-D sized maps, more for volumes so that the second-level sum
-// stays at <= 4096 slots per image
 // pixels per workgroup of the reduction pass: about 4096 workgroups over the whole batch, at least 64 pixels each (per image
 // it ran the 256^2 x 64 layers of a 16-image twin batch as 16384 workgroups of two pixels per thread: +0.35 % on the step)
 static int bwd_pix_per_block(long long pixels, int N) {
@@ -700,6 +684,16 @@ extern "C" int64_t gs_inorm_backward_scratch_floats(int32_t N, int32_t D, int32_
   return (int64_t)N * (chunks + 1) * 3 * C;
 }
 
+// launch(std::integral_constant<int, FM>) for the compile-time fold mode of the kernels: 0 none, 1 reflect 2-D, 2 reflect 3-D,
+// 3 replicate
+template <class F>
+static void by_fold_mode(int fm, F&& launch) {
+  if (fm == 0) launch(std::integral_constant<int, 0>{});
+  else if (fm == 1) launch(std::integral_constant<int, 1>{});
+  else if (fm == 2) launch(std::integral_constant<int, 2>{});
+  else launch(std::integral_constant<int, 3>{});
+}
+
 extern "C" int gs_inorm_act_backward(const void* g_pad, const void* g2, const void* y, const float* mean_rstd,
                                      void* dy, void* gsum, float* scratch, float* bias_grad, int32_t N, int32_t D,
                                      int32_t H, int32_t W, int32_t C, int32_t fold, int32_t fold_mode, int32_t act,
@@ -715,7 +709,6 @@ extern "C" int gs_inorm_act_backward(const void* g_pad, const void* g2, const vo
   const int C8 = C / 8;
   const int HW = D * H * W;
   const int kBwdPixPerBlock = bwd_pix_per_block(HW, N);
-  // compile-time fold mode of the kernels: 0 none, 1 reflect 2-D, 2 reflect 3-D, 3 replicate
   const int fm = fold == 0 ? 0 : (fold_mode == GS_BORDER_REFLECT ? (D == 1 ? 1 : 2) : 3);
   float* sums = nullptr;
   if (mean_rstd) {
@@ -723,25 +716,16 @@ extern "C" int gs_inorm_act_backward(const void* g_pad, const void* g2, const vo
     const int chunks = pre_slots > 0 ? pre_slots : (HW + kBwdPixPerBlock - 1) / kBwdPixPerBlock;
     sums = scratch + (size_t)N * chunks * 3 * C;
     if (pre_slots <= 0) {
-#define GS_LAUNCH_REDUCE2(COLS, FM)                                                                                   \
-  hipLaunchKernelGGL((inorm_bwd_reduce_kernel<COLS, FM>), dim3(chunks, N, (C8 + COLS - 1) / COLS), dim3(256), 0, st, \
-                     static_cast<const uint4*>(g_pad), static_cast<const uint4*>(g2), static_cast<const uint4*>(y),     \
-                     mean_rstd, scratch, D, H, W, C8, fold, fold_mode, act, slope, kBwdPixPerBlock, chunks)
-#define GS_LAUNCH_REDUCE(COLS)                                        \
-  do {                                                                \
-    if (fm == 0) GS_LAUNCH_REDUCE2(COLS, 0);                          \
-    else if (fm == 1) GS_LAUNCH_REDUCE2(COLS, 1);                     \
-    else if (fm == 2) GS_LAUNCH_REDUCE2(COLS, 2);                     \
-    else GS_LAUNCH_REDUCE2(COLS, 3);                                  \
-  } while (0)
-    if (C8 >= 32) GS_LAUNCH_REDUCE(32);
-    else if (C8 >= 8) GS_LAUNCH_REDUCE(8);
-    else if (C8 >= 4) GS_LAUNCH_REDUCE(4);      // 32- / 16-channel layers: the columns of a pixel in one workgroup
-    else if (C8 >= 2) GS_LAUNCH_REDUCE(2);
-    else GS_LAUNCH_REDUCE(1);
-#undef GS_LAUNCH_REDUCE
-#undef GS_LAUNCH_REDUCE2
-    GS_CHECK_HIP(hipGetLastError());
+      // (COLS 4 and 2, the 32- / 16-channel layers: the columns of a pixel in one workgroup)
+      norm_by_cols<32, 8, 4, 2, 1>(C8, [&](auto cols) {
+        by_fold_mode(fm, [&](auto mode) {
+          constexpr int COLS = decltype(cols)::value, FM = decltype(mode)::value;
+          hipLaunchKernelGGL((inorm_bwd_reduce_kernel<COLS, FM>), dim3(chunks, N, (C8 + COLS - 1) / COLS), dim3(256), 0, st,
+                             static_cast<const uint4*>(g_pad), static_cast<const uint4*>(g2), static_cast<const uint4*>(y),
+                             mean_rstd, scratch, D, H, W, C8, fold, fold_mode, act, slope, kBwdPixPerBlock, chunks);
+        });
+      });
+      GS_CHECK_HIP(hipGetLastError());
     }
     if ((C & 63) == 0 && chunks <= 64) {
       // wide layers with few slots: the apply pass sums the slots of its own 64 channels in its prologue (no slot_sum
@@ -764,16 +748,13 @@ extern "C" int gs_inorm_act_backward(const void* g_pad, const void* g2, const vo
         const long long per = (long long)(C / 64) * N;
         while (ppb < 256 && per * ((HW + ppb - 1) / ppb) > slots && per * ((HW + ppb + 31) / (ppb + 32)) >= slots / 2) ppb += 32;
       }
-#define GS_LAUNCH_APPLY_CG(FM)                                                                                      \
-  hipLaunchKernelGGL((inorm_bwd_apply_cg_kernel<FM>), dim3((unsigned)(C / 64) * (unsigned)((HW + ppb - 1) / ppb) * N), dim3(256), 0, \
-                     st, static_cast<const uint4*>(g_pad), static_cast<const uint4*>(g2),                            \
-                     static_cast<const uint4*>(y), mean_rstd, scratch, chunks, static_cast<uint4*>(dy),              \
-                     static_cast<uint4*>(gsum), sums, D, H, W, C8, fold, act, slope, ppb, (int)((HW + ppb - 1) / ppb))
-      if (fm == 0) GS_LAUNCH_APPLY_CG(0);
-      else if (fm == 1) GS_LAUNCH_APPLY_CG(1);
-      else if (fm == 2) GS_LAUNCH_APPLY_CG(2);
-      else GS_LAUNCH_APPLY_CG(3);
-#undef GS_LAUNCH_APPLY_CG
+      const int nchunks = (HW + ppb - 1) / ppb;
+      by_fold_mode(fm, [&](auto mode) {
+        hipLaunchKernelGGL((inorm_bwd_apply_cg_kernel<decltype(mode)::value>), dim3((unsigned)(C / 64) * (unsigned)nchunks * N),
+                           dim3(256), 0, st, static_cast<const uint4*>(g_pad), static_cast<const uint4*>(g2),
+                           static_cast<const uint4*>(y), mean_rstd, scratch, chunks, static_cast<uint4*>(dy),
+                           static_cast<uint4*>(gsum), sums, D, H, W, C8, fold, act, slope, ppb, nchunks);
+      });
       GS_CHECK_HIP(hipGetLastError());
       // per-image totals are at `sums` now; the bias gradient, if asked for here, is one more tiny launch (executors
       // pass bias_grad = NULL and batch all their norm layers into one gs_norm_bias_grads call)
@@ -784,21 +765,12 @@ extern "C" int gs_inorm_act_backward(const void* g_pad, const void* g2, const vo
   const long long per_img = (long long)HW * C8;
   GS_REQUIRE(per_img < (1LL << 31), "gs_inorm_act_backward: image too large");
   const int apply_u = gs_opt(GS_OPT_NORM_APPLY_UNROLL);   // elements per thread
-  long long bx = (per_img + 256LL * apply_u - 1) / (256LL * apply_u);
-  if (bx > 1024) bx = 1024;
-  if (bx < 1) bx = 1;
-  int c8_shift = -1;
-  if ((C8 & (C8 - 1)) == 0) { c8_shift = 0; while ((1 << c8_shift) < C8) ++c8_shift; }
-#define GS_LAUNCH_APPLY(FM)                                                                                        \
-  hipLaunchKernelGGL((inorm_bwd_apply_kernel<FM>), dim3((unsigned)bx, N), dim3(256), 0, st,                         \
-                     static_cast<const uint4*>(g_pad), static_cast<const uint4*>(g2), static_cast<const uint4*>(y), \
-                     mean_rstd, sums, static_cast<uint4*>(dy), static_cast<uint4*>(gsum), D, H, W, C8, c8_shift,    \
-                     fold, fold_mode, act, slope)
-  if (fm == 0) GS_LAUNCH_APPLY(0);
-  else if (fm == 1) GS_LAUNCH_APPLY(1);
-  else if (fm == 2) GS_LAUNCH_APPLY(2);
-  else GS_LAUNCH_APPLY(3);
-#undef GS_LAUNCH_APPLY
+  by_fold_mode(fm, [&](auto mode) {
+    hipLaunchKernelGGL((inorm_bwd_apply_kernel<decltype(mode)::value>), dim3(norm_grid(per_img, 1024, apply_u), N), dim3(256), 0,
+                       st, static_cast<const uint4*>(g_pad), static_cast<const uint4*>(g2), static_cast<const uint4*>(y),
+                       mean_rstd, sums, static_cast<uint4*>(dy), static_cast<uint4*>(gsum), D, H, W, C8, norm_c8_shift(C8),
+                       fold, fold_mode, act, slope);
+  });
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -7,7 +7,7 @@
 // With mean_rstd == NULL there is no norm and `y` holds a sign-preserving activation output (conv epilogue LeakyReLU).
 // HBM-bound streaming kernels: 16 B per lane, fp32 math. Dropout masks come from a counter-based hash of
 // (seed, image, element) so the backward pass regenerates them instead of storing them.
-#include "internal.hpp"
+#include "norm_common.hpp"
 
 struct NormExK {
   gs_norm_ex_desc d;
@@ -32,21 +32,6 @@ __device__ __forceinline__ float drop_scale(const gs_norm_ex_desc& d, int n, uns
   return u >= d.drop_p ? 1.0f / (1.0f - d.drop_p) : 0.f;
 }
 
-__device__ __forceinline__ void ex_load8(float* f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-__device__ __forceinline__ void ex_unpack8(float* f, const uint4 v) {
-  f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
-  f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
-}
-__device__ __forceinline__ uint4 ex_pack8(const float* f) {
-  uint4 o;
-  o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-  return o;
-}
-
 __global__ __launch_bounds__(256) void norm_ex_fwd_kernel(const NormExK p, const uint4* y, const float* mean_rstd,
                                                           unsigned short* x1, unsigned short* x2) {
   const gs_norm_ex_desc& d = p.d;
@@ -58,11 +43,11 @@ __global__ __launch_bounds__(256) void norm_ex_fwd_kernel(const NormExK p, const
     const unsigned px = e / (unsigned)p.C8;
     const int c8 = (int)(e - px * (unsigned)p.C8);
     float v[8], a[8];
-    ex_unpack8(v, yn[e]);
+    unpack_bf8(v, yn[e]);
     if (mr) {
       float mu[8], rs[8];
-      ex_load8(mu, mr + c8 * 8);
-      ex_load8(rs, mr + d.C + c8 * 8);
+      load8(mu, mr + c8 * 8);
+      load8(rs, mr + d.C + c8 * 8);
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = (v[k] - mu[k]) * rs[k];
     }
@@ -71,11 +56,11 @@ __global__ __launch_bounds__(256) void norm_ex_fwd_kernel(const NormExK p, const
     const size_t pix = (size_t)n * p.HW + px;
 #pragma unroll
     for (int k = 0; k < 8; ++k) a[k] = apply_act(v[k], d.act1, d.slope);
-    *reinterpret_cast<uint4*>(x1 + pix * d.x1_cs + d.x1_co + c8 * 8) = ex_pack8(a);
+    *reinterpret_cast<uint4*>(x1 + pix * d.x1_cs + d.x1_co + c8 * 8) = pack_bf8(a);
     if (x2) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) a[k] = apply_act(v[k], d.act2, d.slope);
-      *reinterpret_cast<uint4*>(x2 + pix * d.x2_cs + d.x2_co + c8 * 8) = ex_pack8(a);
+      *reinterpret_cast<uint4*>(x2 + pix * d.x2_cs + d.x2_co + c8 * 8) = pack_bf8(a);
     }
   }
 }
@@ -98,8 +83,8 @@ __device__ __forceinline__ void ex_ghat_from(const NormExK& p, int n, unsigned p
                                              bool g2, const float* yh, float* gh) {
   const gs_norm_ex_desc& d = p.d;
   float a[8], b[8];
-  ex_unpack8(a, av);
-  if (g2) ex_unpack8(b, bv);
+  unpack_bf8(a, av);
+  if (g2) unpack_bf8(b, bv);
   const unsigned e8 = (px * (unsigned)p.C8 + (unsigned)c8) * 8u;
   float t[8];
   if (d.act1 != GS_ACT_TANH && d.act2 != GS_ACT_TANH) {      // (uniform)
@@ -154,8 +139,8 @@ __global__ __launch_bounds__(256) void norm_ex_bwd_reduce_kernel(const NormExK p
   for (int k = 0; k < 8; ++k) a1[k] = a2[k] = a3[k] = 0.f;
   if (c8 < p.C8) {
     float mu[8], rs[8];
-    ex_load8(mu, mr + c8 * 8);
-    ex_load8(rs, mr + d.C + c8 * 8);
+    load8(mu, mr + c8 * 8);
+    load8(rs, mr + d.C + c8 * 8);
     // Four pixels' operands are requested before the first is used: taken one at a time, the 16-workgroup launches of the inner
     // U-Net levels spent 13-17 us on eight serial trips to memory. (Sums in pixel order, as before.)
     constexpr int U = 4;
@@ -174,7 +159,7 @@ __global__ __launch_bounds__(256) void norm_ex_bwd_reduce_kernel(const NormExK p
         const unsigned px = pb + u * ROWS;
         if (px < p1) {
           float yh[8], gh[8];
-          ex_unpack8(yh, yv[u]);
+          unpack_bf8(yh, yv[u]);
 #pragma unroll
           for (int k = 0; k < 8; ++k) yh[k] = (yh[k] - mu[k]) * rs[k];
           ex_ghat_from(p, n, px, c8, av[u], bv[u], g2 != nullptr, yh, gh);
@@ -184,20 +169,7 @@ __global__ __launch_bounds__(256) void norm_ex_bwd_reduce_kernel(const NormExK p
       }
     }
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { red[row][col][k] = a1[k]; red[row][col][8 + k] = a2[k]; red[row][col][16 + k] = a3[k]; }
-  __syncthreads();
-  for (int o = tid; o < COLS * 24; o += 256) {
-    const int cc = o / 24, k = o - cc * 24;
-    const int ch8 = blockIdx.z * COLS + cc;
-    if (ch8 < p.C8) {
-      float sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) sum += red[r][cc][k];
-      float* out = partial + ((size_t)n * chunks + blockIdx.x) * 3 * d.C;
-      out[(k >> 3) * d.C + ch8 * 8 + (k & 7)] = sum;
-    }
-  }
+  row_fold(red, partial, n, chunks, p.C8, a1, a2, a3);
 }
 
 __global__ __launch_bounds__(256) void norm_ex_bwd_apply_kernel(const NormExK p, const unsigned short* g1,
@@ -215,13 +187,13 @@ __global__ __launch_bounds__(256) void norm_ex_bwd_apply_kernel(const NormExK p,
     const unsigned px = e / (unsigned)p.C8;
     const int c8 = (int)(e - px * (unsigned)p.C8);
     float yh[8], gh[8], o[8];
-    ex_unpack8(yh, y_n[e]);
+    unpack_bf8(yh, y_n[e]);
     if (mr) {
       float mu[8], rs[8], s1[8], s2[8];
-      ex_load8(mu, mr + c8 * 8);
-      ex_load8(rs, mr + d.C + c8 * 8);
-      ex_load8(s1, sm + c8 * 8);
-      ex_load8(s2, sm + d.C + c8 * 8);
+      load8(mu, mr + c8 * 8);
+      load8(rs, mr + d.C + c8 * 8);
+      load8(s1, sm + c8 * 8);
+      load8(s2, sm + d.C + c8 * 8);
 #pragma unroll
       for (int k = 0; k < 8; ++k) yh[k] = (yh[k] - mu[k]) * rs[k];
       ex_ghat(p, n, px, c8, g1, g2, yh, gh);
@@ -230,7 +202,7 @@ __global__ __launch_bounds__(256) void norm_ex_bwd_apply_kernel(const NormExK p,
     } else {
       ex_ghat(p, n, px, c8, g1, g2, yh, o);
     }
-    dy_n[e] = ex_pack8(o);
+    dy_n[e] = pack_bf8(o);
   }
 }
 
@@ -251,11 +223,9 @@ extern "C" int gs_norm_act_forward_ex(const gs_norm_ex_desc* d, const void* y, c
              "gs_norm_act_forward_ex: channel strides/offsets must be multiples of 8");
   NormExK k;
   k.d = *d; k.C8 = d->C / 8; k.HW = (unsigned)(d->H * d->W);
-  long long bx = ((long long)k.HW * k.C8 + 255) / 256;
-  if (bx > 2048) bx = 2048;
-  hipLaunchKernelGGL(norm_ex_fwd_kernel, dim3((unsigned)bx, d->N), dim3(256), 0, static_cast<hipStream_t>(stream), k,
-                     static_cast<const uint4*>(y), mean_rstd, static_cast<unsigned short*>(x1),
-                     static_cast<unsigned short*>(x2));
+  hipLaunchKernelGGL(norm_ex_fwd_kernel, dim3(norm_grid((long long)k.HW * k.C8, 2048), d->N), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), k, static_cast<const uint4*>(y), mean_rstd,
+                     static_cast<unsigned short*>(x1), static_cast<unsigned short*>(x2));
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -282,20 +252,17 @@ extern "C" int gs_norm_act_backward_ex(const gs_norm_ex_desc* d, const void* g1,
     GS_REQUIRE(scratch, "gs_norm_act_backward_ex: scratch required with normalisation");
     const int chunks = (int)((k.HW + kExPixPerBlock - 1) / kExPixPerBlock);
     sums = scratch + (size_t)d->N * chunks * 3 * d->C;
-#define GS_LAUNCH_REDUCE(COLS)                                                                                       \
-  hipLaunchKernelGGL((norm_ex_bwd_reduce_kernel<COLS>), dim3(chunks, d->N, (k.C8 + COLS - 1) / COLS), dim3(256), 0, \
-                     st, k, a, b, static_cast<const uint4*>(y), mean_rstd, scratch, kExPixPerBlock, chunks)
-    if (k.C8 >= 32) GS_LAUNCH_REDUCE(32);
-    else if (k.C8 >= 8) GS_LAUNCH_REDUCE(8);
-    else GS_LAUNCH_REDUCE(1);
-#undef GS_LAUNCH_REDUCE
+    // (no COLS 4 / 2 here, unlike norm.hip and prelu.hip: layers under 64 channels take one column per workgroup)
+    norm_by_cols<32, 8, 1>(k.C8, [&](auto cols) {
+      constexpr int COLS = decltype(cols)::value;
+      hipLaunchKernelGGL((norm_ex_bwd_reduce_kernel<COLS>), dim3(chunks, d->N, (k.C8 + COLS - 1) / COLS), dim3(256), 0, st, k, a,
+                         b, static_cast<const uint4*>(y), mean_rstd, scratch, kExPixPerBlock, chunks);
+    });
     GS_CHECK_HIP(hipGetLastError());
     if (int rc = gs_launch_slot_sum3(scratch, sums, d->N, chunks, d->C, 1.0f / (float)k.HW, mean_rstd, bias_grad, st))
       return rc;
   }
-  long long bx = ((long long)k.HW * k.C8 + 255) / 256;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(norm_ex_bwd_apply_kernel, dim3((unsigned)bx, d->N), dim3(256), 0, st, k, a, b,
+  hipLaunchKernelGGL(norm_ex_bwd_apply_kernel, dim3(norm_grid((long long)k.HW * k.C8, 1024), d->N), dim3(256), 0, st, k, a, b,
                      static_cast<const uint4*>(y), mean_rstd, sums, static_cast<uint4*>(dy));
   GS_CHECK_HIP(hipGetLastError());
   return 0;

@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void repack_groups_kernel(const float* __restr
       float f[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) { const int id = index[i * 8 + k]; f[k] = id >= 0 ? master[id] : 0.f; }
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
+      o = pack_bf8(f);
     } else if (b >= 0) {
       float f[8];
       if ((b & 3) == 0) {
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void repack_groups_kernel(const float* __restr
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] = master[b + k];
       }
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
+      o = pack_bf8(f);
     }
     pack[i] = o;
   }

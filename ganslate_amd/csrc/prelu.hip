@@ -9,7 +9,7 @@
 // coupling y1 = x1 + PReLU(IN(conv(x2))) (norm, mode 2), block tails PReLU(core(x) + x) (no norm, mode 1).
 // HBM-bound streaming kernels: 16 B per lane, fp32 math, deterministic two-level reductions (atomics only for the
 // final per-image accumulation into the parameter-gradient buffer, as in wgrad).
-#include "internal.hpp"
+#include "norm_common.hpp"
 
 struct PNormK {
   gs_pnorm_desc d;
@@ -18,23 +18,6 @@ struct PNormK {
   int c8_shift;               // log2(C8) when C8 is a power of two (the element loops' grid strides are multiples of 256), else -1
 };
 
-__device__ __forceinline__ void pn_load8(float* f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-__device__ __forceinline__ void pn_unpack8(float* f, const uint4 v) {
-  f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
-  f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
-}
-__device__ __forceinline__ uint4 pn_pack8(const float* f) {
-  uint4 o;
-  o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-  return o;
-}
-__device__ __forceinline__ void pn_view8(float* f, const unsigned short* t, size_t pix, int cs, int co, int c8) {
-  pn_unpack8(f, *reinterpret_cast<const uint4*>(t + pix * cs + co + c8 * 8));
-}
 // residual of 8 consecutive channels starting at c8*8 of pixel `pix`
 __device__ __forceinline__ void pn_res8(float* f, const gs_pnorm_desc& d, const unsigned short* res, size_t pix,
                                         int c8) {
@@ -43,7 +26,7 @@ __device__ __forceinline__ void pn_res8(float* f, const gs_pnorm_desc& d, const 
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[k] = bf2f(r[(c8 * 8 + k) % d.res_mod]);
   } else {
-    pn_view8(f, res, pix, d.res_cs, d.res_co, c8);
+    view8(f, res, pix, d.res_cs, d.res_co, c8);
   }
 }
 
@@ -54,38 +37,18 @@ struct PnCh {
   float mu[8], rs[8], sl[8];
 };
 __device__ __forceinline__ void pn_ch_load(PnCh& c, const gs_pnorm_desc& d, const float* mr, const float* slope, int c8) {
-  if (mr) { pn_load8(c.mu, mr + c8 * 8); pn_load8(c.rs, mr + d.C + c8 * 8); }
-  if (slope) pn_load8(c.sl, slope + c8 * 8);
+  if (mr) { load8(c.mu, mr + c8 * 8); load8(c.rs, mr + d.C + c8 * 8); }
+  if (slope) load8(c.sl, slope + c8 * 8);
 }
 
 // pre-activation u of one 8-channel group
 __device__ __forceinline__ void pn_preact_c(float* u, float* yh, const PNormK& p, const unsigned short* y, bool has_mr,
                                             const PnCh& c, const unsigned short* res, size_t pix, int c8) {
   const gs_pnorm_desc& d = p.d;
-  pn_view8(yh, y, pix, d.y_cs, d.y_co, c8);
+  view8(yh, y, pix, d.y_cs, d.y_co, c8);
   if (has_mr) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) yh[k] = (yh[k] - c.mu[k]) * c.rs[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) u[k] = yh[k];
-  if (d.res_mode == 1) {
-    float r[8];
-    pn_res8(r, d, res, pix, c8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) u[k] += r[k];
-  }
-}
-__device__ __forceinline__ void pn_preact(float* u, float* yh, const PNormK& p, const unsigned short* y,
-                                          const float* mr, const unsigned short* res, size_t pix, int c8) {
-  const gs_pnorm_desc& d = p.d;
-  pn_view8(yh, y, pix, d.y_cs, d.y_co, c8);
-  if (mr) {
-    float mu[8], rs[8];
-    pn_load8(mu, mr + c8 * 8);
-    pn_load8(rs, mr + d.C + c8 * 8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) yh[k] = (yh[k] - mu[k]) * rs[k];
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) u[k] = yh[k];
@@ -129,7 +92,7 @@ __global__ __launch_bounds__(256) void pnorm_fwd_kernel(const PNormK p, const un
 #pragma unroll
       for (int k = 0; k < 8; ++k) u[k] = r[k] - u[k];
     }
-    *reinterpret_cast<uint4*>(out + pix * d.out_cs + d.out_co + c8 * 8) = pn_pack8(u);
+    *reinterpret_cast<uint4*>(out + pix * d.out_cs + d.out_co + c8 * 8) = pack_bf8(u);
   }
 }
 
@@ -139,9 +102,9 @@ __device__ __forceinline__ void pn_gu_c(float* gu, float* gs, const PNormK& p, c
                                         int c8) {
   const gs_pnorm_desc& d = p.d;
   float a[8], b[8];
-  pn_view8(a, g, pix, d.g_cs, d.g_co, c8);
+  view8(a, g, pix, d.g_cs, d.g_co, c8);
   if (g2) {
-    pn_view8(b, g2, pix, d.g2_cs, d.g2_co, c8);
+    view8(b, g2, pix, d.g2_cs, d.g2_co, c8);
 #pragma unroll
     for (int k = 0; k < 8; ++k) a[k] += b[k];
   }
@@ -153,33 +116,6 @@ __device__ __forceinline__ void pn_gu_c(float* gu, float* gs, const PNormK& p, c
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       gu[k] = u[k] > 0.f ? a[k] : a[k] * c.sl[k];
-      gs[k] = u[k] > 0.f ? 0.f : a[k] * u[k];
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { gu[k] = a[k]; gs[k] = 0.f; }
-  }
-}
-__device__ __forceinline__ void pn_gu(float* gu, float* gs, const PNormK& p, const unsigned short* g,
-                                      const unsigned short* g2, const float* u, const float* slope, size_t pix,
-                                      int c8) {
-  const gs_pnorm_desc& d = p.d;
-  float a[8], b[8], sl[8];
-  pn_view8(a, g, pix, d.g_cs, d.g_co, c8);
-  if (g2) {
-    pn_view8(b, g2, pix, d.g2_cs, d.g2_co, c8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] += b[k];
-  }
-  if (d.res_mode == 3) {                 // out = res - v: the branch sees the negated gradient
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = -a[k];
-  }
-  if (slope) {
-    pn_load8(sl, slope + c8 * 8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      gu[k] = u[k] > 0.f ? a[k] : a[k] * sl[k];
       gs[k] = u[k] > 0.f ? 0.f : a[k] * u[k];
     }
   } else {
@@ -223,80 +159,11 @@ __global__ __launch_bounds__(256) void pnorm_bwd_reduce_kernel(const PNormK p, c
       }
     }
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[row][col][r * 8 + k] = acc[r][k];
-  __syncthreads();
-  for (int o = tid; o < COLS * 32; o += 256) {
-    const int cc = o / 32, k = o - cc * 32;
-    const int ch8 = blockIdx.z * COLS + cc;
-    if (ch8 < p.C8) {
-      float sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) sum += red[r][cc][k];
-      float* out = partial + ((size_t)n * chunks + blockIdx.x) * 4 * d.C;
-      out[(k >> 3) * d.C + ch8 * 8 + (k & 7)] = sum;
-    }
-  }
+  row_fold(red, partial, n, chunks, p.C8, acc[0], acc[1], acc[2], acc[3]);
 }
 
-// pass 2: per (n, c) totals over the chunks -> sums [N][4][C]; parameter gradients:
-//   dslope[c] += S4;  bias_grad[c] += -rstd*S2*S3/hw (sum over pixels of dy, the bias of the conv in front of the norm)
-template <int CH>
-__global__ __launch_bounds__(256) void pnorm_bwd_finalize_kernel(const float* partial, float* sums, int chunks, int C,
-                                                                 float inv_hw, const float* mean_rstd, float* dslope,
-                                                                 float* db) {
-  constexpr int LANES = 256 / CH;
-  __shared__ double red[4][LANES][CH + 1];
-  __shared__ float tot[4][CH];
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const int col = tid % CH, lane = tid / CH;
-  const int c = blockIdx.x * CH + col;
-  const float* src = partial + (size_t)n * chunks * 4 * C;
-  // all four sums of a channel in ONE sweep (the four rows of a chunk are neighbours: 4 x 4 loads in flight per thread; additions
-  // per sum in chunk order, exactly the order of the four serial sweeps this replaced — they cost 16 dependent memory round
-  // trips and three workgroup barriers more, 8-12 us per launch, 148 launches per V-Net step)
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (c < C) {
-    int sl = lane;
-    for (; sl + 3 * LANES < chunks; sl += 4 * LANES) {
-      float v[4][4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[k][r] = src[((size_t)(sl + k * LANES) * 4 + r) * C + c];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[r] += (double)v[k][r];
-    }
-    for (; sl < chunks; sl += LANES)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s[r] += (double)src[((size_t)sl * 4 + r) * C + c];
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) red[r][lane][col] = s[r];
-  __syncthreads();
-  if (lane < 4) {                                  // sum r = lane over the lanes, in lane order
-    double t = 0.0;
-#pragma unroll
-    for (int l = 0; l < LANES; ++l) t += red[lane][l][col];
-    tot[lane][col] = (float)t;
-  }
-  __syncthreads();
-  if (lane == 0 && c < C) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sums[((size_t)n * 4 + r) * C + c] = tot[r][col];
-    if (gridDim.y == 1) {
-      // one image: its totals ARE the parameter gradients — norm_param_grads_kernel's arithmetic (norm.hip) with its sum over
-      // one image, here instead of a launch of one workgroup behind this one (184 such launches per V-Net step at batch 1)
-      if (db && mean_rstd)
-        db[c] = __fadd_rn(db[c], __fmul_rn(__fmul_rn(__fmul_rn(-mean_rstd[C + c], tot[1][col]), tot[2][col]), inv_hw));
-      if (dslope) dslope[c] = __fadd_rn(dslope[c], tot[3][col]);
-    }
-  }
-}
+// (pass 2, per (n, c) totals over the chunks -> sums [N][4][C] and the parameter gradients dslope[c] += S4, bias_grad[c] +=
+// -rstd*S2*S3/hw, is slot_sum_kernel<4> of norm.hip)
 
 // pass 3: dy (and optionally gres = gu)
 __global__ __launch_bounds__(256) void pnorm_bwd_apply_kernel(const PNormK p, const unsigned short* g,
@@ -315,7 +182,7 @@ __global__ __launch_bounds__(256) void pnorm_bwd_apply_kernel(const PNormK p, co
   float s1[8], s2[8];
   auto load_ch = [&](int c8) {
     pn_ch_load(ch, d, mr, slope, c8);
-    if (mr) { pn_load8(s1, sm + c8 * 8); pn_load8(s2, sm + d.C + c8 * 8); }
+    if (mr) { load8(s1, sm + c8 * 8); load8(s2, sm + d.C + c8 * 8); }
   };
   if (fixed) load_ch((int)((blockIdx.x * 256u + threadIdx.x) & (unsigned)(p.C8 - 1)));
   for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < per_img; e += gridDim.x * 256u) {
@@ -326,7 +193,7 @@ __global__ __launch_bounds__(256) void pnorm_bwd_apply_kernel(const PNormK p, co
     if (!fixed) load_ch(c8);
     pn_preact_c(u, yh, p, y, mr != nullptr, ch, res, pix, c8);
     pn_gu_c(gu, gs, p, g, g2, u, slope != nullptr, ch, pix, c8);
-    if (gres) *reinterpret_cast<uint4*>(gres + pix * d.gres_cs + d.gres_co + c8 * 8) = pn_pack8(gu);
+    if (gres) *reinterpret_cast<uint4*>(gres + pix * d.gres_cs + d.gres_co + c8 * 8) = pack_bf8(gu);
     if (mr) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) o[k] = ch.rs[k] * (gu[k] - s1[k] * inv_hw - yh[k] * s2[k] * inv_hw);
@@ -334,15 +201,8 @@ __global__ __launch_bounds__(256) void pnorm_bwd_apply_kernel(const PNormK p, co
 #pragma unroll
       for (int k = 0; k < 8; ++k) o[k] = gu[k];
     }
-    *reinterpret_cast<uint4*>(dy + pix * d.dy_cs + d.dy_co + c8 * 8) = pn_pack8(o);
+    *reinterpret_cast<uint4*>(dy + pix * d.dy_cs + d.dy_co + c8 * 8) = pack_bf8(o);
   }
-}
-
-static int pn_c8_shift(int C8) {
-  if (C8 <= 0 || C8 > 256 || (C8 & (C8 - 1))) return -1;
-  int sh = 0;
-  while ((1 << sh) < C8) ++sh;
-  return sh;
 }
 
 static int pn_pix_per_block(long long pixels) {
@@ -368,12 +228,10 @@ extern "C" int gs_pnorm_forward(const gs_pnorm_desc* d, const void* y, const flo
   GS_REQUIRE((d->out_cs & 7) == 0 && (d->out_co & 7) == 0, "gs_pnorm_forward: output view must be 8-channel aligned");
   PNormK k;
   k.d = *d; k.C8 = d->C / 8; k.HW = (unsigned)d->pixels;
-  k.c8_shift = pn_c8_shift(k.C8);
-  long long bx = ((long long)k.HW * k.C8 + 255) / 256;
-  if (bx > 2048) bx = 2048;
-  hipLaunchKernelGGL(pnorm_fwd_kernel, dim3((unsigned)bx, d->N), dim3(256), 0, static_cast<hipStream_t>(stream), k,
-                     static_cast<const unsigned short*>(y), mean_rstd, static_cast<const unsigned short*>(res), slope,
-                     static_cast<unsigned short*>(out));
+  k.c8_shift = norm_c8_shift(k.C8);
+  hipLaunchKernelGGL(pnorm_fwd_kernel, dim3(norm_grid((long long)k.HW * k.C8, 2048), d->N), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), k, static_cast<const unsigned short*>(y), mean_rstd,
+                     static_cast<const unsigned short*>(res), slope, static_cast<unsigned short*>(out));
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -395,7 +253,7 @@ extern "C" int gs_pnorm_backward(const gs_pnorm_desc* d, const void* g, const vo
   hipStream_t st = static_cast<hipStream_t>(stream);
   PNormK k;
   k.d = *d; k.C8 = d->C / 8; k.HW = (unsigned)d->pixels;
-  k.c8_shift = pn_c8_shift(k.C8);
+  k.c8_shift = norm_c8_shift(k.C8);
   const unsigned short* gp = static_cast<const unsigned short*>(g);
   const unsigned short* g2p = static_cast<const unsigned short*>(g2);
   const unsigned short* yp = static_cast<const unsigned short*>(y);
@@ -406,34 +264,21 @@ extern "C" int gs_pnorm_backward(const gs_pnorm_desc* d, const void* g, const vo
     const int ppb = pn_pix_per_block(d->pixels);
     const int chunks = (int)((d->pixels + ppb - 1) / ppb);
     sums = scratch + (size_t)d->N * chunks * 4 * d->C;
-#define GS_LAUNCH_REDUCE(COLS)                                                                                      \
-  hipLaunchKernelGGL((pnorm_bwd_reduce_kernel<COLS>), dim3(chunks, d->N, (k.C8 + COLS - 1) / COLS), dim3(256), 0, \
-                     st, k, gp, g2p, yp, mean_rstd, rp, slope, scratch, ppb, chunks)
     // (COLS columns of one pixel are neighbouring 16-B loads: with one column per workgroup a 16- or 32-channel slice was
     // read as every second / fourth 16 bytes of a line by two / four different workgroups)
-    if (k.C8 >= 32) GS_LAUNCH_REDUCE(32);
-    else if (k.C8 >= 8) GS_LAUNCH_REDUCE(8);
-    else if (k.C8 >= 4) GS_LAUNCH_REDUCE(4);
-    else if (k.C8 >= 2) GS_LAUNCH_REDUCE(2);
-    else GS_LAUNCH_REDUCE(1);
-#undef GS_LAUNCH_REDUCE
+    norm_by_cols<32, 8, 4, 2, 1>(k.C8, [&](auto cols) {
+      constexpr int COLS = decltype(cols)::value;
+      hipLaunchKernelGGL((pnorm_bwd_reduce_kernel<COLS>), dim3(chunks, d->N, (k.C8 + COLS - 1) / COLS), dim3(256), 0, st, k, gp,
+                         g2p, yp, mean_rstd, rp, slope, scratch, ppb, chunks);
+    });
     GS_CHECK_HIP(hipGetLastError());
-    if (d->C < 128 && chunks > 256)
-      hipLaunchKernelGGL((pnorm_bwd_finalize_kernel<4>), dim3((d->C + 3) / 4, d->N), dim3(256), 0, st, scratch, sums,
-                         chunks, d->C, 1.0f / (float)d->pixels, mean_rstd, slope ? dslope : nullptr, bias_grad);
-    else
-      hipLaunchKernelGGL((pnorm_bwd_finalize_kernel<16>), dim3((d->C + 15) / 16, d->N), dim3(256), 0, st, scratch, sums,
-                         chunks, d->C, 1.0f / (float)d->pixels, mean_rstd, slope ? dslope : nullptr, bias_grad);
-    GS_CHECK_HIP(hipGetLastError());
-    // slope and bias gradients: per-image totals added in image order (norm.hip), not by atomics
-    if (d->N > 1)     // (one image: done by the finalize pass)
-      if (int rc = gs_launch_norm_param_grads(sums, 4, mean_rstd, bias_grad, slope ? dslope : nullptr, d->N, d->C,
-                                              1.0f / (float)d->pixels, st)) return rc;
+    // totals, and the slope and bias gradients: per-image totals added in image order (norm.hip), not by atomics. Narrow layers
+    // with many chunks take 4 channels per workgroup.
+    if (int rc = gs_launch_slot_sum(4, d->C < 128 && chunks > 256, scratch, sums, d->N, chunks, d->C, 1.0f / (float)d->pixels,
+                                    mean_rstd, bias_grad, slope ? dslope : nullptr, st)) return rc;
   }
-  long long bx = ((long long)k.HW * k.C8 + 255) / 256;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(pnorm_bwd_apply_kernel, dim3((unsigned)bx, d->N), dim3(256), 0, st, k, gp, g2p, yp, mean_rstd, rp,
-                     slope, mean_rstd ? sums : nullptr, static_cast<unsigned short*>(dy),
+  hipLaunchKernelGGL(pnorm_bwd_apply_kernel, dim3(norm_grid((long long)k.HW * k.C8, 1024), d->N), dim3(256), 0, st, k, gp, g2p,
+                     yp, mean_rstd, rp, slope, mean_rstd ? sums : nullptr, static_cast<unsigned short*>(dy),
                      static_cast<unsigned short*>(gres));
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -447,14 +292,14 @@ __global__ __launch_bounds__(256) void add_views_kernel(unsigned short* dst, int
     const long long pix = e / C8;
     const int c8 = (int)(e - pix * C8);
     float a[8], b[8];
-    pn_unpack8(b, *reinterpret_cast<const uint4*>(src + pix * scs + sco + c8 * 8));
+    unpack_bf8(b, *reinterpret_cast<const uint4*>(src + pix * scs + sco + c8 * 8));
     uint4* o = reinterpret_cast<uint4*>(dst + pix * dcs + dco + c8 * 8);
     if (accumulate) {
-      pn_unpack8(a, *o);
+      unpack_bf8(a, *o);
 #pragma unroll
       for (int k = 0; k < 8; ++k) b[k] += a[k];
     }
-    *o = pn_pack8(b);
+    *o = pack_bf8(b);
   }
 }
 
@@ -462,9 +307,7 @@ extern "C" int gs_add_views(void* dst, int32_t dst_cs, int32_t dst_co, const voi
                             int64_t pixels, int32_t C, int32_t accumulate, void* stream) {
   GS_REQUIRE(dst && src && pixels > 0 && C > 0 && ((C | dst_cs | dst_co | src_cs | src_co) & 7) == 0,
              "gs_add_views: bad argument (channel counts / strides / offsets must be multiples of 8)");
-  long long bx = (pixels * (C / 8) + 255) / 256;
-  if (bx > 4096) bx = 4096;
-  hipLaunchKernelGGL(add_views_kernel, dim3((unsigned)bx), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(add_views_kernel, dim3(norm_grid(pixels * (C / 8), 4096)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<unsigned short*>(dst), dst_cs, dst_co, static_cast<const unsigned short*>(src), src_cs,
                      src_co, (long long)pixels, C / 8, accumulate);
   GS_CHECK_HIP(hipGetLastError());
@@ -488,9 +331,7 @@ __global__ __launch_bounds__(256) void repeat_bwd_kernel(const unsigned short* g
 extern "C" int gs_repeat_backward(const void* g, int32_t g_cs, int32_t g_co, float* g_img, int32_t N, int32_t Cin,
                                   int32_t C, int64_t pixels, void* stream) {
   GS_REQUIRE(g && g_img && N > 0 && Cin > 0 && C >= Cin && C % Cin == 0 && pixels > 0, "gs_repeat_backward: bad argument");
-  long long bx = (pixels + 255) / 256;
-  if (bx > 2048) bx = 2048;
-  hipLaunchKernelGGL(repeat_bwd_kernel, dim3((unsigned)bx, N), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(repeat_bwd_kernel, dim3(norm_grid(pixels, 2048), N), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(g), g_cs, g_co, g_img, Cin, C, (long long)pixels);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -516,24 +357,12 @@ __global__ __launch_bounds__(256) void slice_stats_kernel(const unsigned short* 
   if (c8 < C8) {
     for (unsigned px = p0 + row; px < p1; px += ROWS) {
       float v[8];
-      pn_view8(v, x, (size_t)n * pixels + px, cs, co, c8);
+      view8(v, x, (size_t)n * pixels + px, cs, co, c8);
 #pragma unroll
       for (int k = 0; k < 8; ++k) { a[k] += v[k]; q[k] += v[k] * v[k]; }
     }
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { red[row][col][k] = a[k]; red[row][col][8 + k] = q[k]; }
-  __syncthreads();
-  for (int o = tid; o < COLS * 16; o += 256) {
-    const int cc = o / 16, k = o - cc * 16;
-    const int ch8 = blockIdx.z * COLS + cc;
-    if (ch8 < C8) {
-      float sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) sum += red[r][cc][k];
-      partial[(((size_t)n * slots + blockIdx.x) * 2 + (k >> 3)) * C + ch8 * 8 + (k & 7)] = sum;
-    }
-  }
+  row_fold(red, partial, n, slots, C8, a, q);
 }
 
 extern "C" int32_t gs_slice_stats_slots(int64_t pixels) {
@@ -551,18 +380,11 @@ extern "C" int gs_slice_stats(const void* x, int32_t N, int64_t pixels, int32_t 
   const int C8 = C / 8;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned short* xs = static_cast<const unsigned short*>(x);
-  if (C8 >= 8)
-    hipLaunchKernelGGL((slice_stats_kernel<8>), dim3(slots, N, (C8 + 7) / 8), dim3(256), 0, st, xs, (unsigned)pixels, cs, co,
-                       C8, C, partial, ppb, slots);
-  else if (C8 >= 4)
-    hipLaunchKernelGGL((slice_stats_kernel<4>), dim3(slots, N, (C8 + 3) / 4), dim3(256), 0, st, xs, (unsigned)pixels, cs, co,
-                       C8, C, partial, ppb, slots);
-  else if (C8 >= 2)
-    hipLaunchKernelGGL((slice_stats_kernel<2>), dim3(slots, N, (C8 + 1) / 2), dim3(256), 0, st, xs, (unsigned)pixels, cs, co,
-                       C8, C, partial, ppb, slots);
-  else
-    hipLaunchKernelGGL((slice_stats_kernel<1>), dim3(slots, N, C8), dim3(256), 0, st, xs, (unsigned)pixels, cs, co, C8, C,
-                       partial, ppb, slots);
+  norm_by_cols<8, 4, 2, 1>(C8, [&](auto cols) {       // (this kernel's own list: no COLS 32)
+    constexpr int COLS = decltype(cols)::value;
+    hipLaunchKernelGGL((slice_stats_kernel<COLS>), dim3(slots, N, (C8 + COLS - 1) / COLS), dim3(256), 0, st, xs, (unsigned)pixels,
+                       cs, co, C8, C, partial, ppb, slots);
+  });
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -49,9 +49,7 @@ __global__ __launch_bounds__(256) void image_unfold_kernel(const float* img, uns
         }
         f[e] = v;
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + (size_t)px * Qp + q0) = o;
+      *reinterpret_cast<uint4*>(out + (size_t)px * Qp + q0) = pack_bf8(f);
     }
   }
 }
@@ -139,9 +137,7 @@ __global__ __launch_bounds__(256) void shiftadd_bwd_kernel(const float* g_img, c
         }
         f[e] = v;
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + (size_t)px * Pp + q0) = o;
+      *reinterpret_cast<uint4*>(out + (size_t)px * Pp + q0) = pack_bf8(f);
     }
   }
 }
@@ -222,9 +218,7 @@ __global__ __launch_bounds__(256) void shiftadd_bwd_row_kernel(const float* g_im
         }
         f[e] = v;
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + q0) = o;
+      *reinterpret_cast<uint4*>(out + q0) = pack_bf8(f);
     }
   }
 }
@@ -262,9 +256,7 @@ __global__ __launch_bounds__(256) void image_unfold_row_kernel(const float* img,
         }
         f[e] = v;
       }
-      uint4 o;
-      o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
-      *reinterpret_cast<uint4*>(out + q0) = o;
+      *reinterpret_cast<uint4*>(out + q0) = pack_bf8(f);
     }
   }
 }

@@ -687,7 +687,9 @@ def test_parity_class_dgrad_with_fused_norm_sums(hip_ops, monkeypatch, case, wit
     close_bf16(res["hip"][2], res["ref"][3], "dy vs oracle")
 
 
-@pytest.mark.parametrize("shape", [(2, 16, 16, 256), (2, 17, 13, 64), (1, 32, 32, 8), (1, 5, 7, 512)])
+# (16 / 32 channels: 2 / 4 channel-group columns per workgroup in the backward reduce pass)
+@pytest.mark.parametrize("shape", [(2, 16, 16, 256), (2, 17, 13, 64), (1, 32, 32, 8), (1, 5, 7, 512), (1, 5, 7, 16),
+                                   (2, 17, 13, 32)])
 @pytest.mark.parametrize("act", ["relu", "lrelu", "none"])
 @pytest.mark.parametrize("res", [False, True])
 def test_inorm_forward_backward(hip_ops, shape, act, res):
