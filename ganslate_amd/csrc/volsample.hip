@@ -24,6 +24,11 @@
 //   v = mask ? (float)x : outside;  v = v / divisor;  v = min(max(v, lo), hi);  v = (v - lo) / (hi - lo);  v = 2 * v - 1
 // one IEEE fp32 operation per step (no contraction), the focal point read from device memory, the start clamped into the
 // volume so that no point can make the kernel read outside it.
+//
+// gs_volume_prepare — a whole case for the val / test engines (data/multimodal_valtest.py): the same mask step and the same
+// per-voxel chain (one device function, clip_minmax), with centred padding up to a target shape in between; the pad value is
+// the minimum of the masked volume over the case, NaN-propagating like np.min, each mask padded with its own minimum. Two
+// launches: 256 partial minima per volume / mask, then the apply pass, whose workgroups fold the partials in one fixed tree.
 #include <limits>
 #include "common.hpp"
 
@@ -268,6 +273,20 @@ struct ClipK {
   long long n;
 };
 
+// the per-voxel chain behind the mask of gs_patch_clip_minmax and gs_volume_prepare: one rounding per step
+__device__ __forceinline__ float clip_minmax(float v, float divisor, float lo, float hi, float span) {
+  v = __fdiv_rn(v, divisor);
+  v = v < lo ? lo : v;                     // NaN stays NaN, like torch.clamp
+  v = v > hi ? hi : v;
+  v = __fdiv_rn(__fsub_rn(v, lo), span);
+  return __fsub_rn(__fmul_rn(2.f, v), 1.f);
+}
+
+__device__ __forceinline__ float voxel_or(const void* vol, int dtype, long long off, bool in, float outside) {
+  if (!in) return outside;
+  return dtype == GS_VOL_F32 ? static_cast<const float*>(vol)[off] : (float)static_cast<const short*>(vol)[off];
+}
+
 __global__ __launch_bounds__(256) void patch_clip_minmax_kernel(const ClipK k, float* out) {
   const int c = blockIdx.y;
   const int size[3] = {k.D, k.H, k.W}, patch[3] = {k.pd, k.ph, k.pw};
@@ -289,14 +308,92 @@ __global__ __launch_bounds__(256) void patch_clip_minmax_kernel(const ClipK k, f
     const long long row = i / k.pw;
     const int y = (int)(row % k.ph), z = (int)(row / k.ph);
     const long long off = ((long long)(s[0] + z) * k.H + (s[1] + y)) * k.W + (s[2] + x);
-    float v = outside;
-    if (k.mask[off])
-      v = dtype == GS_VOL_F32 ? static_cast<const float*>(vol)[off] : (float)static_cast<const short*>(vol)[off];
-    v = __fdiv_rn(v, divisor);
-    v = v < lo ? lo : v;                   // NaN stays NaN, like torch.clamp
-    v = v > hi ? hi : v;
-    v = __fdiv_rn(__fsub_rn(v, lo), span);
-    dst[i] = __fsub_rn(__fmul_rn(2.f, v), 1.f);
+    const float v = voxel_or(vol, dtype, off, k.mask[off] != 0, outside);
+    dst[i] = clip_minmax(v, divisor, lo, hi, span);
+  }
+}
+
+// ---- gs_volume_prepare ---------------------------------------------------------------------------------------------
+constexpr int VP_MAX_MASKS = 1 + GS_VM_MAX_LABELS;
+constexpr int VP_PARTS = 256;              // workgroups of the minimum pass per volume / mask
+
+struct PrepK {
+  const void* vol[PC_MAX];
+  int dtype[PC_MAX];
+  float outside[PC_MAX], divisor[PC_MAX], lo[PC_MAX], hi[PC_MAX];
+  const uint8_t* mask[VP_MAX_MASKS];
+  uint8_t* mask_out[VP_MAX_MASKS];
+  int C, M;
+  int D, H, W, Do, Ho, Wo, pz, py, px;     // input size, output size, pad in front
+  long long n, no;
+  int padded;
+};
+
+// np.min's rule: a NaN anywhere makes the minimum NaN
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : (b < a ? b : a); }
+
+// partial[item * VP_PARTS + block]: item < C the minimum of where(body, v, outside) over the block's voxels, item >= C the
+// minimum byte of mask item - C; a block without voxels contributes +inf
+__global__ __launch_bounds__(256) void prepare_min_kernel(const PrepK k, float* partial) {
+  __shared__ float s[256];
+  const int item = blockIdx.y;
+  float m = std::numeric_limits<float>::infinity();
+  if (item < k.C) {
+    const void* vol = k.vol[item];
+    const int dtype = k.dtype[item];
+    const float outside = k.outside[item];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < k.n; i += (long long)VP_PARTS * 256)
+      m = min_nan(m, voxel_or(vol, dtype, i, k.mask[0][i] != 0, outside));
+  } else {
+    const uint8_t* mask = k.mask[item - k.C];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < k.n; i += (long long)VP_PARTS * 256)
+      m = min_nan(m, (float)mask[i]);
+  }
+  s[threadIdx.x] = m;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] = min_nan(s[threadIdx.x], s[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[item * VP_PARTS + blockIdx.x] = s[0];
+}
+
+__global__ __launch_bounds__(256) void prepare_apply_kernel(const PrepK k, const float* partial, float* out) {
+  __shared__ float s[256];
+  const int item = blockIdx.y;
+  float fill = 0.f;
+  if (k.padded) {                          // every workgroup folds the VP_PARTS partials of its item in the same order
+    s[threadIdx.x] = partial[item * VP_PARTS + threadIdx.x];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) s[threadIdx.x] = min_nan(s[threadIdx.x], s[threadIdx.x + o]);
+      __syncthreads();
+    }
+    fill = s[0];
+  }
+  const bool image = item < k.C;
+  const int c = image ? item : 0, mi = image ? 0 : item - k.C;
+  const void* vol = k.vol[c];
+  const int dtype = k.dtype[c];
+  const float outside = k.outside[c], divisor = k.divisor[c], lo = k.lo[c], hi = k.hi[c];
+  const float span = __fsub_rn(hi, lo);
+  const uint8_t* body = k.mask[0];
+  const uint8_t* msrc = k.mask[mi];
+  float* dst = out + (long long)c * k.no;
+  uint8_t* mdst = k.mask_out[mi];
+  const uint8_t mfill = (uint8_t)fill;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < k.no; i += (long long)gridDim.x * 256) {
+    const int x = (int)(i % k.Wo) - k.px;
+    const long long row = i / k.Wo;
+    const int y = (int)(row % k.Ho) - k.py, z = (int)(row / k.Ho) - k.pz;
+    const bool in = (unsigned)x < (unsigned)k.W && (unsigned)y < (unsigned)k.H && (unsigned)z < (unsigned)k.D;
+    const long long off = ((long long)z * k.H + y) * k.W + x;
+    if (image) {
+      const float v = in ? voxel_or(vol, dtype, off, body[off] != 0, outside) : fill;
+      dst[i] = clip_minmax(v, divisor, lo, hi, span);
+    } else {
+      mdst[i] = in ? msrc[off] : mfill;
+    }
   }
 }
 }  // namespace
@@ -380,6 +477,56 @@ extern "C" int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtyp
   const long long blocks = (k.n + 256 * 4 - 1) / (256 * 4);
   hipLaunchKernelGGL(patch_clip_minmax_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks), (unsigned)C), dim3(256), 0,
                      static_cast<hipStream_t>(stream), k, out);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int64_t gs_volume_prepare_ws_bytes(void) { return (int64_t)(PC_MAX + VP_MAX_MASKS) * VP_PARTS * 4; }
+
+extern "C" int gs_volume_prepare(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* const* masks,
+                                 int32_t M, int32_t D, int32_t H, int32_t W, const int32_t* target, const float* outside,
+                                 const float* divisor, const float* lo, const float* hi, float* out,
+                                 uint8_t* const* masks_out, void* ws, void* stream) {
+  GS_REQUIRE(vols && dtypes && masks && target && outside && divisor && lo && hi && out && masks_out && ws,
+             "gs_volume_prepare: null argument");
+  GS_REQUIRE(C >= 1 && C <= PC_MAX, "gs_volume_prepare: between 1 and %d volumes per call; got %d", PC_MAX, C);
+  GS_REQUIRE(M >= 1 && M <= VP_MAX_MASKS, "gs_volume_prepare: between 1 and %d masks per call (the body mask first); got %d",
+             VP_MAX_MASKS, M);
+  GS_REQUIRE(D > 0 && H > 0 && W > 0 && target[0] > 0 && target[1] > 0 && target[2] > 0,
+             "gs_volume_prepare: volume %d x %d x %d, target %d x %d x %d", D, H, W, target[0], target[1], target[2]);
+  GS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3) == 0, "gs_volume_prepare: the workspace must be 4-byte aligned");
+  PrepK k;
+  for (int c = 0; c < PC_MAX; ++c) {
+    const int s = c < C ? c : 0;
+    GS_REQUIRE(vols[s], "gs_volume_prepare: null volume %d", s);
+    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16,
+               "gs_volume_prepare: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", dtypes[s], s);
+    GS_REQUIRE(hi[s] > lo[s], "gs_volume_prepare: clip range [%g, %g] of volume %d is empty", lo[s], hi[s], s);
+    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "gs_volume_prepare: divisor %g of volume %d", divisor[s], s);
+    k.vol[c] = vols[s];
+    k.dtype[c] = dtypes[s];
+    k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
+  }
+  for (int m = 0; m < VP_MAX_MASKS; ++m) {
+    const int s = m < M ? m : 0;
+    GS_REQUIRE(masks[s] && masks_out[s], "gs_volume_prepare: null mask %d", s);
+    k.mask[m] = masks[s];
+    k.mask_out[m] = masks_out[s];
+  }
+  k.C = C; k.M = M;
+  k.D = D; k.H = H; k.W = W;
+  k.Do = target[0] > D ? target[0] : D; k.Ho = target[1] > H ? target[1] : H; k.Wo = target[2] > W ? target[2] : W;
+  k.pz = (k.Do - D) / 2; k.py = (k.Ho - H) / 2; k.px = (k.Wo - W) / 2;
+  k.n = (long long)D * H * W;
+  k.no = (long long)k.Do * k.Ho * k.Wo;
+  k.padded = k.no != k.n;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* partial = static_cast<float*>(ws);
+  if (k.padded)
+    hipLaunchKernelGGL(prepare_min_kernel, dim3(VP_PARTS, (unsigned)(C + M)), dim3(256), 0, st, k, partial);
+  const long long blocks = (k.no + 256 * 4 - 1) / (256 * 4);
+  hipLaunchKernelGGL(prepare_apply_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks), (unsigned)(C + M)), dim3(256), 0,
+                     st, k, partial, out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -141,3 +141,103 @@ class DeviceMultiModalPipeline:
         self.points = points
         out.update(dst)
         return out
+
+
+class DeviceWholeVolumePipeline:
+    """callable(raw batch) -> {"A": fp32 [N, C_A, Do, Ho, Wo] on the device, "B": fp32 [N, before + C_B + after, ...],
+    "masks": {label: uint8 [N, 1, Do, Ho, Wo] on the device}, "metadata": as it came} for MultiModalVolumeValTestDataset
+    (data/multimodal_valtest.py): raw volumes and masks resident in HBM under the same `max_resident_bytes` rule as the
+    training pipelines, per batch only case indices arrive. A case whose body mask is generated gets it from gs_body_mask
+    (csrc/bodymask.hip) once — the mask stays resident, and that one call reads the component's voxel count back, so a CT
+    without a body raises for the case by name. Per case and use one gs_volume_prepare call (csrc/volsample.hip) masks,
+    pads and normalises all modalities of both domains and pads every mask; one strided copy then splits its channels into
+    A's and B's batch tensors. Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
+    val_test_dataset.py:86-187 with ganslate/data/utils/body_mask.py."""
+
+    def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
+        self.dataset = dataset
+        self.device = torch.device(device)
+        self._ops = ops
+        self.resident = {}
+        self.resident_bytes, self.max_resident_bytes = 0, max_resident_bytes
+
+    @property
+    def ops(self):
+        if self._ops is None:
+            from ..nn.native.backend import get_ops
+            self._ops = get_ops()
+        return self._ops
+
+    def _keep(self, key, v):
+        nbytes = v.numel() * v.element_size()
+        if self.resident_bytes + nbytes <= self.max_resident_bytes:          # beyond the budget: upload / generate per use
+            self.resident[key] = v
+            self.resident_bytes += nbytes
+        return v
+
+    def volume(self, name, index, mask=False):
+        key = (name, index)
+        v = self.resident.get(key)
+        if v is None:
+            host = torch.from_numpy(np.array(self.dataset.load(name, index)))       # a copy out of the memory map
+            if mask:
+                host = (host != 0).to(torch.uint8)
+            elif host.dtype not in (torch.float32, torch.int16):
+                host = host.float()
+            v = self._keep(key, host.to(self.device))
+        return v
+
+    def body(self, index):
+        ds = self.dataset
+        if not ds.generates(index):
+            return self.volume(ds.body_mask, index, mask=True)
+        key = (None, index)                                  # no file has this name
+        v = self.resident.get(key)
+        if v is None:
+            v, info = self.ops.body_mask(self.volume(ds.body_mask_from, index), ds.body_mask_threshold)
+            if int(info[0].item()) == 0:
+                raise ds.empty_body_error(index)
+            self._keep(key, v)
+        return v
+
+    def __call__(self, batch):
+        from .multimodal_valtest import RawWholeCase
+        items = batch.get("A")
+        if not items or not isinstance(items[0], RawWholeCase):
+            return batch
+        ds = self.dataset
+        domains = ds.domains()
+        names = [n for k in domains for n in ds.modalities[k]]
+        labels = ds.mask_labels()
+        out = {k: v for k, v in batch.items() if k not in ("A", "B")}
+        both, masks = None, None
+        for i, item in enumerate(items):
+            index = item.index
+            body = self.body(index)
+            extra = [body if ds.masks[label] == ds.body_mask else self.volume(ds.masks[label], index, mask=True)
+                     for label in labels]
+            shape = tuple(max(s, t) for s, t in zip(body.shape, ds.pad_to or body.shape))
+            if both is None:
+                both = torch.empty((len(items), len(names), *shape), dtype=torch.float32, device=self.device)
+                masks = torch.empty((1 + len(labels), len(items), 1, *shape), dtype=torch.uint8, device=self.device)
+            elif tuple(both.shape[2:]) != shape:
+                raise ValueError(f"the cases of one batch come out in different shapes ({tuple(both.shape[2:])} and {shape} "
+                                 f"for {ds.cases[index]!r}): set `pad_to` to a common shape or use `batch_size: 1`")
+            self.ops.volume_prepare([self.volume(n, index) for n in names], body, extra, shape,
+                                    [ds.outside_value[n] for n in names], [ds.divisor(n, index) for n in names],
+                                    [ds.clip_range[n][0] for n in names], [ds.clip_range[n][1] for n in names],
+                                    out=both[i], masks_out=[masks[m, i, 0] for m in range(1 + len(labels))])
+        n_A = len(ds.modalities["A"])
+        out["A"] = both[:, :n_A].contiguous() if len(names) > n_A else both
+        if "B" in domains:
+            before, after = ds.dummy_channels_B
+            B = torch.zeros((len(items), before + len(names) - n_A + after, *both.shape[2:]), dtype=torch.float32,
+                            device=self.device) if before or after else None
+            if B is None:
+                B = both[:, n_A:].contiguous()
+            else:
+                B[:, before:before + len(names) - n_A].copy_(both[:, n_A:])
+            out["B"] = B
+        if labels:
+            out["masks"] = {label: masks[1 + m] for m, label in enumerate(labels)}
+        return out

@@ -12,6 +12,7 @@ ACT = {"none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
 VM_FLAGS = {"ssim": 1, "hist": 2}     # GS_VM_SSIM, GS_VM_HIST
 VM_BINS = 100
 VM_MAX_LABELS = 8                       # GS_VM_MAX_LABELS
+PATCH_MAX_MODALITIES = 8                # GS_PATCH_MAX_MODALITIES
 VIS_MAX_SRCS = 16                       # GS_VIS_MAX_SRCS
 CAT_MAX_SRCS = 4                        # GS_CAT_MAX_SRCS
 
@@ -216,6 +217,14 @@ _PROTOS = {
                                        C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_float),
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
                                        C.c_void_p]),
+    "gs_volume_prepare_ws_bytes": (C.c_int64, []),
+    "gs_volume_prepare": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "gs_body_mask_ws_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gs_body_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
     "gs_mse_const": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_adv_loss": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]),

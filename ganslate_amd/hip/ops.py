@@ -1071,6 +1071,78 @@ class HipOps(TwinSplit):
                                               _ptr(point), fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
                 "gs_patch_clip_minmax")
 
+    def volume_prepare(self, volumes, mask, extra_masks, target, outside, divisor, lo, hi, out=None, masks_out=None):
+        """gs_volume_prepare: one whole case for the val / test engines -> (out, [masks]). volumes: C fp32 / int16
+        (D, H, W) device tensors; mask: the body mask (uint8, non-zero = inside); extra_masks: up to VM_MAX_LABELS further
+        uint8 masks; target: (Dt, Ht, Wt) — every axis comes out as max(size, target), padded centred with the minimum of
+        where(mask, v, outside) (each mask with its own minimum); then / divisor, clamp to [lo, hi], min-max to [-1, 1].
+        out: fp32 [C, Do, Ho, Wo]; masks: uint8 [Do, Ho, Wo] each, the body mask first. Enqueued on the current stream;
+        nothing syncs."""
+        n = len(volumes)
+        if not 1 <= n <= L.PATCH_MAX_MODALITIES:
+            raise ValueError(f"volume_prepare: between 1 and {L.PATCH_MAX_MODALITIES} volumes; got {n}")
+        extra_masks = list(extra_masks or [])
+        if len(extra_masks) > L.VM_MAX_LABELS:
+            raise ValueError(f"volume_prepare: at most {L.VM_MAX_LABELS} extra masks; got {len(extra_masks)}")
+        self._case_volume("mask", mask, (torch.uint8,))
+        for i, v in enumerate(volumes):
+            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        for i, m in enumerate(extra_masks):
+            self._case_volume(f"extra mask {i}", m, (torch.uint8,), mask.shape)
+        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
+            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
+        target = [int(v) for v in target]
+        if len(target) != 3 or min(target) < 1:
+            raise ValueError(f"target must be three positive sizes (D, H, W); got {target}")
+        shape = tuple(max(s, t) for s, t in zip(mask.shape, target))
+        masks_in = [mask] + extra_masks
+        if out is None:
+            out = torch.empty((n, *shape), dtype=torch.float32, device=mask.device)
+        if masks_out is None:
+            masks_out = [torch.empty(shape, dtype=torch.uint8, device=mask.device) for _ in masks_in]
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == (n, *shape)):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *shape)}")
+        if len(masks_out) != len(masks_in):
+            raise ValueError(f"masks_out: one tensor per mask ({len(masks_in)})")
+        for i, m in enumerate(masks_out):
+            self._case_volume(f"masks_out {i}", m, (torch.uint8,), shape)
+        nws = getattr(self, "_prepare_ws", None) or int(self.lib.gs_volume_prepare_ws_bytes())
+        self._prepare_ws = nws
+        ws = torch.empty(nws // 4, dtype=torch.float32, device=mask.device)     # per launch: private to it
+        fl = lambda vals: (C.c_float * n)(*[float(v) for v in vals])
+        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in volumes])
+        dts = (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes])
+        mi = (C.c_void_p * len(masks_in))(*[m.data_ptr() for m in masks_in])
+        mo = (C.c_void_p * len(masks_in))(*[m.data_ptr() for m in masks_out])
+        L.check(self.lib.gs_volume_prepare(ptrs, dts, n, mi, len(masks_in), *mask.shape, (C.c_int32 * 3)(*target), fl(outside),
+                                           fl(divisor), fl(lo), fl(hi), _ptr(out), mo, _ptr(ws), _stream()),
+                "gs_volume_prepare")
+        return out, list(masks_out)
+
+    def body_mask(self, volume, threshold, out=None, return_rounds=False):
+        """gs_body_mask: (mask, info) of a dense (D, H, W) fp32 / int16 device volume — mask uint8 0 / 1 by the definition
+        of data/utils/body_mask.py (threshold, largest 6-connected component, per-slice hole filling), info int32[2] on the
+        device: voxels of the chosen component and its first voxel's flat index (0, -1: nothing reached the threshold, the
+        mask is all zero). Exact and reproducible. Synchronises the current stream a few times (the labelling rounds read a
+        device flag back). return_rounds: also the rounds the two labelling phases ran, as a third value."""
+        self._case_volume("volume", volume, tuple(self.VOL_DTYPES))
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("body_mask: the threshold is NaN")
+        if volume.numel() == 0 or volume.numel() >= 1 << 31:
+            raise ValueError(f"body_mask: {tuple(volume.shape)} voxels do not fit 31-bit indices (or there are none)")
+        if out is None:
+            out = torch.empty(tuple(volume.shape), dtype=torch.uint8, device=volume.device)
+        self._case_volume("out", out, (torch.uint8,), volume.shape)
+        info = torch.empty(2, dtype=torch.int32, device=volume.device)
+        ws = torch.empty(int(self.lib.gs_body_mask_ws_bytes(*volume.shape)) // 8, dtype=torch.int64, device=volume.device)
+        L.check(self.lib.gs_body_mask(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, threshold, _ptr(out),
+                                      _ptr(info), _ptr(ws), _stream()), "gs_body_mask")
+        if return_rounds:
+            return out, info, [int(v) for v in ws[:1].view(torch.int32).tolist()]
+        return out, info
+
     ADV_MODES = {"lsgan": 0, "vanilla": 1, "wgangp": 2, "nonsaturating": 3}
 
     def adv_loss(self, x, mode, target_is_real, label, loss=None, grad=None, grad_scale=None):

@@ -537,6 +537,53 @@ int gs_voxel_draw(const uint8_t* mask, const void* weight, int32_t wdtype, int32
 int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask, int32_t D,
                          int32_t H, int32_t W, const int32_t* patch, const int32_t* point, const float* outside,
                          const float* divisor, const float* lo, const float* hi, float* out, void* stream);
+/* gs_volume_prepare: one whole case for the val / test engines (the reference's val_test_dataset.py:136-161): body
+ * masking, centred padding to a target shape and the per-voxel chain of gs_patch_clip_minmax, for all C
+ * (1..GS_PATCH_MAX_MODALITIES) volumes and M (1..1 + GS_VM_MAX_LABELS) byte masks of a D x H x W case. masks[0] is the
+ * body mask (non-zero = inside), masks[1..] are further region masks. target: host {Dt, Ht, Wt}; the output size of an
+ * axis is max(size, target), pad = output - size, pad / 2 voxels in front and pad / 2 + pad % 2 behind (integer
+ * division), as ganslate/data/utils/ops.py pad() does. Per volume c, in fp32, one IEEE operation per step:
+ *   x = masks[0] ? (float)v : outside[c];    pad voxels: x = min of x over the whole case (NaN if any x is NaN, like
+ *   np.min);    x = x / divisor;  x = min(max(x, lo), hi);  x = (x - lo) / (hi - lo);  x = 2 * x - 1
+ * out: dense fp32 [C, Do, Ho, Wo]. masks_out[m]: dense bytes [Do, Ho, Wo] = masks[m] copied, padded with its own
+ * minimum byte. Two launches: per-block partial minima of every volume and mask (256 blocks each, skipped when no axis is
+ * padded), then the apply pass, whose workgroups each fold the 256 partials in index order. No atomics, no host
+ * synchronisation. ws: gs_volume_prepare_ws_bytes() bytes, 4-byte aligned, private to the call. Null pointers, C or M
+ * out of range, non-positive sizes, an empty clip range, a zero or NaN divisor and a dtype other than GS_VOL_F32 /
+ * GS_VOL_I16 are refused before any launch. */
+int64_t gs_volume_prepare_ws_bytes(void);
+int gs_volume_prepare(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* const* masks, int32_t M,
+                      int32_t D, int32_t H, int32_t W, const int32_t* target, const float* outside, const float* divisor,
+                      const float* lo, const float* hi, float* out, uint8_t* const* masks_out, void* ws, void* stream);
+
+/* ---- patient body mask from a CT (csrc/bodymask.hip) ---------------------------------------------- */
+/* The reference's ganslate/data/utils/body_mask.py without its contour smoothing. For a dense D x H x W volume v (dtype
+ * GS_VOL_F32 or GS_VOL_I16) and a threshold t (compared in fp32; int16 values are exact in fp32):
+ *   1. b = v >= t; a NaN voxel is outside.
+ *   2. components of b under 6-connectivity (scipy.ndimage.label's default structure).
+ *   3. the component with the most voxels; ties go to the component whose first voxel in C order comes first.
+ *   4. per depth slice, every pixel that is NOT a non-component pixel 4-connected to the slice's border through
+ *      non-component pixels (scipy.ndimage.binary_fill_holes per slice): holes are filled, a cavity that opens to the
+ *      border in a slice stays open in that slice, a hole that touches the outside only diagonally is filled.
+ *   5. no voxel reaches t: an all-zero mask and a count of 0.
+ * mask_out: D*H*W bytes of 0 / 1. info: DEVICE int32[2] = {voxels of the chosen component, flat index of its first voxel
+ * in C order or -1}. All quantities are integers, so the result is exact and the same on every run.
+ * Labelling runs in ROUNDS of launches, once in 3-D on b and once per slice on the complement of the chosen component,
+ * by one routine: every voxel holds a parent index <= its own inside its component; a hook launch lowers the parent of
+ * each voxel's root to the smallest root among its neighbours (integer atomic min), a flatten launch replaces every
+ * parent by its root (a walk over strictly decreasing indices). Every access to the parent array inside those launches
+ * is an agent-scope atomic, and nothing depends on a store of another workgroup of the same launch being seen; a round
+ * in which no hook fired ends the phase. Rounds are enqueued eight at a time (rounds after a quiet one return at once)
+ * and the host then reads the quiet flag back: gs_body_mask SYNCHRONISES the stream once per eight rounds, a few times
+ * per case, and therefore cannot be captured into a graph. The number of rounds grows with the number of merges a
+ * component needs, not with the length of a path. Component sizes are integer atomic adds on the roots; the argmax is a
+ * two-level reduction over (count, lowest root) in a fixed order.
+ * ws: gs_body_mask_ws_bytes(D, H, W) bytes, 8-byte aligned, private to the call; after the call its first two int32 hold
+ * the rounds the two phases ran (diagnostic). D * H * W must be below 2^31; that, null pointers, non-positive sizes, the
+ * dtype and a NaN threshold are refused before any launch. */
+int64_t gs_body_mask_ws_bytes(int32_t D, int32_t H, int32_t W);
+int gs_body_mask(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, float threshold, uint8_t* mask_out,
+                 int32_t* info, void* ws, void* stream);
 
 /* ---- losses (fp32, on the boundary images / discriminator maps) --------------------------------- */
 /* loss[0] = mean((x-target)^2); if grad != NULL: grad = grad_scale * 2*(x-target)/n
