@@ -15,6 +15,7 @@ VM_MAX_LABELS = 8                       # GS_VM_MAX_LABELS
 PATCH_MAX_MODALITIES = 8                # GS_PATCH_MAX_MODALITIES
 VIS_MAX_SRCS = 16                       # GS_VIS_MAX_SRCS
 CAT_MAX_SRCS = 4                        # GS_CAT_MAX_SRCS
+IMG_DTYPES = {"uint8": 0, "float32": 1}  # GS_IMG_U8, GS_IMG_F32
 
 
 class GConvDesc(C.Structure):
@@ -94,6 +95,13 @@ class U8BatchItem(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("src", "bounds_h", "kk_h", "bounds_v", "kk_v")] + [("tmp_off", C.c_int64)] + [
         (n, C.c_int32) for n in ("in_h", "in_w", "rh", "rw", "row0", "rows", "top", "left", "flip", "ksize_h", "ksize_v",
                                  "pad_")]
+
+
+class ImgStackItem(C.Structure):
+    """Mirror of GsImgStackItem."""
+    _fields_ = [(n, C.c_void_p) for n in ("src", "idx_y", "w_y", "idx_x", "w_x")] + [
+        (n, C.c_int32) for n in ("dtype", "hwc", "in_h", "in_w", "c", "item", "c0", "rescale")] + [
+        (n, C.c_float) for n in ("lo", "hi", "noise_std")] + [("key0", C.c_uint32), ("key1", C.c_uint32), ("pad_", C.c_int32)]
 
 
 _PROTOS = {
@@ -204,6 +212,8 @@ _PROTOS = {
     "gs_u8_batch_resample_h": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gs_u8_batch_resample_v_crop_normalize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                                         C.c_void_p, C.c_void_p]),
+    "gs_img_stack_check": (C.c_int, [C.POINTER(ImgStackItem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gs_img_stack": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "gs_patch_zscore_ws_floats": (C.c_int64, []),
     "gs_patch_zscore": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,

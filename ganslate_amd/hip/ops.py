@@ -991,6 +991,62 @@ class HipOps(TwinSplit):
                 "gs_u8_batch_resample_v_crop_normalize")
         return table, tmp
 
+    # ---- device-side multi-modal 2-D samples (csrc/imgstack.hip) ------------------------------------------
+    IMG_DTYPES = {torch.uint8: L.IMG_DTYPES["uint8"], torch.float32: L.IMG_DTYPES["float32"]}
+
+    @staticmethod
+    def img_stack_table(items_host):
+        """ctypes array of GsImgStackItem for a batch. Each of `items_host` carries `src` — a contiguous (in_h, in_w) or
+        (in_h, in_w, c) uint8 / fp32 tensor ((c, in_h, in_w) with `hwc` False), or None for `c` zero channels — `taps_y` / `taps_x` (the tap tables of its two
+        axes: objects with `idx` int32 [n_out, 4], `w` fp32 [n_out, 4] and the `n_in` they were built for), `c`, `item`,
+        `c0`, `lo`, `hi`, `rescale`, `noise_std` and `key` (two 32-bit words). A table built for another source size is
+        refused here: its indices are the only thing between the kernel and a read outside the image. Pure host code."""
+        table = (L.ImgStackItem * len(items_host))()
+        for d, it in zip(table, items_host):
+            d.item, d.c0, d.c = int(it.item), int(it.c0), int(it.c)
+            if it.src is None:
+                continue
+            src, hwc = it.src, bool(getattr(it, "hwc", True))       # hwc False: a (c, in_h, in_w) source, planes apart
+            assert src.dtype in HipOps.IMG_DTYPES and src.is_contiguous() and src.dim() in (2, 3), (src.dtype, src.shape)
+            assert hwc or src.dim() == 3, src.shape
+            in_h, in_w = src.shape[:2] if hwc else src.shape[1:]
+            assert (1 if src.dim() == 2 else src.shape[2 if hwc else 0]) == d.c, (src.shape, d.c)
+            for taps, n_in in ((it.taps_y, in_h), (it.taps_x, in_w)):
+                assert taps.n_in == n_in and taps.idx.shape == taps.w.shape == (taps.idx.shape[0], 4), (taps.n_in, n_in)
+                assert taps.idx.dtype == torch.int32 and taps.w.dtype == torch.float32
+                assert taps.idx.is_contiguous() and taps.w.is_contiguous()
+            d.src, d.idx_y, d.w_y, d.idx_x, d.w_x = (t.data_ptr() for t in (src, it.taps_y.idx, it.taps_y.w, it.taps_x.idx,
+                                                                            it.taps_x.w))
+            d.dtype, d.hwc, d.in_h, d.in_w = HipOps.IMG_DTYPES[src.dtype], int(hwc), in_h, in_w
+            d.lo, d.hi, d.rescale, d.noise_std = float(it.lo), float(it.hi), int(bool(it.rescale)), float(it.noise_std or 0.0)
+            d.key0, d.key1 = int(it.key[0]) & 0xFFFFFFFF, int(it.key[1]) & 0xFFFFFFFF
+        return table
+
+    def img_stack_check(self, table, N, Cc, H, W):
+        """the library's validation of a HOST descriptor table; raises its error (the kernel cannot report one)"""
+        L.check(self.lib.gs_img_stack_check(table, len(table), N, Cc, H, W), "gs_img_stack_check")
+
+    def img_stack(self, items_host, out):
+        """Bicubic tensor resize + clamp + min-max + noise plane + channel concat of every (sample, modality) of a batch in
+        one launch: out fp32 (N, C, H, W) on the device, every element written once (zeros where an item has no source).
+        One descriptor table, validated on the host and uploaded with one copy; nothing synchronises. Returns the host
+        table. The caller vouches for the tap tables: every `idx` of `taps_y` / `taps_x` must lie in [0, in_h) / [0, in_w)
+        of its source. The tables live on the device and are not read back; what is checked here is only the `n_in` they
+        were declared for, so build them with data/multimodal_images.py `bicubic_taps`, as the pipeline does."""
+        assert out.dim() == 4 and out.is_contiguous() and out.dtype == torch.float32 and out.is_cuda, (out.shape, out.dtype)
+        N, Cc, H, W = out.shape
+        for it in items_host:
+            if it.src is not None:
+                assert it.src.device == out.device and it.taps_y.idx.device == out.device and it.taps_x.idx.device == out.device
+                assert it.taps_y.idx.shape[0] == H and it.taps_x.idx.shape[0] == W, (it.taps_y.idx.shape, it.taps_x.idx.shape)
+        table = self.img_stack_table(items_host)
+        self.img_stack_check(table, N, Cc, H, W)
+        staged = torch.empty(C.sizeof(table), dtype=torch.uint8, pin_memory=True)
+        staged.copy_(torch.frombuffer(table, dtype=torch.uint8))
+        dev = staged.to(out.device, non_blocking=True)
+        L.check(self.lib.gs_img_stack(_ptr(dev), len(table), _ptr(out), N, Cc, H, W, _stream()), "gs_img_stack")
+        return table
+
     VOL_DTYPES = {torch.float32: 0, torch.int16: 1}
 
     def patch_zscore(self, volume, start, size, out, scale_to_range=(-1.0, 1.0)):

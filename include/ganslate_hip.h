@@ -483,6 +483,45 @@ int gs_u8_batch_resample_h(const GsU8BatchItem* items, int32_t n, int32_t C, voi
 int gs_u8_batch_resample_v_crop_normalize(const GsU8BatchItem* items, int32_t n, int32_t C, const void* tmp, int32_t fh,
                                           int32_t fw, float* out, void* stream);
 
+/* ---- device-side multi-modal 2-D samples (csrc/imgstack.hip) --------------------------------------- */
+/* What the reference's ClearGrasp datasets do per modality on the host (projects/cleargrasp_depth_estimation/datasets/
+ * train_dataset.py:75-146, val_test_dataset.py:80-167): transforms.Resize(load_size, BICUBIC) on the fp32 tensor — torch's
+ * bicubic interpolation without antialiasing, cubic convolution A = -0.75, align_corners = False — clamp to the modality's
+ * range, min-max to [-1, 1], one noise plane on domain B's RGB, concat along channels; here one launch builds a whole fp32
+ * [N][C][H][W] batch from decoded images resident in device memory as stored. One descriptor per (sample, modality), in a
+ * device array; the pointers are device pointers. Tap tables of an axis n_in -> n_out: idx[o][4] the source indices
+ * f-1 .. f+2 clamped to [0, n_in - 1] and w[o][4] their weights c2(t+1), c1(t), c1(1-t), c2(2-t), with
+ * s = (o + 0.5) * n_in / n_out - 0.5, f = floor(s), t = s - f, computed by the caller in float64 and rounded once to
+ * fp32 (rows of 16 bytes, 16-byte aligned); the kernel computes no coordinate. Per element, fp32:
+ *   r = sum_j w_y[y][j] * sum_i w_x[x][i] * src[idx_y[y][j]][idx_x[x][i]][ch];  v = min(max(r, lo), hi);
+ *   rescale != 0: v = (v - lo) / (hi - lo), v = 2 v - 1;
+ *   noise_std > 0: v = min(max(v + noise_std * z, -1), 1), z = sqrt(-2 ln u1) * cos(2 pi u2) with
+ *   u1 = ((r0 >> 9) + 0.5) * 2^-23, u2 = (r1 >> 8) * 2^-24 from the first two words of Philox4x32-10 on the counter
+ *   (y * W + x, 0, 0, 0) and the key (key0, key1): the channels of a descriptor share the plane.
+ * src == NULL: the descriptor's c channels are written as zeros (tables and source fields unused). */
+enum { GS_IMG_U8 = 0, GS_IMG_F32 = 1 };
+typedef struct GsImgStackItem {
+  const void* src;              /* in_h x in_w x c (hwc != 0) or c x in_h x in_w (hwc == 0) elements of `dtype`, or NULL */
+  const int32_t* idx_y;         /* [H][4], w_y [H][4]: in_h -> H */
+  const float* w_y;
+  const int32_t* idx_x;         /* [W][4], w_x [W][4]: in_w -> W */
+  const float* w_x;
+  int32_t dtype, hwc;
+  int32_t in_h, in_w, c;        /* stored size, channels of the modality */
+  int32_t item, c0;             /* batch item and first output channel: out[item][c0 .. c0 + c) */
+  int32_t rescale;              /* 0: clamp only */
+  float lo, hi, noise_std;
+  uint32_t key0, key1;          /* Philox key of the noise plane */
+  int32_t pad_;
+} GsImgStackItem;
+/* Host-side validation of a descriptor table BEFORE it is uploaded (the kernel cannot report a bad descriptor): `items` is a
+ * HOST array here. Batch item inside [0, N), channels [c0, c0 + c) inside [0, C), every channel of every batch item written
+ * by exactly one descriptor; with a source: tables non-null, sizes positive, dtype known, lo < hi, noise_std >= 0. */
+int gs_img_stack_check(const GsImgStackItem* items, int32_t n, int32_t N, int32_t C, int32_t H, int32_t W);
+/* items: DEVICE array of n descriptors; grid (ceil(W / 256), H, n); out: N * C * H * W floats, each written once. */
+int gs_img_stack(const GsImgStackItem* items, int32_t n, float* out, int32_t N, int32_t C, int32_t H, int32_t W,
+                 void* stream);
+
 /* ---- device-side 3-D training patches ------------------------------------------- */
 /* What the 3-D datasets' workers do per sample on the host (projects/brats_mri_sequence_translation/datasets/
  * train_dataset.py:83-86 -> ganslate/data/utils/normalization.py:18-30): out = z_score_normalize(volume[z:z+d, y:y+h,
