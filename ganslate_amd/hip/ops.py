@@ -1357,6 +1357,68 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_mind_l1_backward(_ptr(x), _ptr(y), N, Cx, y.shape[1], H, W, *self._mind_args(cfg),
                                              _ptr(grad_scale), _ptr(grad_y), _ptr(scratch), _stream()), "gs_mind_l1_backward")
 
+    # ---- MIND structure-consistency loss for volumes (mind3d.hip) ---------------------------------------------------
+    MIND3D_CONFIG = {"non_local_region_size": 3, "patch_size": 5, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
+
+    @staticmethod
+    def _mind3d_check(*volumes):
+        """ValueError before any launch: [N, C, D, H, W] fp32 dense tensors on one device, equal in N, D, H and W"""
+        for t in volumes:
+            if t.dim() != 5:
+                raise ValueError(f"the volumetric MIND descriptor takes [N, C, D, H, W] volumes; got {tuple(t.shape)}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"the MIND kernels take fp32 volumes; got {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError("the MIND kernels take dense (contiguous) volumes")
+            if t.numel() == 0:
+                raise ValueError(f"empty volume batch {tuple(t.shape)}")
+        a = volumes[0]
+        for t in volumes[1:]:
+            if (t.shape[0], *t.shape[2:]) != (a.shape[0], *a.shape[2:]) or t.device != a.device:
+                raise ValueError(f"MIND loss: volumes differ in batch, extent or device: {tuple(a.shape)} vs {tuple(t.shape)}")
+
+    def _mind3d_args(self, cfg):
+        cfg = dict(self.MIND3D_CONFIG, **(cfg or {}))
+        return (int(cfg["non_local_region_size"]), int(cfg["patch_size"]), int(cfg["neighbor_size"]),
+                float(cfg["gaussian_patch_sigma"]))
+
+    def mind3d_descriptor(self, x, out=None, cfg=None):
+        """[N, C, D, H, W] fp32 -> [N, 27, D, H, W] MIND features of the channel mean (gs_mind3d_descriptor)"""
+        self._mind3d_check(x)
+        N, Cc, D, H, W = x.shape
+        if out is None:
+            out = torch.empty((N, 27, D, H, W), dtype=torch.float32, device=x.device)
+        self._mind3d_check(out)
+        if tuple(out.shape) != (N, 27, D, H, W):
+            raise ValueError(f"mind3d_descriptor: out must be {(N, 27, D, H, W)}, got {tuple(out.shape)}")
+        L.check(self.lib.gs_mind3d_descriptor(_ptr(x), N, Cc, D, H, W, *self._mind3d_args(cfg), _ptr(out), _stream()),
+                "gs_mind3d_descriptor")
+        return out
+
+    def mind3d_l1(self, x, y, out, cfg=None):
+        """out (0-d fp32) = sum |MIND(x) - MIND(y)| / (D H W 27): a sum over the batch, unweighted (gs_mind3d_l1)"""
+        self._mind3d_check(x, y)
+        if out.dtype != torch.float32 or out.numel() != 1:
+            raise ValueError("mind3d_l1: out must hold one fp32 value")
+        N, Cx, D, H, W = x.shape
+        scratch = torch.empty(self.lib.gs_mind3d_scratch_bytes(N, D, H, W, 0), dtype=torch.uint8, device=x.device)
+        L.check(self.lib.gs_mind3d_l1(_ptr(x), _ptr(y), N, Cx, y.shape[1], D, H, W, *self._mind3d_args(cfg), _ptr(out),
+                                      _ptr(scratch), _stream()), "gs_mind3d_l1")
+
+    def mind3d_l1_backward(self, x, y, grad_y, grad_scale=None, cfg=None):
+        """grad_y = grad_scale * d mind3d_l1(x, y) / dy; grad_scale is a device scalar (gs_mind3d_l1_backward)"""
+        self._mind3d_check(x, y)
+        self._mind3d_check(grad_y)
+        if grad_y.shape != y.shape:
+            raise ValueError(f"mind3d_l1_backward: grad_y must have y's shape {tuple(y.shape)}, got {tuple(grad_y.shape)}")
+        if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1):
+            raise ValueError("mind3d_l1_backward: grad_scale must hold one fp32 value")
+        N, Cx, D, H, W = x.shape
+        scratch = torch.empty(self.lib.gs_mind3d_scratch_bytes(N, D, H, W, 1), dtype=torch.uint8, device=x.device)
+        L.check(self.lib.gs_mind3d_l1_backward(_ptr(x), _ptr(y), N, Cx, y.shape[1], D, H, W, *self._mind3d_args(cfg),
+                                               _ptr(grad_scale), _ptr(grad_y), _ptr(scratch), _stream()),
+                "gs_mind3d_l1_backward")
+
     # ---- validation / test image metrics (valmetrics.hip) --------------------------------------------------
     VALMETRIC_COLUMNS = ("mae", "mse", "nmse", "psnr", "ssim", "nmi", "histogram_chi2")
 

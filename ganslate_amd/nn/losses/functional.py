@@ -1,5 +1,5 @@
 """Autograd entry points of the fused loss kernels (libganslate_hip: gs_l1, gs_mse_const, gs_adv_loss, gs_mean,
-gs_ssim_distance, gs_mind_l1, and the channel-window forms gs_l1_window / gs_ssim_distance_window). Each forward is one
+gs_ssim_distance, gs_mind_l1, gs_mind3d_l1, and the channel-window forms gs_l1_window / gs_ssim_distance_window). Each forward is one
 wavefront-reduced kernel writing a 0-d fp32 tensor; each backward is one elementwise kernel that folds the upstream scalar gradient in (passed as a device pointer — no host sync)."""
 import torch
 
@@ -225,6 +225,46 @@ def mind_structure_autograd(X, Y):
         if t.dim() != 4:
             raise ValueError(f"the structure loss takes [N, C, H, W] images (volumes are not supported); got {tuple(t.shape)}")
     return _MINDL1.apply(X.float(), Y.float())
+
+
+class _MIND3DL1(torch.autograd.Function):
+    """_MINDL1 for volumes: sum |f^X - f^Y| / (D H W 27) over the 27-channel volumetric MIND descriptors (gs_mind3d_l1 /
+    gs_mind3d_l1_backward, csrc/mind3d.hip); each side's gradient is computed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, X, Y):
+        ops = get_ops()
+        if not hasattr(ops, "mind3d_l1"):
+            raise NotImplementedError(f"the '{getattr(ops, 'name', type(ops).__name__)}' backend has no volumetric MIND "
+                                      "structure loss (mind3d_l1 / mind3d_l1_backward)")
+        X, Y = X.contiguous(), Y.contiguous()
+        out = torch.empty((), dtype=torch.float32, device=X.device)
+        ops.mind3d_l1(X, Y, out)
+        ctx.save_for_backward(X, Y)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, Y = ctx.saved_tensors
+        g = g.contiguous().float()
+        gx = gy = None
+        if ctx.needs_input_grad[1]:
+            gy = torch.empty_like(Y)
+            get_ops().mind3d_l1_backward(X, Y, gy, grad_scale=g)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(X)
+            get_ops().mind3d_l1_backward(Y, X, gx, grad_scale=g)
+        return gx, gy
+
+
+def mind3d_structure_autograd(X, Y):
+    """Differentiable structure-consistency distance sum |MIND(X) - MIND(Y)| / (D H W 27) of two [N, C, D, H, W] batches
+    (the volumetric definition of include/ganslate_hip.h, without lambda_structure; a sum over the batch, not a mean).
+    Volumes with several channels are reduced by their channel mean first; X and Y may differ in channels."""
+    for t in (X, Y):
+        if t.dim() != 5:
+            raise ValueError(f"the volumetric structure loss takes [N, C, D, H, W] volumes; got {tuple(t.shape)}")
+    return _MIND3DL1.apply(X.float(), Y.float())
 
 
 class _ScalarAffine(torch.autograd.Function):

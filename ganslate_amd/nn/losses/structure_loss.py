@@ -4,13 +4,18 @@ and of its tutorial docs/tutorials_basic/2_new_project.md, on the fused kernels 
 
 The descriptor is fixed to MIND_DESCRIPTOR_CONFIG (non-local region 9x9, patch 7x7, neighbourhood 3x3, sigma 2). Images
 with several channels are reduced to one plane by the mean over their channels; the project-specific channel slicing of the
-reference's v1 / v2 variants is left to the caller (slice before calling)."""
+reference's v1 / v2 variants is left to the caller (slice before calling).
+
+Volumes take MINDDescriptor3D / StructureLoss3D on the kernels of csrc/mind3d.hip: MIND3D_DESCRIPTOR_CONFIG (non-local region
+3x3x3, patch 5x5x5, neighbourhood 3x3x3, sigma 2), a definition of this project's own (include/ganslate_hip.h) — the
+reference has none. The 2-D classes refuse volumes and the 3-D classes refuse images."""
 import torch
 
 from ..native.backend import get_ops
-from .functional import mind_structure_autograd, scalar_affine
+from .functional import mind3d_structure_autograd, mind_structure_autograd, scalar_affine
 
 MIND_DESCRIPTOR_CONFIG = {"non_local_region_size": 9, "patch_size": 7, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
+MIND3D_DESCRIPTOR_CONFIG = {"non_local_region_size": 3, "patch_size": 5, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
 
 
 def _need(ops, method):
@@ -50,6 +55,47 @@ class StructureLoss:
         _need(get_ops(), "mind_l1")
         _need(get_ops(), "mind_l1_backward")
         return [(self.lambda_structure, mind_structure_autograd(input_, fake))]
+
+    def __call__(self, input_, fake):
+        (w, x), = self.terms(input_, fake)
+        return scalar_affine([x], [[w]])[0]
+
+
+class MINDDescriptor3D:
+    """volume [N, C, D, H, W] -> features [N, 27, D, H, W]; channel i is the shift with depth offset i % 3 - 1, row offset
+    (i // 3) % 3 - 1 and column offset i // 9 - 1. No gradient flows through it: the differentiable path is
+    StructureLoss3D."""
+
+    def __init__(self, **config):
+        unknown = set(config) - set(MIND3D_DESCRIPTOR_CONFIG)
+        if unknown:
+            raise TypeError(f"unknown MIND descriptor setting(s): {sorted(unknown)}")
+        self.config = dict(MIND3D_DESCRIPTOR_CONFIG, **config)
+
+    def __call__(self, volume):
+        if volume.dim() != 5:
+            raise ValueError(f"the volumetric MIND descriptor takes [N, C, D, H, W] volumes; got {tuple(volume.shape)}")
+        ops = get_ops()
+        _need(ops, "mind3d_descriptor")
+        with torch.no_grad():
+            return ops.mind3d_descriptor(volume.detach().contiguous().float(), cfg=self.config)
+
+
+class StructureLoss3D:
+    """lambda_structure * sum_{n,a,p} |f_a(input) - f_a(fake)| / (D H W 27): StructureLoss for volumes, a SUM over the batch
+    as well."""
+
+    def __init__(self, lambda_structure):
+        self.lambda_structure = lambda_structure
+
+    def terms(self, input_, fake):
+        """[(weight, 0-d loss)] whose weighted sum is the loss"""
+        for t in (input_, fake):
+            if t.dim() != 5:
+                raise ValueError(f"the volumetric structure loss takes [N, C, D, H, W] volumes; got {tuple(t.shape)}")
+        _need(get_ops(), "mind3d_l1")
+        _need(get_ops(), "mind3d_l1_backward")
+        return [(self.lambda_structure, mind3d_structure_autograd(input_, fake))]
 
     def __call__(self, input_, fake):
         (w, x), = self.terms(input_, fake)

@@ -708,6 +708,37 @@ int gs_mind_l1_backward(const float* x, const float* y, int32_t N, int32_t Cx, i
  * per sample, in place of the tensors autograd keeps for :172-181) */
 int64_t gs_mind_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t backward);
 
+/* ---- MIND structure-consistency loss for volumes (mind3d.hip) ----
+ * The reference has no volumetric MIND: this is the definition. Volumes are fp32 NCDHW, contiguous; I is the mean over the
+ * channels of a sample, zero outside the volume. With the 27 shifts a of the 3x3x3 non-local region, the 5x5x5 patch and the
+ * 3x3x3 neighbourhood (the only sizes built: anything else is refused with a message), eps = 1e-8:
+ *   d_a(r) = I(r + a) - I(r)                           (r inside; I(r + a) = 0 outside)
+ *   D_a(p) = sum_{q in 5^3, p+q inside} g(q) d_a(p+q)^2,  g(q) = exp(-|q|_2 / sigma^2)  (Euclidean distance, not squared;
+ *            distance and quotient in fp32, the exponential in double, stored as fp32, as gs_mind_* round theirs)
+ *   B_b(p) = sum_{q in 5^3, p+q inside} I(p+q+b) for the 27 shifts b of the neighbourhood;  V = variance of the 27, divisor 26
+ *   n_a = exp(-D_a / (V + eps));  f_a = n_a / sum_c n_c
+ *   L(X, Y) = sum_{n,a,p} |f_a^X - f_a^Y| / (D H W 27)   (a sum over the batch, not a mean)
+ * Channel i of the features has depth offset i % 3 - 1, row offset (i / 3) % 3 - 1 and column offset i / 9 - 1 (the first
+ * spatial axis runs fastest, as in gs_mind_descriptor). No float atomics: results are bitwise reproducible. All launches go
+ * to `stream`. Refused before any launch: null pointers, non-positive extents, 2^31 or more workgroups (one per 4 x 8 x 8
+ * box), a sample of 2^31 or more voxels. */
+/* out = [N, 27, D, H, W] features */
+int gs_mind3d_descriptor(const float* x, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, int32_t nl_size,
+                         int32_t patch_size, int32_t neighbor_size, float sigma, float* out, void* stream);
+/* out[0] = L(x, y); x has Cx channels, y has Cy. No 27-channel volume is written to memory. scratch =
+ * gs_mind3d_scratch_bytes(N, D, H, W, 0) bytes. */
+int gs_mind3d_l1(const float* x, const float* y, int32_t N, int32_t Cx, int32_t Cy, int32_t D, int32_t H, int32_t W,
+                 int32_t nl_size, int32_t patch_size, int32_t neighbor_size, float sigma, float* out, void* scratch,
+                 void* stream);
+/* gradient of gs_mind3d_l1 w.r.t. y (the loss is symmetric: swap x and y for the other one), [N, Cy, D, H, W], scaled by
+ * the upstream scalar grad_scale[0] (device pointer, NULL = 1). scratch = gs_mind3d_scratch_bytes(N, D, H, W, 1) bytes. */
+int gs_mind3d_l1_backward(const float* x, const float* y, int32_t N, int32_t Cx, int32_t Cy, int32_t D, int32_t H, int32_t W,
+                          int32_t nl_size, int32_t patch_size, int32_t neighbor_size, float sigma, const float* grad_scale,
+                          float* grad_y, void* scratch, void* stream);
+/* bytes of scratch for gs_mind3d_l1 (backward = 0: one partial per box) or gs_mind3d_l1_backward (backward = 1: 81 volumes
+ * per sample) */
+int64_t gs_mind3d_scratch_bytes(int32_t N, int32_t D, int32_t H, int32_t W, int32_t backward);
+
 /* ---- validation / test image metrics (ganslate/utils/metrics/val_test_metrics.py:37-166, valmetrics.hip) ----
  * t (target) and p (prediction): N samples of P planes of H x W fp32, contiguous. table = device [N][7] fp64, one row per
  * sample: mae, mse, nmse (:37-53), psnr = 10 log10(max(t)^2 / mse) (:56-59), ssim = mean over the P planes of skimage
