@@ -193,6 +193,8 @@ extern "C" int gs_image_to_act_backward(const void* g_pad, float* g_img, int32_t
   GS_REQUIRE(g_pad && g_img && N > 0 && C > 0 && Cp >= C && D > 0, "gs_image_to_act_backward: bad argument");
   GS_REQUIRE(fold == 0 || fold_mode == GS_BORDER_REFLECT || (fold_mode == GS_BORDER_REPLICATE && fold <= 3),
              "gs_image_to_act_backward: fold must be reflect, or replicate with fold <= 3");
+  GS_REQUIRE(fold == 0 || fold_mode != GS_BORDER_REFLECT || (H > fold && W > fold && (D == 1 || D > fold)),
+             "gs_image_to_act_backward: a reflect fold needs every folded extent > fold");
   const long long hw = (long long)D * H * W;
   hipLaunchKernelGGL(image_to_act_bwd_kernel, img_grid(hw, N), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(g_pad), g_img, C, D, H, W, Cp, fold, fold_mode, accumulate);

@@ -148,7 +148,11 @@ __global__ __launch_bounds__(256) void shiftadd_bwd_kernel(const float* g_img, c
 // apart between neighbouring threads, for the output conv's shift-add — 52 us for a 26 MB tensor whose stream time is 6 us
 // (profiles/r02_step_by_grid_v7.txt: 0.54 ms per training step in the four boundary transforms). Here a workgroup stages the
 // row segment it needs ONCE with 16-byte coalesced loads (or coalesced fp32 loads for the NCHW side) and every thread reads
-// its taps out of LDS. Same arithmetic, same summation order per output element -> bit-identical results.
+// its taps out of LDS. Same arithmetic, same summation order per output element -> bit-identical results, with one exception:
+// image_unfold_bwd_row_kernel sums tap by tap inside a source row and then adds the rows' partial sums, the per-pixel kernel
+// runs one chain through every source row. An output row with ONE source row (no fold, or away from the border) is
+// bit-identical; a border row with several fold sources associates differently and agrees to fp32 rounding of its terms only
+// (tests/test_boundary_edges_gpu.py asserts both halves).
 constexpr int WF_SEG = 256;
 
 __global__ __launch_bounds__(256) void shiftadd_to_image_row_kernel(const unsigned short* z, const float* bias, float* img,
@@ -328,8 +332,10 @@ extern "C" int gs_image_unfold(const float* img, void* act, int32_t N, int32_t C
                                int32_t k, int32_t p, int32_t border, void* stream) {
   GS_REQUIRE(img && act && N > 0 && C > 0 && rows > 0 && W > 0 && k > 0 && Qp >= k * C && (Qp & 7) == 0,
              "gs_image_unfold: bad argument (Qp must be a multiple of 8 and >= k*C)");
+  GS_REQUIRE(border != GS_BORDER_REFLECT || (W > p && W > k - 1 - p), "gs_image_unfold: reflect needs W > pad on either side");
   const long long segs = (W + WF_SEG - 1) / WF_SEG;
-  if (gs_opt(GS_OPT_WFOLD_ROWS) && rows * segs < (1LL << 31) && N <= 65535) {
+  // the row form stages C rows of WF_SEG + k - 1 floats: beyond 48 KiB (C > 46 at k = 7) the per-pixel kernel runs
+  if (gs_opt(GS_OPT_WFOLD_ROWS) && (long long)C * (WF_SEG + k - 1) * 4 <= 48 * 1024 && rows * segs < (1LL << 31) && N <= 65535) {
     const int lds = C * (WF_SEG + k - 1) * 4;
     hipLaunchKernelGGL(image_unfold_row_kernel, dim3((unsigned)(rows * segs), N), dim3(256), lds,
                        static_cast<hipStream_t>(stream), img, static_cast<unsigned short*>(act), C, (long long)rows, W, Qp, k,
@@ -349,6 +355,8 @@ extern "C" int gs_image_unfold_backward(const void* g, float* g_img, int32_t N, 
   GS_REQUIRE(g && g_img && N > 0 && C > 0 && D > 0 && H > 0 && W > 0 && k > 0 && Qp >= k * C,
              "gs_image_unfold_backward: bad argument");
   GS_REQUIRE(border != GS_BORDER_REPLICATE || (fold <= 3 && p <= 3), "gs_image_unfold_backward: replicate needs pad <= 3");
+  GS_REQUIRE(border != GS_BORDER_REFLECT || (W > p && W > k - 1 - p && H > fold && (D == 1 || D > fold)),
+             "gs_image_unfold_backward: reflect needs every padded extent > its pad");
   // the sum over fold sources is taken source row by source row here, tap by tap inside a row, as in the per-pixel kernel
   // when there is one source row; border rows (several fold sources) add the rows' partial sums in the same (a, b) order
   if (gs_opt(GS_OPT_WFOLD_ROWS) && C <= 4 && W <= 1024 && (Qp & 7) == 0 && (long long)W * Qp * 2 <= 48 * 1024 && (long long)D * H < (1LL << 31) && N <= 65535) {

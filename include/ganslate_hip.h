@@ -401,8 +401,9 @@ int gs_act_to_image(const void* act, float* img, int32_t N, int32_t C, int32_t H
 int gs_act_to_image_backward(const float* g_img, const float* out_img, void* g_act, int32_t N, int32_t C,
                              int32_t H, int32_t W, int32_t Cp, int32_t act_kind, void* stream);
 /* gradient of gs_image_to_act composed with the first conv's padding fold: g_pad act (padded by fold)
- * -> NC(D)HW fp32 image gradient; accumulate != 0 adds into g_img. The other three boundary functions are
- * layout-only: a volume goes through them with H := D*H. */
+ * -> NC(D)HW fp32 image gradient; accumulate != 0 adds into g_img. A reflect fold needs every folded extent (H, W, and D
+ * when D > 1) > fold, a replicate fold <= 3. The other three boundary functions are layout-only: a volume goes through them
+ * with H := D*H. */
 int gs_image_to_act_backward(const void* g_pad, float* g_img, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                              int32_t Cp, int32_t fold, int32_t fold_mode, int32_t accumulate, void* stream);
 
@@ -411,7 +412,8 @@ int gs_image_to_act_backward(const void* g_pad, float* g_img, int32_t N, int32_t
  * axis are moved into the channel axis and the conv itself runs with a k x [k x] 1 kernel through gs_gconv_forward /
  * gs_wgrad; these are the boundary transforms and their adjoints. `rows` = D*H of a volume (or H of an image).
  *   unfold   : act[n, r, j][dw*C + c] = img[n][c][r][B(j + dw - p)], channels >= k*C zero (fused NCHW fp32 -> NHWC bf16)
- *   shift-add: img[n][co][r][j] = act(bias[co] + sum_dw z[n, r, j + dw][dw*Co + co]),  z is W + k - 1 wide */
+ *   shift-add: img[n][co][r][j] = act(bias[co] + sum_dw z[n, r, j + dw][dw*Co + co]),  z is W + k - 1 wide
+ * A reflect border needs W > p and W > k - 1 - p (and, in the adjoint, H > fold, D > fold when D > 1). */
 int gs_image_unfold(const float* img, void* act, int32_t N, int32_t C, int64_t rows, int32_t W, int32_t Qp, int32_t k,
                     int32_t p, int32_t border, void* stream);
 /* adjoint of gs_image_unfold composed with the (depth, row) padding fold of the stem conv: g is the data gradient of the

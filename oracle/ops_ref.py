@@ -543,7 +543,8 @@ class RefOps(TwinSplit):
         xl = img.movedim(1, -1)                                   # [N, ..., W, C]
         for dw in range(k):
             j, ok = _border(torch.arange(W) + dw - p, W, border)
-            v = xl.index_select(-2, j) * ok.float()[:, None]
+            v = xl.index_select(-2, j)
+            v = torch.where(ok[:, None], v, torch.zeros_like(v))  # (a zero, not v * 0: that is -0 for v < 0 and NaN for inf)
             act_t[..., dw * Cc:(dw + 1) * Cc] = v.to(act_t.dtype)
 
     def image_unfold_backward(self, g, g_img, k, p, fold, border, accumulate=False):
@@ -554,9 +555,10 @@ class RefOps(TwinSplit):
         for ax, n in enumerate(sp[:-1], start=1):
             if fold == 0 or (len(sp) == 3 and ax == 1 and n == 1):
                 continue
-            src, _ = _border(torch.arange(n + 2 * fold) - fold, n, border)
+            src, ok = _border(torch.arange(n + 2 * fold) - fold, n, border)
             shape = list(gf.shape); shape[ax] = n
-            nxt = torch.zeros(shape); nxt.index_add_(ax, src, gf); gf = nxt
+            keep = ok.float().view([-1 if a == ax else 1 for a in range(gf.dim())])    # zero border: the pad cells are dropped
+            nxt = torch.zeros(shape); nxt.index_add_(ax, src, gf * keep); gf = nxt
         out = torch.zeros(*g_img.shape[:1], *sp, Cc)             # channels-last
         for dw in range(k):
             j, ok = _border(torch.arange(W) + dw - p, W, border)
