@@ -1,5 +1,7 @@
 """Device validation / test metrics (valmetrics.hip through HipOps.valmetrics and utils/val_metrics.py) against the
-float64 restatement of val_test_metrics.py (tests/valmetrics_ref.py), and the GPU Validator / Tester built on them."""
+float64 restatement of val_test_metrics.py (tests/valmetrics_ref.py), and the GPU Validator / Tester built on them.
+The SSIM tolerance (abs 1e-5) is the slack of the restatement's cumulative sums: the kernel's window sums are fp64 sums of
+fp64 products, and tests/test_valmetrics_edges_gpu.py holds every column to the kernel's own rounding."""
 import csv
 from pathlib import Path
 

@@ -1,8 +1,9 @@
 """Masked device validation / test metrics (valmetrics.hip through HipOps.valmetrics_masked and utils/val_metrics.py)
 against the float64 restatement of the reference's masked arrays (tests/valmetrics_masked_ref.py), and the GPU
 Validator / Tester reporting `<metric>_<label>` for datasets that yield masks. Tolerances are those of
-tests/test_valmetrics_gpu.py, for its reasons: fp64 accumulation in another order than numpy's (rel 1e-9), SSIM window
-sums of float32 products against cumulative sums (abs 1e-5), bin counts exact."""
+tests/test_valmetrics_gpu.py, for its reasons: fp64 accumulation in another order than numpy's (rel 1e-9), SSIM against
+the restatement's cumulative sums (abs 1e-5; the kernel's window sums are fp64 sums of fp64 products, so the slack is the
+cumulative sums', and tests/test_valmetrics_edges_gpu.py holds the kernel to its own rounding), bin counts exact."""
 import csv
 from pathlib import Path
 
