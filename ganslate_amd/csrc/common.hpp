@@ -189,6 +189,22 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// out = scale * the sum of n per-workgroup partials (float or double), by one workgroup of 256, in double: thread t takes
+// t, t + 256, ... in index order, then a fixed tree over the threads. MAX_THREADS is the launch bound the code is generated
+// for (1024 = none: SSIM's reducer never had one and keeps its code).
+template <typename P, int MAX_THREADS>
+__global__ __launch_bounds__(MAX_THREADS) void final_sum_kernel(const P* partial, int n, double scale, float* out) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
+}
 
 // ---- Adam (optim.hip; wgrad.hip's fused epilogue) ----------------------------------------------------------------------
 // One element of the update; the same expression for the scalar tail and the four lanes of a 16-byte access.

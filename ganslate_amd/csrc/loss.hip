@@ -376,18 +376,6 @@ __global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* x, int
                                                              float* maps, size_t map_stride) {
   ssim_tile<float, true>(x, xpl, xstride, y, H, W, tiles_w, tiles_h, grad_scale, inv_cnt, maps, map_stride);
 }
-// the per-tile partials (float or double) summed in index order by one workgroup, in double
-template <typename P>
-__global__ void ssim_final_kernel(const P* partial, int n, double scale, float* out) {
-  __shared__ double sh[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
-}
-
 static int ssim_init_gauss() {
   static bool init = false;
   if (!init) {
@@ -432,7 +420,7 @@ static int ssim_forward(void (*kernel)(const float*, int, long long, const float
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, x, xpl, xstride, y, H, W, tw, th, partial);
   double scale = 1.0 / ((double)NC * (H - 10) * (W - 10));
   if (std::is_same<P, float>::value) scale = (double)(float)scale;      // the fp32 path has always rounded its scale to fp32
-  hipLaunchKernelGGL(ssim_final_kernel<P>, dim3(1), dim3(256), 0, st, partial, blocks, scale, out);
+  hipLaunchKernelGGL((final_sum_kernel<P, 1024>), dim3(1), dim3(256), 0, st, partial, blocks, scale, out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }

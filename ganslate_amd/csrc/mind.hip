@@ -15,8 +15,7 @@
 // it. The 81 numerators of a pixel stay in registers (the shift loop is unrolled, so every index is a constant) until their
 // sum is known: no 81-channel map leaves the workgroup in the forward. No atomics anywhere: the loss is one partial per
 // workgroup summed in index order by a second launch, the backward is a gather.
-#include "common.hpp"
-#include <math.h>
+#include "mind_common.hpp"
 
 #define MIND_T 16                    // tile edge
 #define MIND_PW 30                   // plane tile: MIND_T + 2 * 7
@@ -24,7 +23,6 @@
 #define MIND_DS 48                   // ... its row stride: the four rows of a wave read disjoint banks (0, 48, 32, 16 mod 64)
 #define MIND_EW 24                   // backward: tile of E_a, MIND_T + 2 * 4
 #define MIND_NS 81
-#define MIND_EPS 1e-8f
 
 struct MindW { float g[49]; };       // the patch weights, a kernel argument (scalar registers)
 
@@ -190,14 +188,6 @@ __global__ __launch_bounds__(256) void mind_descriptor_kernel(const float* x, in
   }
 }
 
-__device__ __forceinline__ float mind_block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) sh[wv] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 __global__ __launch_bounds__(256) void mind_l1_kernel(const float* x, const float* y, int Cx, int Cy, int H, int W,
                                                       int tiles_w, int tiles_h, const MindW w, float* partial) {
   __shared__ float sI[MIND_PW * MIND_PW];
@@ -215,20 +205,6 @@ __global__ __launch_bounds__(256) void mind_l1_kernel(const float* x, const floa
   });
   acc = mind_block_sum((gy < H && gx < W) ? acc : 0.f, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-// partials in index order: thread t takes t, t + 256, ..., then a fixed tree over the threads
-__global__ __launch_bounds__(256) void mind_final_kernel(const float* partial, int n, double scale, float* out) {
-  __shared__ double sh[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
 }
 
 // ---- backward w.r.t. the second image ---------------------------------------------------------------------------------
@@ -357,34 +333,25 @@ __global__ __launch_bounds__(256) void mind_gather_kernel(const float* y, int C,
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-// the reference's weights, rounded as it rounds them (:126-135): the distance and the quotient in fp32, the exponential in
-// double, the result stored as fp32
+// the reference's weights (mind_weight), by position in the patch
 static MindW mind_weights(float sigma) {
   MindW w;
-  const float sigma2 = (float)((double)sigma * (double)sigma);
   for (int x = 0; x < 7; ++x)
-    for (int y = 0; y < 7; ++y) {
-      const float d = sqrtf((float)((x - 3) * (x - 3) + (y - 3) * (y - 3)));
-      const float e = -d / sigma2;
-      w.g[x * 7 + y] = (float)exp((double)e);
-    }
+    for (int y = 0; y < 7; ++y) w.g[x * 7 + y] = mind_weight((x - 3) * (x - 3) + (y - 3) * (y - 3), sigma);
   return w;
 }
 
 struct MindGrid { int th, tw; int64_t blocks; };
 static MindGrid mind_grid(int N, int H, int W) {
   MindGrid g;
-  g.th = (H + MIND_T - 1) / MIND_T;
-  g.tw = (W + MIND_T - 1) / MIND_T;
+  g.th = mind_ceil_div(H, MIND_T);
+  g.tw = mind_ceil_div(W, MIND_T);
   g.blocks = (int64_t)N * g.th * g.tw;
   return g;
 }
 
 #define MIND_REQUIRE_SIZES(name)                                                                                        \
-  GS_REQUIRE(nl_size == 9 && patch_size == 7 && neighbor_size == 3,                                                     \
-             name ": only non_local_region_size 9, patch_size 7, neighbor_size 3 are built (got %d, %d, %d)", nl_size,  \
-             patch_size, neighbor_size);                                                                                \
-  GS_REQUIRE(sigma > 0.f && N > 0 && H > 0 && W > 0, name ": bad argument");                                            \
+  if (int rc = mind_check_sizes(name, 9, 7, nl_size, patch_size, neighbor_size, sigma, N > 0 && H > 0 && W > 0)) return rc; \
   GS_REQUIRE(mind_grid(N, H, W).blocks < (1ll << 31), name ": too many tiles")
 
 extern "C" int64_t gs_mind_scratch_bytes(int32_t N, int32_t H, int32_t W, int32_t backward) {
@@ -414,7 +381,7 @@ extern "C" int gs_mind_l1(const float* x, const float* y, int32_t N, int32_t Cx,
   float* partial = static_cast<float*>(scratch);
   hipLaunchKernelGGL(mind_l1_kernel, dim3((unsigned)g.blocks), dim3(256), 0, st, x, y, Cx, Cy, H, W, g.tw, g.th,
                      mind_weights(sigma), partial);
-  hipLaunchKernelGGL(mind_final_kernel, dim3(1), dim3(256), 0, st, partial, (int)g.blocks,
+  hipLaunchKernelGGL((final_sum_kernel<float, 256>), dim3(1), dim3(256), 0, st, (const float*)partial, (int)g.blocks,
                      1.0 / ((double)H * W * MIND_NS), out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;

@@ -17,8 +17,7 @@
 // forward. The 27 neighbourhood sums are box sums over a clipped box, a product of three clipped intervals: they are built
 // separably (columns, then rows, then depth), 343 LDS reads per voxel instead of 3375. No atomics anywhere: the loss is one
 // partial per workgroup summed in index order by a second launch, the backward is a gather.
-#include "common.hpp"
-#include <math.h>
+#include "mind_common.hpp"
 
 #define M3_BZ 4                      // box: depth
 #define M3_BY 8                      // ... rows
@@ -34,7 +33,6 @@
 #define M3_EZ 6                      // backward: box of E_a with a ring of 1, M3_BZ + 2 planes
 #define M3_EY 10                     // ... of M3_BY + 2 rows of M3_BX + 2 columns
 #define M3_NS 27
-#define M3_EPS 1e-8f
 
 struct Mind3W { float g[13]; };      // the patch weight by SQUARED distance (0 .. 12), a kernel argument (scalar registers)
 
@@ -130,7 +128,7 @@ __device__ __forceinline__ Mind3V mind3_variance(const float* sI, const Mind3Pos
 #pragma unroll
   for (int k = 0; k < M3_NS; ++k) { const float d = v.B[k] - m; s += d * d; }
   v.mean = m;
-  v.veps = s / 26.f + M3_EPS;
+  v.veps = s / 26.f + MIND_EPS;
   return v;
 }
 
@@ -253,14 +251,6 @@ __global__ __launch_bounds__(256) void mind3d_descriptor_kernel(const float* x, 
   }
 }
 
-__device__ __forceinline__ float mind3_block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) sh[wv] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 __global__ __launch_bounds__(256) void mind3d_l1_kernel(const float* x, const float* y, int Cx, int Cy, int D, int H, int W,
                                                         int bw, int bh, int bd, const Mind3W w, float* partial) {
   __shared__ float sI[M3_IN];
@@ -278,22 +268,8 @@ __global__ __launch_bounds__(256) void mind3d_l1_kernel(const float* x, const fl
     constexpr int a = decltype(ic)::value;
     acc += fabsf(nx[a] / Zx - ny[a] / Zy);
   });
-  acc = mind3_block_sum((gz < D && gy < H && gx < W) ? acc : 0.f, sh);
+  acc = mind_block_sum((gz < D && gy < H && gx < W) ? acc : 0.f, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-// partials in index order: thread t takes t, t + 256, ..., then a fixed tree over the threads
-__global__ __launch_bounds__(256) void mind3d_final_kernel(const float* partial, int n, double scale, float* out) {
-  __shared__ double sh[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
 }
 
 // ---- backward w.r.t. the second volume --------------------------------------------------------------------------------
@@ -435,34 +411,26 @@ __global__ __launch_bounds__(256) void mind3d_gather_kernel(const float* y, int 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-// the weights rounded as mind.hip's mind_weights rounds them: the distance and the quotient in fp32, the exponential in
-// double, the result stored as fp32; the squared distance of a tap of the 5^3 patch is an integer in 0 .. 12
+// the weights (mind_weight) by squared distance: that of a tap of the 5^3 patch is an integer in 0 .. 12
 static Mind3W mind3_weights(float sigma) {
   Mind3W w;
-  const float sigma2 = (float)((double)sigma * (double)sigma);
-  for (int r2 = 0; r2 < 13; ++r2) {
-    const float d = sqrtf((float)r2);
-    const float e = -d / sigma2;
-    w.g[r2] = (float)exp((double)e);
-  }
+  for (int r2 = 0; r2 < 13; ++r2) w.g[r2] = mind_weight(r2, sigma);
   return w;
 }
 
 struct Mind3Grid { int bd, bh, bw; int64_t blocks; };
 static Mind3Grid mind3_grid(int N, int D, int H, int W) {
   Mind3Grid g;
-  g.bd = (D + M3_BZ - 1) / M3_BZ;
-  g.bh = (H + M3_BY - 1) / M3_BY;
-  g.bw = (W + M3_BX - 1) / M3_BX;
+  g.bd = mind_ceil_div(D, M3_BZ);
+  g.bh = mind_ceil_div(H, M3_BY);
+  g.bw = mind_ceil_div(W, M3_BX);
   g.blocks = (int64_t)N * g.bd * g.bh * g.bw;
   return g;
 }
 
 #define MIND3_REQUIRE_SIZES(name)                                                                                       \
-  GS_REQUIRE(nl_size == 3 && patch_size == 5 && neighbor_size == 3,                                                     \
-             name ": only non_local_region_size 3, patch_size 5, neighbor_size 3 are built (got %d, %d, %d)", nl_size,  \
-             patch_size, neighbor_size);                                                                                \
-  GS_REQUIRE(sigma > 0.f && N > 0 && D > 0 && H > 0 && W > 0, name ": bad argument");                                   \
+  if (int rc = mind_check_sizes(name, 3, 5, nl_size, patch_size, neighbor_size, sigma, N > 0 && D > 0 && H > 0 && W > 0))   \
+    return rc;                                                                                                          \
   GS_REQUIRE((int64_t)D * H * W < (1ll << 31), name ": a sample of 2^31 or more voxels");                               \
   GS_REQUIRE(mind3_grid(N, D, H, W).blocks < (1ll << 31), name ": too many boxes")
 
@@ -493,7 +461,7 @@ extern "C" int gs_mind3d_l1(const float* x, const float* y, int32_t N, int32_t C
   float* partial = static_cast<float*>(scratch);
   hipLaunchKernelGGL(mind3d_l1_kernel, dim3((unsigned)g.blocks), dim3(256), 0, st, x, y, Cx, Cy, D, H, W, g.bw, g.bh, g.bd,
                      mind3_weights(sigma), partial);
-  hipLaunchKernelGGL(mind3d_final_kernel, dim3(1), dim3(256), 0, st, partial, (int)g.blocks,
+  hipLaunchKernelGGL((final_sum_kernel<float, 256>), dim3(1), dim3(256), 0, st, (const float*)partial, (int)g.blocks,
                      1.0 / ((double)D * H * W * M3_NS), out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;

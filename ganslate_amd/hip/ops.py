@@ -1296,128 +1296,105 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_ssim_distance(_ptr(x), _ptr(y), NC, H, W, _ptr(out), _ptr(scratch), _stream()),
                 "gs_ssim_distance")
 
-    # ---- MIND structure-consistency loss (mind.hip) ---------------------------------------------------------------
+    # ---- MIND structure-consistency loss for images and volumes (mind.hip, mind3d.hip) -------------------------------
     MIND_CONFIG = {"non_local_region_size": 9, "patch_size": 7, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
+    MIND3D_CONFIG = {"non_local_region_size": 3, "patch_size": 5, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
+    # what differs between the two ranks: the prefix of the methods and of the library's four entry points, the tensors'
+    # rank, the descriptor's channels, the default config and the words of the refusals
+    _MIND = {
+        2: dict(name="mind", dim=4, channels=81, config=MIND_CONFIG, noun="image",
+                takes="the MIND descriptor takes [N, C, H, W] images (volumes are not supported)"),
+        3: dict(name="mind3d", dim=5, channels=27, config=MIND3D_CONFIG, noun="volume",
+                takes="the volumetric MIND descriptor takes [N, C, D, H, W] volumes"),
+    }
 
     @staticmethod
-    def _mind_check(*images):
-        """ValueError before any launch: [N, C, H, W] fp32 dense tensors on one device, equal in N, H and W"""
-        for t in images:
-            if t.dim() != 4:
-                raise ValueError(f"the MIND descriptor takes [N, C, H, W] images (volumes are not supported); got {tuple(t.shape)}")
+    def _mind_check(r, *samples):
+        """ValueError before any launch: fp32 dense tensors of the rank's shape on one device, equal in batch and extent"""
+        noun = r["noun"]
+        for t in samples:
+            if t.dim() != r["dim"]:
+                raise ValueError(f"{r['takes']}; got {tuple(t.shape)}")
             if t.dtype != torch.float32:
-                raise ValueError(f"the MIND kernels take fp32 images; got {t.dtype}")
+                raise ValueError(f"the MIND kernels take fp32 {noun}s; got {t.dtype}")
             if not t.is_contiguous():
-                raise ValueError("the MIND kernels take dense (contiguous) images")
+                raise ValueError(f"the MIND kernels take dense (contiguous) {noun}s")
             if t.numel() == 0:
-                raise ValueError(f"empty image batch {tuple(t.shape)}")
-        a = images[0]
-        for t in images[1:]:
-            if (t.shape[0], t.shape[2], t.shape[3]) != (a.shape[0], a.shape[2], a.shape[3]) or t.device != a.device:
-                raise ValueError(f"MIND loss: images differ in batch, extent or device: {tuple(a.shape)} vs {tuple(t.shape)}")
+                raise ValueError(f"empty {noun} batch {tuple(t.shape)}")
+        a = samples[0]
+        for t in samples[1:]:
+            if (t.shape[0], *t.shape[2:]) != (a.shape[0], *a.shape[2:]) or t.device != a.device:
+                raise ValueError(f"MIND loss: {noun}s differ in batch, extent or device: {tuple(a.shape)} vs {tuple(t.shape)}")
 
-    def _mind_args(self, cfg):
-        cfg = dict(self.MIND_CONFIG, **(cfg or {}))
+    @staticmethod
+    def _mind_args(r, cfg):
+        cfg = dict(r["config"], **(cfg or {}))
         return (int(cfg["non_local_region_size"]), int(cfg["patch_size"]), int(cfg["neighbor_size"]),
                 float(cfg["gaussian_patch_sigma"]))
+
+    def _mind_descriptor(self, r, x, out, cfg):
+        self._mind_check(r, x)
+        N, Cc, *ext = x.shape
+        shape = (N, r["channels"], *ext)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        self._mind_check(r, out)
+        if tuple(out.shape) != shape:
+            raise ValueError(f"{r['name']}_descriptor: out must be {shape}, got {tuple(out.shape)}")
+        entry = f"gs_{r['name']}_descriptor"
+        L.check(getattr(self.lib, entry)(_ptr(x), N, Cc, *ext, *self._mind_args(r, cfg), _ptr(out), _stream()), entry)
+        return out
+
+    def _mind_scratch(self, r, x, backward):
+        nbytes = getattr(self.lib, f"gs_{r['name']}_scratch_bytes")(x.shape[0], *x.shape[2:], backward)
+        return torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+
+    def _mind_l1(self, r, x, y, out, cfg):
+        self._mind_check(r, x, y)
+        if out.dtype != torch.float32 or out.numel() != 1:
+            raise ValueError(f"{r['name']}_l1: out must hold one fp32 value")
+        N, Cx, *ext = x.shape
+        scratch = self._mind_scratch(r, x, 0)
+        entry = f"gs_{r['name']}_l1"
+        L.check(getattr(self.lib, entry)(_ptr(x), _ptr(y), N, Cx, y.shape[1], *ext, *self._mind_args(r, cfg), _ptr(out),
+                                         _ptr(scratch), _stream()), entry)
+
+    def _mind_l1_backward(self, r, x, y, grad_y, grad_scale, cfg):
+        self._mind_check(r, x, y)
+        self._mind_check(r, grad_y)
+        if grad_y.shape != y.shape:
+            raise ValueError(f"{r['name']}_l1_backward: grad_y must have y's shape {tuple(y.shape)}, got {tuple(grad_y.shape)}")
+        if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1):
+            raise ValueError(f"{r['name']}_l1_backward: grad_scale must hold one fp32 value")
+        N, Cx, *ext = x.shape
+        scratch = self._mind_scratch(r, x, 1)
+        entry = f"gs_{r['name']}_l1_backward"
+        L.check(getattr(self.lib, entry)(_ptr(x), _ptr(y), N, Cx, y.shape[1], *ext, *self._mind_args(r, cfg),
+                                         _ptr(grad_scale), _ptr(grad_y), _ptr(scratch), _stream()), entry)
 
     def mind_descriptor(self, x, out=None, cfg=None):
         """[N, C, H, W] fp32 -> [N, 81, H, W] MIND features of the channel mean (gs_mind_descriptor)"""
-        self._mind_check(x)
-        N, Cc, H, W = x.shape
-        if out is None:
-            out = torch.empty((N, 81, H, W), dtype=torch.float32, device=x.device)
-        self._mind_check(out)
-        if tuple(out.shape) != (N, 81, H, W):
-            raise ValueError(f"mind_descriptor: out must be {(N, 81, H, W)}, got {tuple(out.shape)}")
-        L.check(self.lib.gs_mind_descriptor(_ptr(x), N, Cc, H, W, *self._mind_args(cfg), _ptr(out), _stream()),
-                "gs_mind_descriptor")
-        return out
+        return self._mind_descriptor(self._MIND[2], x, out, cfg)
 
     def mind_l1(self, x, y, out, cfg=None):
         """out (0-d fp32) = sum |MIND(x) - MIND(y)| / (H W 81): a sum over the batch, unweighted (gs_mind_l1)"""
-        self._mind_check(x, y)
-        if out.dtype != torch.float32 or out.numel() != 1:
-            raise ValueError("mind_l1: out must hold one fp32 value")
-        N, Cx, H, W = x.shape
-        scratch = torch.empty(self.lib.gs_mind_scratch_bytes(N, H, W, 0), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.gs_mind_l1(_ptr(x), _ptr(y), N, Cx, y.shape[1], H, W, *self._mind_args(cfg), _ptr(out),
-                                    _ptr(scratch), _stream()), "gs_mind_l1")
+        self._mind_l1(self._MIND[2], x, y, out, cfg)
 
     def mind_l1_backward(self, x, y, grad_y, grad_scale=None, cfg=None):
         """grad_y = grad_scale * d mind_l1(x, y) / dy; grad_scale is a device scalar (gs_mind_l1_backward)"""
-        self._mind_check(x, y)
-        self._mind_check(grad_y)
-        if grad_y.shape != y.shape:
-            raise ValueError(f"mind_l1_backward: grad_y must have y's shape {tuple(y.shape)}, got {tuple(grad_y.shape)}")
-        if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1):
-            raise ValueError("mind_l1_backward: grad_scale must hold one fp32 value")
-        N, Cx, H, W = x.shape
-        scratch = torch.empty(self.lib.gs_mind_scratch_bytes(N, H, W, 1), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.gs_mind_l1_backward(_ptr(x), _ptr(y), N, Cx, y.shape[1], H, W, *self._mind_args(cfg),
-                                             _ptr(grad_scale), _ptr(grad_y), _ptr(scratch), _stream()), "gs_mind_l1_backward")
-
-    # ---- MIND structure-consistency loss for volumes (mind3d.hip) ---------------------------------------------------
-    MIND3D_CONFIG = {"non_local_region_size": 3, "patch_size": 5, "neighbor_size": 3, "gaussian_patch_sigma": 2.0}
-
-    @staticmethod
-    def _mind3d_check(*volumes):
-        """ValueError before any launch: [N, C, D, H, W] fp32 dense tensors on one device, equal in N, D, H and W"""
-        for t in volumes:
-            if t.dim() != 5:
-                raise ValueError(f"the volumetric MIND descriptor takes [N, C, D, H, W] volumes; got {tuple(t.shape)}")
-            if t.dtype != torch.float32:
-                raise ValueError(f"the MIND kernels take fp32 volumes; got {t.dtype}")
-            if not t.is_contiguous():
-                raise ValueError("the MIND kernels take dense (contiguous) volumes")
-            if t.numel() == 0:
-                raise ValueError(f"empty volume batch {tuple(t.shape)}")
-        a = volumes[0]
-        for t in volumes[1:]:
-            if (t.shape[0], *t.shape[2:]) != (a.shape[0], *a.shape[2:]) or t.device != a.device:
-                raise ValueError(f"MIND loss: volumes differ in batch, extent or device: {tuple(a.shape)} vs {tuple(t.shape)}")
-
-    def _mind3d_args(self, cfg):
-        cfg = dict(self.MIND3D_CONFIG, **(cfg or {}))
-        return (int(cfg["non_local_region_size"]), int(cfg["patch_size"]), int(cfg["neighbor_size"]),
-                float(cfg["gaussian_patch_sigma"]))
+        self._mind_l1_backward(self._MIND[2], x, y, grad_y, grad_scale, cfg)
 
     def mind3d_descriptor(self, x, out=None, cfg=None):
         """[N, C, D, H, W] fp32 -> [N, 27, D, H, W] MIND features of the channel mean (gs_mind3d_descriptor)"""
-        self._mind3d_check(x)
-        N, Cc, D, H, W = x.shape
-        if out is None:
-            out = torch.empty((N, 27, D, H, W), dtype=torch.float32, device=x.device)
-        self._mind3d_check(out)
-        if tuple(out.shape) != (N, 27, D, H, W):
-            raise ValueError(f"mind3d_descriptor: out must be {(N, 27, D, H, W)}, got {tuple(out.shape)}")
-        L.check(self.lib.gs_mind3d_descriptor(_ptr(x), N, Cc, D, H, W, *self._mind3d_args(cfg), _ptr(out), _stream()),
-                "gs_mind3d_descriptor")
-        return out
+        return self._mind_descriptor(self._MIND[3], x, out, cfg)
 
     def mind3d_l1(self, x, y, out, cfg=None):
         """out (0-d fp32) = sum |MIND(x) - MIND(y)| / (D H W 27): a sum over the batch, unweighted (gs_mind3d_l1)"""
-        self._mind3d_check(x, y)
-        if out.dtype != torch.float32 or out.numel() != 1:
-            raise ValueError("mind3d_l1: out must hold one fp32 value")
-        N, Cx, D, H, W = x.shape
-        scratch = torch.empty(self.lib.gs_mind3d_scratch_bytes(N, D, H, W, 0), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.gs_mind3d_l1(_ptr(x), _ptr(y), N, Cx, y.shape[1], D, H, W, *self._mind3d_args(cfg), _ptr(out),
-                                      _ptr(scratch), _stream()), "gs_mind3d_l1")
+        self._mind_l1(self._MIND[3], x, y, out, cfg)
 
     def mind3d_l1_backward(self, x, y, grad_y, grad_scale=None, cfg=None):
         """grad_y = grad_scale * d mind3d_l1(x, y) / dy; grad_scale is a device scalar (gs_mind3d_l1_backward)"""
-        self._mind3d_check(x, y)
-        self._mind3d_check(grad_y)
-        if grad_y.shape != y.shape:
-            raise ValueError(f"mind3d_l1_backward: grad_y must have y's shape {tuple(y.shape)}, got {tuple(grad_y.shape)}")
-        if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1):
-            raise ValueError("mind3d_l1_backward: grad_scale must hold one fp32 value")
-        N, Cx, D, H, W = x.shape
-        scratch = torch.empty(self.lib.gs_mind3d_scratch_bytes(N, D, H, W, 1), dtype=torch.uint8, device=x.device)
-        L.check(self.lib.gs_mind3d_l1_backward(_ptr(x), _ptr(y), N, Cx, y.shape[1], D, H, W, *self._mind3d_args(cfg),
-                                               _ptr(grad_scale), _ptr(grad_y), _ptr(scratch), _stream()),
-                "gs_mind3d_l1_backward")
+        self._mind_l1_backward(self._MIND[3], x, y, grad_y, grad_scale, cfg)
 
     # ---- validation / test image metrics (valmetrics.hip) --------------------------------------------------
     VALMETRIC_COLUMNS = ("mae", "mse", "nmse", "psnr", "ssim", "nmi", "histogram_chi2")

@@ -185,36 +185,45 @@ def channel_embed(x, channels, c0):
     return out
 
 
-class _MINDL1(torch.autograd.Function):
-    """L1 distance of the MIND descriptors of two image batches, sum |f^X - f^Y| / (H W 81) (a sum over the batch): fused
-    forward (gs_mind_l1, no 81-channel map in memory) and hand-written backward (gs_mind_l1_backward); the distance is
-    symmetric, so the gradient w.r.t. the first image is the same kernel with the arguments swapped, and each side is
-    computed only when asked for."""
+def _mind_l1_function(prefix, what):
+    """The autograd function of one rank: ops.<prefix>_l1 forward, ops.<prefix>_l1_backward backward (looked up when called)"""
 
-    @staticmethod
-    def forward(ctx, X, Y):
-        ops = get_ops()
-        if not hasattr(ops, "mind_l1"):
-            raise NotImplementedError(f"the '{getattr(ops, 'name', type(ops).__name__)}' backend has no MIND structure loss "
-                                      "(mind_l1 / mind_l1_backward)")
-        X, Y = X.contiguous(), Y.contiguous()
-        out = torch.empty((), dtype=torch.float32, device=X.device)
-        ops.mind_l1(X, Y, out)
-        ctx.save_for_backward(X, Y)
-        return out
+    class _MINDL1(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, X, Y):
+            ops = get_ops()
+            if not hasattr(ops, f"{prefix}_l1"):
+                raise NotImplementedError(f"the '{getattr(ops, 'name', type(ops).__name__)}' backend has no {what} "
+                                          f"({prefix}_l1 / {prefix}_l1_backward)")
+            X, Y = X.contiguous(), Y.contiguous()
+            out = torch.empty((), dtype=torch.float32, device=X.device)
+            getattr(ops, f"{prefix}_l1")(X, Y, out)
+            ctx.save_for_backward(X, Y)
+            return out
 
-    @staticmethod
-    def backward(ctx, g):
-        X, Y = ctx.saved_tensors
-        g = g.contiguous().float()
-        gx = gy = None
-        if ctx.needs_input_grad[1]:
-            gy = torch.empty_like(Y)
-            get_ops().mind_l1_backward(X, Y, gy, grad_scale=g)
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(X)
-            get_ops().mind_l1_backward(Y, X, gx, grad_scale=g)
-        return gx, gy
+        @staticmethod
+        def backward(ctx, g):
+            X, Y = ctx.saved_tensors
+            g = g.contiguous().float()
+            gx = gy = None
+            if ctx.needs_input_grad[1]:
+                gy = torch.empty_like(Y)
+                getattr(get_ops(), f"{prefix}_l1_backward")(X, Y, gy, grad_scale=g)
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty_like(X)
+                getattr(get_ops(), f"{prefix}_l1_backward")(Y, X, gx, grad_scale=g)
+            return gx, gy
+
+    _MINDL1.__name__ = _MINDL1.__qualname__ = f"_{prefix.upper()}L1"
+    return _MINDL1
+
+
+# L1 distance of the MIND descriptors of two batches, sum |f^X - f^Y| / (H W 81) for images (gs_mind_l1, csrc/mind.hip) and
+# / (D H W 27) for volumes (gs_mind3d_l1, csrc/mind3d.hip), a sum over the batch: fused forward (no 81- / 27-channel map in
+# memory) and hand-written backward (gs_mind[3d]_l1_backward); the distance is symmetric, so the gradient w.r.t. the first
+# sample is the same kernel with the arguments swapped, and each side is computed only when asked for.
+_MINDL1 = _mind_l1_function("mind", "MIND structure loss")
+_MIND3DL1 = _mind_l1_function("mind3d", "volumetric MIND structure loss")
 
 
 def mind_structure_autograd(X, Y):
@@ -225,36 +234,6 @@ def mind_structure_autograd(X, Y):
         if t.dim() != 4:
             raise ValueError(f"the structure loss takes [N, C, H, W] images (volumes are not supported); got {tuple(t.shape)}")
     return _MINDL1.apply(X.float(), Y.float())
-
-
-class _MIND3DL1(torch.autograd.Function):
-    """_MINDL1 for volumes: sum |f^X - f^Y| / (D H W 27) over the 27-channel volumetric MIND descriptors (gs_mind3d_l1 /
-    gs_mind3d_l1_backward, csrc/mind3d.hip); each side's gradient is computed only when asked for."""
-
-    @staticmethod
-    def forward(ctx, X, Y):
-        ops = get_ops()
-        if not hasattr(ops, "mind3d_l1"):
-            raise NotImplementedError(f"the '{getattr(ops, 'name', type(ops).__name__)}' backend has no volumetric MIND "
-                                      "structure loss (mind3d_l1 / mind3d_l1_backward)")
-        X, Y = X.contiguous(), Y.contiguous()
-        out = torch.empty((), dtype=torch.float32, device=X.device)
-        ops.mind3d_l1(X, Y, out)
-        ctx.save_for_backward(X, Y)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        X, Y = ctx.saved_tensors
-        g = g.contiguous().float()
-        gx = gy = None
-        if ctx.needs_input_grad[1]:
-            gy = torch.empty_like(Y)
-            get_ops().mind3d_l1_backward(X, Y, gy, grad_scale=g)
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(X)
-            get_ops().mind3d_l1_backward(Y, X, gx, grad_scale=g)
-        return gx, gy
 
 
 def mind3d_structure_autograd(X, Y):

@@ -24,79 +24,72 @@ def _need(ops, method):
                                   f"(missing ops.{method})")
 
 
-class MINDDescriptor:
-    """image [N, C, H, W] -> features [N, 81, H, W]; channel i is the shift with row offset i % 9 - 4 and column offset
-    i // 9 - 4. No gradient flows through it: the differentiable path is StructureLoss."""
+class _Descriptor:
+    """One rank's descriptor: the subclass names its config, its tensor rank, its refusal and its backend method."""
+    _CONFIG = _DIM = _TAKES = _METHOD = None
 
     def __init__(self, **config):
-        unknown = set(config) - set(MIND_DESCRIPTOR_CONFIG)
+        unknown = set(config) - set(self._CONFIG)
         if unknown:
             raise TypeError(f"unknown MIND descriptor setting(s): {sorted(unknown)}")
-        self.config = dict(MIND_DESCRIPTOR_CONFIG, **config)
+        self.config = dict(self._CONFIG, **config)
 
-    def __call__(self, image):
-        if image.dim() != 4:
-            raise ValueError(f"the MIND descriptor takes [N, C, H, W] images (volumes are not supported); got {tuple(image.shape)}")
+    def __call__(self, sample):
+        if sample.dim() != self._DIM:
+            raise ValueError(f"{self._TAKES}; got {tuple(sample.shape)}")
         ops = get_ops()
-        _need(ops, "mind_descriptor")
+        _need(ops, self._METHOD)
         with torch.no_grad():
-            return ops.mind_descriptor(image.detach().contiguous().float(), cfg=self.config)
+            return getattr(ops, self._METHOD)(sample.detach().contiguous().float(), cfg=self.config)
 
 
-class StructureLoss:
-    """lambda_structure * sum_{n,a,p} |f_a(input) - f_a(fake)| / (H W 81). As in the reference this is a SUM over the
-    batch, not a mean: the loss grows with the batch size."""
+class _Structure:
+    """One rank's loss: the subclass names its backend methods and its autograd function."""
+    _PREFIX = None
+    _autograd = None
 
     def __init__(self, lambda_structure):
         self.lambda_structure = lambda_structure
 
     def terms(self, input_, fake):
         """[(weight, 0-d loss)] whose weighted sum is the loss"""
-        _need(get_ops(), "mind_l1")
-        _need(get_ops(), "mind_l1_backward")
-        return [(self.lambda_structure, mind_structure_autograd(input_, fake))]
+        _need(get_ops(), f"{self._PREFIX}_l1")
+        _need(get_ops(), f"{self._PREFIX}_l1_backward")
+        return [(self.lambda_structure, self._autograd(input_, fake))]
 
     def __call__(self, input_, fake):
         (w, x), = self.terms(input_, fake)
         return scalar_affine([x], [[w]])[0]
 
 
-class MINDDescriptor3D:
+class MINDDescriptor(_Descriptor):
+    """image [N, C, H, W] -> features [N, 81, H, W]; channel i is the shift with row offset i % 9 - 4 and column offset
+    i // 9 - 4. No gradient flows through it: the differentiable path is StructureLoss."""
+    _CONFIG, _DIM, _METHOD = MIND_DESCRIPTOR_CONFIG, 4, "mind_descriptor"
+    _TAKES = "the MIND descriptor takes [N, C, H, W] images (volumes are not supported)"
+
+
+class StructureLoss(_Structure):
+    """lambda_structure * sum_{n,a,p} |f_a(input) - f_a(fake)| / (H W 81). As in the reference this is a SUM over the
+    batch, not a mean: the loss grows with the batch size."""
+    _PREFIX, _autograd = "mind", staticmethod(mind_structure_autograd)
+
+
+class MINDDescriptor3D(_Descriptor):
     """volume [N, C, D, H, W] -> features [N, 27, D, H, W]; channel i is the shift with depth offset i % 3 - 1, row offset
     (i // 3) % 3 - 1 and column offset i // 9 - 1. No gradient flows through it: the differentiable path is
     StructureLoss3D."""
-
-    def __init__(self, **config):
-        unknown = set(config) - set(MIND3D_DESCRIPTOR_CONFIG)
-        if unknown:
-            raise TypeError(f"unknown MIND descriptor setting(s): {sorted(unknown)}")
-        self.config = dict(MIND3D_DESCRIPTOR_CONFIG, **config)
-
-    def __call__(self, volume):
-        if volume.dim() != 5:
-            raise ValueError(f"the volumetric MIND descriptor takes [N, C, D, H, W] volumes; got {tuple(volume.shape)}")
-        ops = get_ops()
-        _need(ops, "mind3d_descriptor")
-        with torch.no_grad():
-            return ops.mind3d_descriptor(volume.detach().contiguous().float(), cfg=self.config)
+    _CONFIG, _DIM, _METHOD = MIND3D_DESCRIPTOR_CONFIG, 5, "mind3d_descriptor"
+    _TAKES = "the volumetric MIND descriptor takes [N, C, D, H, W] volumes"
 
 
-class StructureLoss3D:
+class StructureLoss3D(_Structure):
     """lambda_structure * sum_{n,a,p} |f_a(input) - f_a(fake)| / (D H W 27): StructureLoss for volumes, a SUM over the batch
     as well."""
-
-    def __init__(self, lambda_structure):
-        self.lambda_structure = lambda_structure
+    _PREFIX, _autograd = "mind3d", staticmethod(mind3d_structure_autograd)
 
     def terms(self, input_, fake):
-        """[(weight, 0-d loss)] whose weighted sum is the loss"""
-        for t in (input_, fake):
+        for t in (input_, fake):           # refused before the backend is asked for its kernels
             if t.dim() != 5:
                 raise ValueError(f"the volumetric structure loss takes [N, C, D, H, W] volumes; got {tuple(t.shape)}")
-        _need(get_ops(), "mind3d_l1")
-        _need(get_ops(), "mind3d_l1_backward")
-        return [(self.lambda_structure, mind3d_structure_autograd(input_, fake))]
-
-    def __call__(self, input_, fake):
-        (w, x), = self.terms(input_, fake)
-        return scalar_affine([x], [[w]])[0]
+        return super().terms(input_, fake)
