@@ -103,6 +103,8 @@ template <int N>
 __device__ __forceinline__ void gs_lgkm_wait64(uint2& a, uint2& b, uint2& c, uint2& d, uint2& e, uint2& f) {
   asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "i"(N) : "memory");
 }
+// per-fragment fence behind gs_lgkm_wait_only<N>() (any number of fragments, see reg_fence(bf16x8&) above)
+__device__ __forceinline__ void reg_fence(uint2& lo, uint2& hi) { asm volatile("" : "+v"(lo), "+v"(hi)); }
 // compile-time loop: f(std::integral_constant<int, I>{}) for I in [B, E)
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {

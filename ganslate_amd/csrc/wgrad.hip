@@ -10,6 +10,9 @@
 // memory (NHWC), so MFMA fragments (8 consecutive k per lane) are read with the LDS transpose read
 // ds_read_b64_tr_b16 from [64 pixels][128 channels] tiles staged by LDS-DMA. The pixel range of every image
 // is split over workgroups (split-K); partial tiles are accumulated with fp32 atomics.
+// The K loop shows the compiler no LDS access between issue(ks + 2) and the end of the iteration (inline-asm transpose reads,
+// counted lgkmcnt waits): behind an LDS-DMA, hipcc puts s_waitcnt vmcnt(0) in front of the first LDS read it can see, which
+// drained the stage issued a few instructions earlier and left the 3-stage ring one stage deep.
 #include "internal.hpp"
 #include <cstdlib>
 
@@ -57,7 +60,12 @@ __global__ __launch_bounds__(WP * WQ * 64) void wgrad_kernel(const WGradK p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
 
-  int b = blockIdx.x;
+  // Workgroups are dealt to the 8 XCDs round-robin (blockIdx b and b + 8 share one: observed, used for speed only). Renumber
+  // them so that consecutive numbers — the column and row tiles of one pixel split, which stage the same dense rows and
+  // overlapping gathered rows — run on one XCD at the same time and meet in its L2 instead of each fetching over the fabric.
+  // A bijection of [0, gridDim.x): which workgroup computes a tile changes, what it computes and where it stores does not.
+  const int nblk = (int)gridDim.x, xper = nblk >> 3, xrem = nblk & 7, xcd = (int)blockIdx.x & 7;
+  int b = (xcd < xrem ? xcd * (xper + 1) : xrem * (xper + 1) + (xcd - xrem) * xper) + ((int)blockIdx.x >> 3);
   const int tq = b % p.tiles_q;
   b /= p.tiles_q;
   const int tp = b % p.tiles_p;
@@ -93,8 +101,13 @@ __global__ __launch_bounds__(WP * WQ * 64) void wgrad_kernel(const WGradK p) {
   const int g_dh = (int)(signed char)(tpv & 0xff), g_dw = (int)(signed char)((tpv >> 8) & 0xff), g_dd = tpv >> 16;
   static_assert((GRI * NW) % 16 == 0, "row step must keep the swizzle invariant");
 
-  // pixel coordinates of this lane's gathered rows, advanced by BK pixels per K-step (no divisions in the loop)
-  int gn[NGI], gz[NGI], gi[NGI], gj[NGI];
+  // Pixel coordinates of this lane's gathered rows, advanced by BK pixels per K-step. The staging arithmetic is issue work on
+  // the vector ALUs of all 16 waves, next to the MFMAs: no divisions, no data-dependent loops and no full 32-bit multiplies
+  // but the last in the K loop. BK pixels are (s_n images, s_z planes, s_i rows, s_j columns) — the coordinates advance by these
+  // with one carry per level; the image's base pixel gnb = n * g_img advances with n; the dense row's byte offset advances
+  // by BK * a_cs elements; coordinates and extents are below 2^24 (launcher), so their products are 24-bit multiplies.
+  int gz[NGI], gi[NGI], gj[NGI];
+  unsigned gnb[NGI];
 #pragma unroll
   for (int i = 0; i < NGI; ++i) {
     const int m = k0 + g_row0 + i * GRI * NW;
@@ -102,18 +115,29 @@ __global__ __launch_bounds__(WP * WQ * 64) void wgrad_kernel(const WGradK p) {
     const int rem = m - nz * HW;
     gi[i] = div_small(rem, d.Wa, p.rcp_wa);
     gj[i] = rem - gi[i] * d.Wa;
-    gn[i] = VOL ? div_small(nz, d.Da, p.rcp_da) : nz;
-    gz[i] = VOL ? nz - gn[i] * d.Da : 0;
+    const int n = VOL ? div_small(nz, d.Da, p.rcp_da) : nz;
+    gz[i] = VOL ? nz - n * d.Da : 0;
+    gnb[i] = (unsigned)n * g_img;
   }
+  const int s_nz = div_small(BK, HW, p.rcp_hw), s_rem = BK - s_nz * HW;            // (uniform)
+  const int s_i = div_small(s_rem, d.Wa, p.rcp_wa), s_j = s_rem - s_i * d.Wa;
+  const int s_n = VOL ? div_small(s_nz, d.Da, p.rcp_da) : s_nz, s_z = VOL ? s_nz - s_n * d.Da : 0;
+  const unsigned s_nb = (unsigned)s_n * g_img;
+  unsigned a_off[NAI];
+#pragma unroll
+  for (int i = 0; i < NAI; ++i)
+    a_off[i] = ((unsigned)(k0 + a_row0 + i * ARI * NW) * (unsigned)d.a_cs + (unsigned)a_pch) * 2u;
+  const unsigned a_step = (unsigned)BK * (unsigned)d.a_cs * 2u;
 
-  auto issue = [&](int ks, int buf) {      // always called with ks increasing by 1
+  auto issue = [&](int ks, int buf) {      // always called with ks increasing by 1, from 0
     char* sb = smem + buf * STAGE;
     const int mb = k0 + ks * BK;
 #pragma unroll
     for (int i = 0; i < NAI; ++i) {
       const int R = a_row0 + i * ARI * NW;
       const int m = mb + R;
-      unsigned off = ((unsigned)m * (unsigned)d.a_cs + (unsigned)a_pch) * 2u;
+      unsigned off = a_off[i];
+      a_off[i] += a_step;
       asm volatile("" : "+v"(off));
       const bool real = A_INSTR % NW == 0 || wave + i * NW < A_INSTR;   // wave-uniform
       const char* src = (real && m < k1 && a_cv) ? a_n + off : p.zero;
@@ -124,20 +148,29 @@ __global__ __launch_bounds__(WP * WQ * 64) void wgrad_kernel(const WGradK p) {
       const int R = g_row0 + i * GRI * NW;
       const int m = mb + R;
       bool ok = g_tv && m < k1;
-      const int nn = gn[i], zz = gz[i], ii = gi[i], jj = gj[i];
-      gj[i] += BK;
-      while (gj[i] >= d.Wa) { gj[i] -= d.Wa; ++gi[i]; }
-      int iz = 0;
+      const int zz = gz[i], ii = gi[i], jj = gj[i];
+      const unsigned nb = gnb[i];
+      gj[i] += s_j;
+      int c = gj[i] >= d.Wa;
+      gj[i] -= c ? d.Wa : 0;
+      gi[i] += s_i + c;
+      c = gi[i] >= d.Ha;
+      gi[i] -= c ? d.Ha : 0;
+      unsigned lin;
       if constexpr (VOL) {
-        while (gi[i] >= d.Ha) { gi[i] -= d.Ha; ++gz[i]; }
-        while (gz[i] >= d.Da) { gz[i] -= d.Da; ++gn[i]; }
-        iz = border_index(zz * d.si + g_dd, d.Dg, d.border, ok);
+        gz[i] += s_z + c;
+        c = gz[i] >= d.Da;
+        gz[i] -= c ? d.Da : 0;
+        const int iz = border_index((int)__umul24(zz, d.si) + g_dd, d.Dg, d.border, ok);
+        const int ih = border_index((int)__umul24(ii, d.si) + g_dh, d.Hg, d.border, ok);
+        lin = (unsigned)(((int)__umul24(iz, d.Hg) + ih) * d.Wg);
       } else {
-        while (gi[i] >= d.Ha) { gi[i] -= d.Ha; ++gn[i]; }
+        const int ih = border_index((int)__umul24(ii, d.si) + g_dh, d.Hg, d.border, ok);
+        lin = __umul24(ih, d.Wg);
       }
-      const int ih = border_index(ii * d.si + g_dh, d.Hg, d.border, ok);
-      const int iw = border_index(jj * d.si + g_dw, d.Wg, d.border, ok);
-      unsigned off = (((unsigned)nn * g_img + (unsigned)((iz * d.Hg + ih) * d.Wg + iw)) * (unsigned)d.g_cs + (unsigned)(g_q8 * 8)) * 2u;
+      gnb[i] += s_nb + (c ? g_img : 0u);
+      const int iw = border_index((int)__umul24(jj, d.si) + g_dw, d.Wg, d.border, ok);
+      unsigned off = ((nb + lin + (unsigned)iw) * (unsigned)d.g_cs + (unsigned)(g_q8 * 8)) * 2u;
       asm volatile("" : "+v"(off));
       const char* src = ok ? g_n + off : p.zero;
       glds16(src, sb + AT + (wave + i * NW) * 1024);
@@ -183,31 +216,48 @@ __global__ __launch_bounds__(WP * WQ * 64) void wgrad_kernel(const WGradK p) {
     if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (ks + 2 < nk) issue(ks + 2, nxt2);
-    const char* ab = smem + cur * STAGE;
-    const char* gb = ab + AT;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      uint2 ah[TI][2], gh[TJ][2];   // two 64-bit transpose reads = one 8-element MFMA fragment
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-          ah[i][h] = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) s16x4*)GS_LDS(ab + aoff[i] + (kk * 32 + h * 4) * ARB)));
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-          gh[j][h] = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) s16x4*)GS_LDS(gb + goff[j] + (kk * 32 + h * 4) * GRB)));
+    // ---- fragment reads + MFMAs of the two 32-pixel halves: inline-asm transpose reads with counted lgkmcnt waits -----------
+    // Fragment order of a half: a[0], g[0] .. g[TJ-1], a[1] .. a[TI-1] — the order in which the MFMAs (i outer, j inner, as
+    // ever) first need them; one fragment = two 64-bit transpose reads (pixel rows +0..3 and +4..7 of its 8-pixel blocks).
+    // Half 0 is read in one go; every wait for one of its fragments is followed by the read of the same fragment of half 1
+    // (two after the first wait), so the LDS pipe stays fed under half 0's MFMAs and at most 12 reads are in flight (the
+    // counter has 4 bits). LDS returns in order: a wait counts the reads issued after the fragment it needs.
+    constexpr int NF = TI + TJ;
+    const unsigned ab = lds_addr(smem) + (unsigned)(cur * STAGE), gb = ab + AT;
+    uint2 fr[2][NF][2];
+    auto rd = [&](auto kf) {
+      constexpr int kk = decltype(kf)::value / NF, f = decltype(kf)::value % NF;
+      if constexpr (f == 0 || f > TJ) {
+        constexpr int i = f == 0 ? 0 : f - TJ;
+        lds_read64_tr<kk * 32 * ARB>(fr[kk][f][0], ab + (unsigned)aoff[i]);
+        lds_read64_tr<(kk * 32 + 4) * ARB>(fr[kk][f][1], ab + (unsigned)aoff[i]);
+      } else {
+        constexpr int j = f - 1;
+        lds_read64_tr<kk * 32 * GRB>(fr[kk][f][0], gb + (unsigned)goff[j]);
+        lds_read64_tr<(kk * 32 + 4) * GRB>(fr[kk][f][1], gb + (unsigned)goff[j]);
       }
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              __builtin_bit_cast(bf16x8, uint4{ah[i][0].x, ah[i][0].y, ah[i][1].x, ah[i][1].y}),
-              __builtin_bit_cast(bf16x8, uint4{gh[j][0].x, gh[j][0].y, gh[j][1].x, gh[j][1].y}), acc[i][j], 0, 0, 0);
-    }
+    };
+    if (ks + 2 < nk) issue(ks + 2, nxt2);
+    static_for<0, NF>(rd);
+    static_for<0, 2 * TI * TJ>([&](auto mm) {
+      constexpr int kk = decltype(mm)::value / (TI * TJ), i = decltype(mm)::value % (TI * TJ) / TJ, j = decltype(mm)::value % TJ;
+      constexpr int F = i == 0 ? j + 1 : (j == 0 ? TJ + i : 0);   // the last fragment in read order this MFMA is the first to need
+      if constexpr (F > 0) {
+        constexpr int ahead = kk == 1 ? 0 : (F == 1 ? 0 : F);     // fragments of half 1 already issued
+        __builtin_amdgcn_sched_barrier(0);                        // (the MFMAs above stay above this wait)
+        gs_lgkm_wait_only<2 * (NF - 1 - F) + 2 * ahead>();
+        if constexpr (F == 1) reg_fence(fr[kk][0][0], fr[kk][0][1]);
+        reg_fence(fr[kk][F][0], fr[kk][F][1]);
+        if constexpr (kk == 0) {
+          if constexpr (F == 1) rd(std::integral_constant<int, NF>{});
+          rd(std::integral_constant<int, NF + F>{});
+        }
+      }
+      constexpr int fa = i == 0 ? 0 : TJ + i, fg = 1 + j;
+      acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          __builtin_bit_cast(bf16x8, uint4{fr[kk][fa][0].x, fr[kk][fa][0].y, fr[kk][fa][1].x, fr[kk][fa][1].y}),
+          __builtin_bit_cast(bf16x8, uint4{fr[kk][fg][0].x, fr[kk][fg][0].y, fr[kk][fg][1].x, fr[kk][fg][1].y}), acc[i][j], 0, 0, 0);
+    });
     cur = cur == 2 ? 0 : cur + 1;
     nxt2 = nxt2 == 2 ? 0 : nxt2 + 1;
   }
@@ -341,6 +391,8 @@ int launch_wgrad_impl(WGradK& k, const gs_wgrad_desc* d, hipStream_t st, int pla
   GS_REQUIRE(M * k.nets < (1 << 24) && M * k.nets * d->a_cs < (1LL << 31) &&
                  (long long)d->N * d->Dg * d->Hg * d->Wg * d->g_cs < (1LL << 31),
              "gs_wgrad: tensor too large for 32-bit offsets");
+  GS_REQUIRE(d->si >= 1 && d->si < (1 << 24) && d->Dg < (1 << 24) && d->Hg < (1 << 24) && d->Wg < (1 << 24),
+             "gs_wgrad: stride or gathered extent outside the 24-bit coordinate arithmetic of the kernel");
   const long long tiles = (long long)k.tiles_p * k.tiles_q * k.nets;
   const long long max_splits = (M + 1023) / 1024 > 0 ? (M + 1023) / 1024 : 1;
   long long splits = 1;
