@@ -150,10 +150,10 @@ class Piresnet3D(Vnet3D):
         n, mr0, y, mr = rec
         dy = torch.empty_like(y)
         if sign > 0:
-            ops.inorm_act_backward(g_out, None, y, mr, dy, None, act="relu", bias_grad=self._bias_slice(node, want_w))
+            ops.inorm_act_backward(g_out, None, y, mr, dy, None, act="relu", bias_grad=self._bias_slice(s, node, want_w))
         else:
             ops.pnorm_backward(g_out, y, mr, dy, C=h, slope=self._zero_slope(h), res_mode=3,
-                               bias_grad=self._bias_slice(node, want_w))
+                               bias_grad=self._bias_slice(s, node, want_w))
         if want_w:
             self._wgrad(s, node, n, dy)
         lw, sp = s.lows[node], self.nodes[node].spec
@@ -164,19 +164,21 @@ class Piresnet3D(Vnet3D):
         ops.add_views(g_into, dx, h, accumulate=True)
 
     # ---- forward ----------------------------------------------------------------------------------------------------
-    def _forward(self, x, save, stop=None):
+    def _forward(self, x, save, stop=None, tw=None, inverse=False):
         assert stop is None, "feature taps are not implemented for Piresnet3D"
+        assert tw is None, "twin passes are not implemented for Piresnet3D"
         ops, c = self.ops, self.c
         N, sizes = x.shape[0], tuple(x.shape[2:])
         half = tuple(v // 2 for v in sizes)
         s = _Saved()
-        inv = s.inverse = bool(getattr(self, "_next_inverse", False))
+        s.tw, s.stop, s.need = None, None, None
+        inv = s.inverse = bool(inverse)
         s.recompute = bool(save and self.use_memory_saving)
         d1, d2, u1, u2 = self.ends["ba" if inv else "ab"]
         s.x_img, s.N, s.sizes = x, N, sizes
         s.lows, s.pk = self._lowered(*sizes), self._get_packs(*sizes)
         a0 = self._new(N, sizes, self.nodes[d1].spec.cin_p)
-        ops.image_to_act(x, a0)
+        self._images_to_act((x,), a0)
         s.a0 = a0
         s.y1, s.mr1 = self._conv(s, d1, a0)
         s.t1 = self._new(N, sizes, c)
@@ -207,8 +209,9 @@ class Piresnet3D(Vnet3D):
         return out, (s if save else None)
 
     # ---- backward ------------------------------------------------------------------------------------------------------
-    def _backward(self, s, g_img, need_input_grad, want_w, start=None, inj_x=None, inj_y=None):
+    def _backward(self, s, g_img, need_input_grad, want_w, start=None, inj_x=None, inj_y=None, tw=None):
         assert start is None and not inj_x and not inj_y, "feature taps are not implemented for Piresnet3D"
+        assert tw is None, "twin passes are not implemented for Piresnet3D"
         ops, c, N = self.ops, self.c, s.N
         if self.master.grad is None:
             self.master.grad = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
@@ -218,7 +221,7 @@ class Piresnet3D(Vnet3D):
         dpack = lambda i: s.pk["dpack"][s.pk["d_off"][i]:]
         # upconv: tanh, conv5 (replicate-padded: its data gradient lives on the padded domain and is folded by the norm)
         gz = torch.empty_like(s.z)
-        ops.act_to_image_backward(g_img.contiguous().float(), s.out_img, gz, act="tanh")
+        self._image_grad_to_act(g_img, (s.x_img,), s.out_img, gz)
         sp = self.nodes[u2].spec
         if want_w:
             self._wgrad(s, u2, s.t3, gz)
@@ -228,7 +231,7 @@ class Piresnet3D(Vnet3D):
         ops.gconv_classes(lw.dgrad, gz, dpack(u2), None, g_pad)
         dy3 = torch.empty_like(s.y3)
         ops.inorm_act_backward(g_pad, None, s.y3, s.mr3, dy3, None, fold=lw.dgrad_fold, fold_mode=sp.pad_mode, act="relu",
-                               bias_grad=self._bias_slice(u1, want_w))
+                               bias_grad=self._bias_slice(s, u1, want_w))
         if want_w:
             self._wgrad(s, u1, s.Xn, dy3)
         gX = self._dgrad(s, u1, dy3)                       # w.r.t. the core output [.., 2c]
@@ -261,12 +264,12 @@ class Piresnet3D(Vnet3D):
         ops.add_views(gD0, gb, c, dst_co=c, src_co=0, accumulate=False)
         # downconv
         dy2 = torch.empty_like(s.y2)
-        ops.inorm_act_backward(gD0, None, s.y2, s.mr2, dy2, None, act="relu", bias_grad=self._bias_slice(d2, want_w))
+        ops.inorm_act_backward(gD0, None, s.y2, s.mr2, dy2, None, act="relu", bias_grad=self._bias_slice(s, d2, want_w))
         if want_w:
             self._wgrad(s, d2, s.t1, dy2)
         gt1 = self._dgrad(s, d2, dy2)
         dy1 = torch.empty_like(s.y1)
-        ops.inorm_act_backward(gt1, None, s.y1, s.mr1, dy1, None, act="relu", bias_grad=self._bias_slice(d1, want_w))
+        ops.inorm_act_backward(gt1, None, s.y1, s.mr1, dy1, None, act="relu", bias_grad=self._bias_slice(s, d1, want_w))
         if want_w:
             self._wgrad(s, d1, s.a0, dy1)
         if not need_input_grad:
@@ -274,6 +277,4 @@ class Piresnet3D(Vnet3D):
         lw, sp = s.lows[d1], self.nodes[d1].spec
         gx_pad = self._new(N, lw.dgrad_dims, sp.cin_p)
         ops.gconv_classes(lw.dgrad, dy1, dpack(d1), None, gx_pad)
-        g_in = torch.empty_like(s.x_img)
-        ops.image_to_act_backward(gx_pad, g_in, fold=lw.dgrad_fold, fold_mode=sp.pad_mode)
-        return g_in
+        return self._act_grad_to_images(gx_pad, (s.x_img,), s.need, lw.dgrad_fold, sp.pad_mode)[0]

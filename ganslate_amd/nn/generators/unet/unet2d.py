@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import torch
 
 from .... import configs
-from ...native.net import ChannelSources, NativeNet, Node
+from ...native.net import NativeNet, Node
 from ...native.spec import ConvSpec, lower
 from ...utils import is_bias_before_norm, require_instance_norm
 
@@ -121,12 +121,14 @@ class Unet2D(NativeNet):
         return torch.empty(N, *sizes, C, dtype=self.ops.act_dtype, device=self.device)
 
     # ---- forward -----------------------------------------------------------------------------------------------------
-    def _forward(self, x, save):
+    def _forward(self, x, save, stop=None, tw=None, inverse=False):
+        """x: one batch — a tensor, or the channel windows of NativeNet.forward_sources (side by side: no cat, no slice)"""
+        assert stop is None and tw is None and not inverse, "Unet2D runs whole single-network passes in its one direction"
         ops, D, c = self.ops, self.D, self.c
         N, sizes = x.shape[0], tuple(x.shape[2:])
         lows, pk = self._lowered(*sizes), self._get_packs(*sizes)
         s = _Saved()
-        s.x_img, s.N, s.sizes, s.lows = x, N, sizes, lows
+        s.x_img, s.N, s.sizes, s.lows, s.need = x, N, sizes, lows, None
         # nn.Dropout draws a new mask per forward (unet2d.py:146-147). The 64-bit mask seed lives in device memory
         # (gs_norm_ex_desc.seed_dev): a captured step replays these launches with identical arguments, so the recipe
         # uploads a fresh seed before every replay (prepare_host_state); launch by launch the pass draws it itself.
@@ -137,10 +139,7 @@ class Unet2D(NativeNet):
                 self.prepare_host_state()
             s.seed_dev = self._seed_dev
         a0 = self._new(N, sizes, self.nodes[0].spec.cin_p)
-        if isinstance(x, ChannelSources):      # channel windows side by side (NativeNet.forward_sources): no cat, no slice
-            ops.image_cat_to_act(list(x), a0)
-        else:
-            ops.image_to_act(x, a0)
+        self._images_to_act((x,), a0)
         s.L = {0: a0}          # L[k]: LeakyReLU(h_k), the input of down_{k+1}
         s.cat, s.yd, s.mrd, s.yu, s.mru = {}, {}, {}, {}, {}
         for k in range(1, D + 1):
@@ -202,7 +201,8 @@ class Unet2D(NativeNet):
         self.ops.gconv_classes(lw.dgrad, dy, dpack, None, gx)
         return gx
 
-    def _backward(self, s, g_img, need_input_grad, want_w):
+    def _backward(self, s, g_img, need_input_grad, want_w, start=None, inj_x=None, inj_y=None, tw=None):
+        assert start is None and not inj_x and not inj_y and tw is None, "Unet2D: neither feature taps nor twin passes"
         ops, D, c, N = self.ops, self.D, self.c, s.N
         lows, pk = s.lows, self._get_packs(*s.sizes)
         if self.master.grad is None:
@@ -211,7 +211,7 @@ class Unet2D(NativeNet):
         final_pass = want_w and self._dist is not None and self._fw_pending == 0 and not self.external_reduce
         bias_slice = lambda i: grad[self.b_off[i]:self.b_off[i] + self.nodes[i].spec.cout_p] if want_w else None
         dy = torch.empty_like(s.y1)
-        ops.act_to_image_backward(g_img.contiguous().float(), s.out_img, dy, act="tanh")
+        self._image_grad_to_act(g_img, (s.x_img,), s.out_img, dy)
         gcat = {}
         # a layer whose weight gradient launch also updates its weights (gs_wgrad_adam) must have launched its data gradient:
         # parameter gradients after the data gradient then
@@ -261,8 +261,4 @@ class Unet2D(NativeNet):
                 self._early_step_at(i)
         if not need_input_grad:
             return None
-        if isinstance(s.x_img, ChannelSources):
-            return s.x_img.write_grads(ops, gL, getattr(self, "_cat_need", None) or (True,) * len(s.x_img))
-        g_in = torch.empty_like(s.x_img)
-        ops.image_to_act_backward(gL, g_in, fold=0)
-        return g_in
+        return self._act_grad_to_images(gL, (s.x_img,), s.need)[0]

@@ -77,12 +77,11 @@ class _Block:
 
 class Vnet3D(NativeNet):
     dims = 3
-    twin_extras_ok = True        # TwinNet: the PReLU slopes (extras) are handled per network (see _tw below)
+    twin_extras_ok = True        # TwinNet: the PReLU slopes (extras) are handled per network. In a twin pass (s.tw: the second
+                                 # network) every per-network tensor (master, packs, gradient buffer, slopes) is a Twin and the
+                                 # batch holds both networks' images, first this network's (nn/native/twin.py)
     twin_default = False         # ... but recipes pair V-Nets only on request (GS_TWIN=all): measured slower on the brats recipe
     is_separable = False         # (class default: executors that borrow the conv helpers below — Piresnet3D — are dense)
-    _tw = None                   # the second network of a twin pass while that pass is being launched: every per-network
-                                 # tensor (master, packs, gradient buffer, slopes) is then a Twin and the batch holds both
-                                 # networks' images, first this network's (nn/native/twin.py)
 
     def __init__(self, in_channels, out_channels, norm_type, first_layer_channels=16, down_blocks=(1, 2, 3, 2),
                  up_blocks=(2, 2, 1, 1), use_memory_saving=True, use_inverse=True, is_separable=False, attention=()):
@@ -268,7 +267,7 @@ class Vnet3D(NativeNet):
 
     def _conv1(self, s, i, x, in_co=0, stats=True, out=None):
         ops, sp, lw, N = self.ops, self.nodes[i].spec, s.lows[i], s.N
-        tw = self._tw
+        tw = s.tw
         m = self.master.detach() if tw is None else Twin(self.master.detach(), tw.master.detach())
         bias = m[self.b_off[i]:self.b_off[i] + sp.cout_p]
         fpack = (s.pk["fpack"] if tw is None else Twin(s.pk["fpack"], s.pk_tw["fpack"]))[s.pk["f_off"][i]:]
@@ -288,12 +287,12 @@ class Vnet3D(NativeNet):
         ops.inorm_finalize(part, N, slots * lw.out_images, sp.cout_p, lw.out_pixels, mr)
         return y, mr
 
-    def _slope(self, name, grad=False):
+    def _slope(self, s, name, grad=False):
         t = self.extra(name, grad=grad)
-        return t if self._tw is None else Twin(t, self._tw.extra(name, grad=grad))
+        return t if s.tw is None else Twin(t, s.tw.extra(name, grad=grad))
 
-    def _grad_buf(self):
-        return self.master.grad if self._tw is None else Twin(self.master.grad, self._tw.master.grad)
+    def _grad_buf(self, s):
+        return self.master.grad if s.tw is None else Twin(self.master.grad, s.tw.master.grad)
 
     # ---- forward -----------------------------------------------------------------------------------------------------
     def _couplings_forward(self, s, blk, X):
@@ -318,9 +317,9 @@ class Vnet3D(NativeNet):
         nf, sf, ng, sg = cp
         Y = self._new(s.N, X.shape[1:-1], blk.C)
         ya, mra = self._conv(s, nf, X, in_co=h)                             # F reads x2
-        ops.pnorm_forward(ya, mra, Y, C=h, slope=self._slope(sf), res=X, res_mode=2, res_co=0, out_co=0)
+        ops.pnorm_forward(ya, mra, Y, C=h, slope=self._slope(s, sf), res=X, res_mode=2, res_co=0, out_co=0)
         yb, mrb = self._conv(s, ng, Y, in_co=0)                             # G reads y1
-        ops.pnorm_forward(yb, mrb, Y, C=h, slope=self._slope(sg), res=X, res_mode=2, res_co=h, out_co=h)
+        ops.pnorm_forward(yb, mrb, Y, C=h, slope=self._slope(s, sg), res=X, res_mode=2, res_co=h, out_co=h)
         return Y, ya, mra, yb, mrb
 
     def _coupling_inv_one(self, s, blk, cp, Y):
@@ -329,9 +328,9 @@ class Vnet3D(NativeNet):
         nf, sf, ng, sg = cp
         X = self._new(s.N, Y.shape[1:-1], blk.C)
         yb, mrb = self._conv(s, ng, Y, in_co=0)                             # G reads y1
-        ops.pnorm_forward(yb, mrb, X, C=h, slope=self._slope(sg), res=Y, res_mode=3, res_co=h, out_co=h)
+        ops.pnorm_forward(yb, mrb, X, C=h, slope=self._slope(s, sg), res=Y, res_mode=3, res_co=h, out_co=h)
         ya, mra = self._conv(s, nf, X, in_co=h)                             # F reads x2
-        ops.pnorm_forward(ya, mra, X, C=h, slope=self._slope(sf), res=Y, res_mode=3, res_co=0, out_co=0)
+        ops.pnorm_forward(ya, mra, X, C=h, slope=self._slope(s, sf), res=Y, res_mode=3, res_co=0, out_co=0)
         return X, ya, mra, yb, mrb
 
     def _couplings_inverse(self, s, blk, Y):
@@ -349,37 +348,25 @@ class Vnet3D(NativeNet):
         (vnet3d.py:107-150); needs use_inverse=True"""
         if inverse and not self.use_inverse:
             raise ValueError("Trying to perform inverse forward while `use_inverse` flag is turned off.")
-        self._next_inverse = bool(inverse)
-        try:
-            return super().forward(x)
-        finally:
-            self._next_inverse = False
+        return self._whole_pass(x, inverse=bool(inverse))
 
     __call__ = forward
 
-    def _forward(self, x, save, stop=None, tw=None):
+    def _forward(self, x, save, stop=None, tw=None, inverse=False):
         """tw: a second Vnet3D of identical architecture (TwinNet) — x is then ((this network's batches), (tw's batches)) and
         the pass runs as ONE batch, this network's images first. A tuple of batches without tw (forward_parts): one pass over
         all of them. stop = k: the encoder-only pass of CUT up to tap level k (see encoder_tap) — InputBlock and DownBlocks
         0 .. k-1 in the A -> B direction, no attention, no up path, no OutBlock; returns (None, saved)"""
         assert stop is None or tw is None, "twin passes run whole networks"
-        self._tw = tw
-        try:
-            return self._forward_impl(x, save, stop)
-        finally:
-            self._tw = None
-
-    def _forward_impl(self, x, save, stop=None):
         ops, c, L = self.ops, self.c, self.L
-        tw = self._tw
         xs = (tuple(x[0]) + tuple(x[1])) if tw is not None else (tuple(x) if isinstance(x, (tuple, list)) else (x,))
         N, sizes = sum(t.shape[0] for t in xs), tuple(xs[0].shape[2:])
         s = _Saved()
-        s.tw = tw
+        s.tw, s.need = tw, None       # (need: which input tensors want a gradient — the node that records the pass says)
         s.mid, s.dmid = {}, {}        # separable convs: output of the (1,k,k) launch by conv index / its gradient
-        assert tw is None or not getattr(self, "_next_inverse", False), "twin passes run A -> B"
+        assert tw is None or not inverse, "twin passes run A -> B"
         # (the reference's encoder walk calls the modules without `inverse`: an encoder pass runs A -> B, cut.py:297-312)
-        inv = s.inverse = bool(getattr(self, "_next_inverse", False)) and stop is None
+        inv = s.inverse = bool(inverse) and stop is None
         s.stop = stop
         s.recompute = bool(save and self.use_memory_saving)
         n_in, s_in = (self.n_in_ba, self.s_in_ba) if inv else (self.n_in, self.s_in)
@@ -387,21 +374,17 @@ class Vnet3D(NativeNet):
         bconv = (lambda b: (b.conv_ba, b.conv_slope_ba)) if inv else (lambda b: (b.conv, b.conv_slope))
         core = self._couplings_inverse if inv else self._couplings_forward
         s.parts = not torch.is_tensor(x)               # several batches: gradients go in and come back per batch
-        s.x_img, s.N, s.sizes = (x if torch.is_tensor(x) else xs), N, sizes
+        s.xs, s.N, s.sizes = xs, N, sizes
         s.lows, s.pk = self._lowered(*sizes), self._get_packs(*sizes)
         s.pk_tw = tw._get_packs(*sizes) if tw is not None else None
         lv = lambda k: tuple(v >> k for v in sizes)
         a0 = self._new(N, sizes, self.nodes[0].spec.cin_p)
-        n0 = 0
-        for xh in xs:
-            ops.image_to_act(xh, a0[n0:n0 + xh.shape[0]])
-            n0 += xh.shape[0]
-        s.xs = xs
+        self._images_to_act(xs, a0)
         s.a0 = a0
         # InputBlock
         s.y_in, s.mr_in = self._conv(s, n_in, a0)
         out1 = self._new(N, sizes, c)
-        ops.pnorm_forward(s.y_in, s.mr_in, out1, C=c, slope=self._slope(s_in), res=a0, res_mode=1,
+        ops.pnorm_forward(s.y_in, s.mr_in, out1, C=c, slope=self._slope(s, s_in), res=a0, res_mode=1,
                           res_mod=self.in_channels)
         s.out1 = out1
         # DownBlocks
@@ -415,10 +398,10 @@ class Vnet3D(NativeNet):
             nconv, sconv = bconv(blk)
             rec.y, rec.mr = self._conv(s, nconv, cur)
             rec.D0 = self._new(N, lv(blk.level), blk.C)
-            ops.pnorm_forward(rec.y, rec.mr, rec.D0, C=blk.C, slope=self._slope(sconv))
+            ops.pnorm_forward(rec.y, rec.mr, rec.D0, C=blk.C, slope=self._slope(s, sconv))
             rec.Xn, rec.coup = core(s, blk, rec.D0)
             rec.out = self._new(N, lv(blk.level), blk.C)
-            ops.pnorm_forward(rec.Xn, None, rec.out, C=blk.C, slope=self._slope(blk.tail_slope), res=rec.D0, res_mode=1)
+            ops.pnorm_forward(rec.Xn, None, rec.out, C=blk.C, slope=self._slope(s, blk.tail_slope), res=rec.D0, res_mode=1)
             rec.attn = None
             # (an encoder pass walks `encoder` = [in_ab] + downs and never meets the attention blocks)
             if stop is None and self.attention[len(s.down)]:      # the attended map feeds the next down block AND the skip connection
@@ -437,18 +420,18 @@ class Vnet3D(NativeNet):
             nconv, sconv = bconv(blk)
             rec.y, rec.mr = self._conv(s, nconv, cur)
             rec.D0 = self._new(N, lv(blk.level), blk.C)                      # xcat = [up | skip]
-            ops.pnorm_forward(rec.y, rec.mr, rec.D0, C=h, slope=self._slope(sconv), out_co=0)
+            ops.pnorm_forward(rec.y, rec.mr, rec.D0, C=h, slope=self._slope(s, sconv), out_co=0)
             ops.add_views(rec.D0, skips[i], h, dst_co=h, src_co=0, accumulate=False)
             rec.Xn, rec.coup = core(s, blk, rec.D0)
             rec.out = self._new(N, lv(blk.level), blk.C)
-            ops.pnorm_forward(rec.Xn, None, rec.out, C=blk.C, slope=self._slope(blk.tail_slope), res=rec.D0, res_mode=1)
+            ops.pnorm_forward(rec.Xn, None, rec.out, C=blk.C, slope=self._slope(s, blk.tail_slope), res=rec.D0, res_mode=1)
             s.up.append(rec)
             cur = rec.out
         # OutBlock
         s.o_in = cur
         s.y_o1, s.mr_o1 = self._conv(s, n_o1, cur)
         s.t = self._new(N, sizes, 2 * c)
-        ops.pnorm_forward(s.y_o1, s.mr_o1, s.t, C=2 * c, slope=self._slope(s_o1))
+        ops.pnorm_forward(s.y_o1, s.mr_o1, s.t, C=2 * c, slope=self._slope(s, s_o1))
         s.z, _ = self._conv(s, n_o2, s.t, stats=False)
         out = torch.empty(N, self.out_channels, *sizes, dtype=torch.float32, device=self.device)
         ops.act_to_image(s.z, out, act="tanh")
@@ -542,28 +525,28 @@ class Vnet3D(NativeNet):
             dmid = self._dmid(s, i, dy)
             sp = self.nodes[i].spec
             if sp.bias:
-                self.ops.bias_grad(dmid, sp.cout_p, self._grad_buf()[self.b_off[i]:self.b_off[i] + sp.cout_p])
+                self.ops.bias_grad(dmid, sp.cout_p, self._grad_buf(s)[self.b_off[i]:self.b_off[i] + sp.cout_p])
             return self._wgrad1(s, i, x_in, dmid, x_co)
         self._wgrad1(s, i, x_in, dy, x_co)
 
     def _wgrad1(self, s, i, x_in, dy, x_co=0):
-        ops, sp, lw, grad = self.ops, self.nodes[i].spec, s.lows[i], self._grad_buf()
+        ops, sp, lw, grad = self.ops, self.nodes[i].spec, s.lows[i], self._grad_buf(s)
         dw = grad[self.w_off[i]:self.w_off[i] + sp.master_numel]
-        self._wgrad_written(i, self._tw)    # (every weight-gradient launch is noted, NativeNet._wgrad_written; no fresh= hint here)
+        self._wgrad_written(i, s.tw)    # (every weight-gradient launch is noted, NativeNet._wgrad_written; no fresh= hint here)
         x_in, dy = lw.vin(x_in), lw.vout(dy)
         if sp.kind == "conv":
             ops.wgrad(lw.wgrad, dy, x_in, dw, g_co=x_co)
         else:
             ops.wgrad(lw.wgrad, x_in, dy, dw, a_co=x_co)
         self.grad_dirty = True
-        if self._tw is not None:
-            self._tw.grad_dirty = True
+        if s.tw is not None:
+            s.tw.grad_dirty = True
 
-    def _bias_slice(self, i, want_w):
+    def _bias_slice(self, s, i, want_w):
         """gradient slice of the bias in front of conv i's norm (separable: the (k,1,1) layer's)"""
         i = i + 1 if self.is_separable else i
         sp = self.nodes[i].spec
-        return self._grad_buf()[self.b_off[i]:self.b_off[i] + sp.cout_p] if (want_w and sp.bias) else None
+        return self._grad_buf(s)[self.b_off[i]:self.b_off[i] + sp.cout_p] if (want_w and sp.bias) else None
 
     def _dmid(self, s, i, dy):
         """separable conv i: gradient of the intermediate = data gradient of the (k,1,1) layer, computed once per dy"""
@@ -585,19 +568,19 @@ class Vnet3D(NativeNet):
     def _dgrad1(self, s, i, dy, out=None, out_co=0, accumulate=False):
         sp, lw = self.nodes[i].spec, s.lows[i]
         gx = out if out is not None else self._new(s.N, lw.in_dims, sp.cin_p)
-        dpack = (s.pk["dpack"] if self._tw is None else Twin(s.pk["dpack"], s.pk_tw["dpack"]))[s.pk["d_off"][i]:]
+        dpack = (s.pk["dpack"] if s.tw is None else Twin(s.pk["dpack"], s.pk_tw["dpack"]))[s.pk["d_off"][i]:]
         self.ops.gconv_classes(lw.dgrad, lw.vout(dy), dpack, None, lw.vin(gx), out_co=out_co, accumulate=accumulate)
         return gx
 
     def _block_backward(self, s, blk, rec, g, g2, g2_co, want_w):
         """gradient w.r.t. the block output (g [+ g2 slice]) -> total gradient w.r.t. D0 (= down, or xcat)"""
         ops, h = self.ops, blk.C // 2
-        dsl = (lambda name: self._slope(name, grad=True)) if want_w else (lambda name: None)
+        dsl = (lambda name: self._slope(s, name, grad=True)) if want_w else (lambda name: None)
         gu = torch.empty_like(rec.out)
         # G (= gu, the residual's gradient: second output of the same pass, not a copy launch behind it) becomes the gradient
         # w.r.t. core's input, in place
         G = torch.empty_like(rec.out)
-        ops.pnorm_backward(g, rec.Xn, None, gu, C=blk.C, slope=self._slope(blk.tail_slope), dslope=dsl(blk.tail_slope),
+        ops.pnorm_backward(g, rec.Xn, None, gu, C=blk.C, slope=self._slope(s, blk.tail_slope), dslope=dsl(blk.tail_slope),
                            g2=g2, g2_co=g2_co, res=rec.D0, res_mode=1, gres=G)
         cur = rec.Xn                                     # memory saving: the core's output, walked back coupling by coupling
         if s.inverse:
@@ -612,14 +595,14 @@ class Vnet3D(NativeNet):
                 else:
                     X, Y, ya, mra, yb, mrb = kept
                 dya = torch.empty_like(ya)
-                ops.pnorm_backward(G, ya, mra, dya, C=h, slope=self._slope(sf), dslope=dsl(sf), g_co=0, res_mode=3,
-                                   bias_grad=self._bias_slice(nf, want_w))
+                ops.pnorm_backward(G, ya, mra, dya, C=h, slope=self._slope(s, sf), dslope=dsl(sf), g_co=0, res_mode=3,
+                                   bias_grad=self._bias_slice(s, nf, want_w))
                 if want_w:
                     self._wgrad(s, nf, X, dya, x_co=h)
                 self._dgrad(s, nf, dya, out=G, out_co=h, accumulate=True)      # x2 also fed F
                 dyb = torch.empty_like(yb)
-                ops.pnorm_backward(G, yb, mrb, dyb, C=h, slope=self._slope(sg), dslope=dsl(sg), g_co=h, res_mode=3,
-                                   bias_grad=self._bias_slice(ng, want_w))
+                ops.pnorm_backward(G, yb, mrb, dyb, C=h, slope=self._slope(s, sg), dslope=dsl(sg), g_co=h, res_mode=3,
+                                   bias_grad=self._bias_slice(s, ng, want_w))
                 if want_w:
                     self._wgrad(s, ng, Y, dyb, x_co=0)
                 self._dgrad(s, ng, dyb, out=G, out_co=0, accumulate=True)      # y1 also fed G
@@ -635,20 +618,29 @@ class Vnet3D(NativeNet):
                 X, Y, ya, mra, yb, mrb = kept
             # y2 = x2 + G(y1): gradient of G's conv output from the y2 half, its data gradient joins the y1 half
             dyb = torch.empty_like(yb)
-            ops.pnorm_backward(G, yb, mrb, dyb, C=h, slope=self._slope(sg), dslope=dsl(sg), g_co=h,
-                               bias_grad=self._bias_slice(ng, want_w))
+            ops.pnorm_backward(G, yb, mrb, dyb, C=h, slope=self._slope(s, sg), dslope=dsl(sg), g_co=h,
+                               bias_grad=self._bias_slice(s, ng, want_w))
             if want_w:
                 self._wgrad(s, ng, Y, dyb, x_co=0)
             self._dgrad(s, ng, dyb, out=G, out_co=0, accumulate=True)
             # y1 = x1 + F(x2)
             dya = torch.empty_like(ya)
-            ops.pnorm_backward(G, ya, mra, dya, C=h, slope=self._slope(sf), dslope=dsl(sf), g_co=0,
-                               bias_grad=self._bias_slice(nf, want_w))
+            ops.pnorm_backward(G, ya, mra, dya, C=h, slope=self._slope(s, sf), dslope=dsl(sf), g_co=0,
+                               bias_grad=self._bias_slice(s, nf, want_w))
             if want_w:
                 self._wgrad(s, nf, X, dya, x_co=h)
             self._dgrad(s, nf, dya, out=G, out_co=h, accumulate=True)
         ops.add_views(G, gu, blk.C, accumulate=True)     # out = core(D0) + D0
         return G
+
+    def _inject(self, g, like, items):
+        """g (None: zeros shaped like `like`) += the sampled rows of a tapped level; ids are flat over the level's
+        [D,] H, W in row-major order, i.e. row numbers of the channels-last buffer"""
+        if g is None:
+            g = self.ops.zeros_like_act(like)
+        for n0, n, pid, rows in items or ():
+            self.ops.tap_scatter_add(g[n0:n0 + n], pid, rows, like.shape[-2])
+        return g
 
     def _backward(self, s, g_img, need_input_grad, want_w, start=None, inj_x=None, inj_y=None, tw=None):
         """tw: the pass recorded by _forward(..., tw) — g_img holds one gradient per input batch (None: that output took no part
@@ -660,27 +652,12 @@ class Vnet3D(NativeNet):
         assert not inj_y, "Vnet3D taps are block outputs: their gradients come as inj_x"
         assert tw is s.tw, "twin pass: backward with the partner the forward pass ran with"
         assert start == s.stop and (start is None) == (g_img is not None), "backward of the pass the forward recorded"
-        self._tw = tw
-        try:
-            return self._backward_impl(s, g_img, need_input_grad, want_w, start, inj_x or {})
-        finally:
-            self._tw = None
-
-    def _inject(self, g, like, items):
-        """g (None: zeros shaped like `like`) += the sampled rows of a tapped level; ids are flat over the level's
-        [D,] H, W in row-major order, i.e. row numbers of the channels-last buffer"""
-        if g is None:
-            g = self.ops.zeros_like_act(like)
-        for n0, n, pid, rows in items or ():
-            self.ops.tap_scatter_add(g[n0:n0 + n], pid, rows, like.shape[-2])
-        return g
-
-    def _backward_impl(self, s, g_img, need_input_grad, want_w, start=None, inj_x=None):
+        inj_x = inj_x or {}
         ops, c, L = self.ops, self.c, self.L
-        for net in (self, self._tw):
+        for net in (self, s.tw):
             if net is not None and net.master.grad is None:
                 net.master.grad = torch.zeros(net.numel, dtype=torch.float32, device=self.device)
-        dsl = (lambda name: self._slope(name, grad=True)) if want_w else (lambda name: None)
+        dsl = (lambda name: self._slope(s, name, grad=True)) if want_w else (lambda name: None)
         inv = s.inverse
         n_in, s_in = (self.n_in_ba, self.s_in_ba) if inv else (self.n_in, self.s_in)
         bconv = (lambda b: (b.conv_ba, b.conv_slope_ba)) if inv else (lambda b: (b.conv, b.conv_slope))
@@ -710,8 +687,8 @@ class Vnet3D(NativeNet):
             G = self._block_backward(s, blk, rec, g_cur, g2, g2_co, want_w)
             nconv, sconv = bconv(blk)
             dy = torch.empty_like(rec.y)
-            ops.pnorm_backward(G, rec.y, rec.mr, dy, C=blk.C, slope=self._slope(sconv),
-                               dslope=dsl(sconv), bias_grad=self._bias_slice(nconv, want_w))
+            ops.pnorm_backward(G, rec.y, rec.mr, dy, C=blk.C, slope=self._slope(s, sconv),
+                               dslope=dsl(sconv), bias_grad=self._bias_slice(s, nconv, want_w))
             if want_w:
                 self._wgrad(s, nconv, rec.x_in, dy)
             g_cur = self._dgrad(s, nconv, dy)
@@ -723,50 +700,29 @@ class Vnet3D(NativeNet):
             g_cur = self._inject(g_cur, s.out1, inj_x.get(0))
         dy = torch.empty_like(s.y_in)
         gres = torch.empty_like(s.y_in) if need_input_grad else None
-        ops.pnorm_backward(g_cur, s.y_in, s.mr_in, dy, C=c, slope=self._slope(s_in), dslope=dsl(s_in),
+        ops.pnorm_backward(g_cur, s.y_in, s.mr_in, dy, C=c, slope=self._slope(s, s_in), dslope=dsl(s_in),
                            g2=g2, g2_co=g2_co, res=s.a0, res_mode=1, res_mod=self.in_channels, gres=gres,
-                           bias_grad=self._bias_slice(n_in, want_w))
+                           bias_grad=self._bias_slice(s, n_in, want_w))
         if want_w:
             self._wgrad(s, n_in, s.a0, dy)
         if not need_input_grad:
             return None
         gx = self._dgrad(s, n_in, dy)
-        if not s.parts:
-            g_in = torch.empty_like(s.x_img)
-            ops.image_to_act_backward(gx, g_in, fold=0)
-            ops.repeat_backward(gres, g_in, c)               # adjoint of x.repeat (vnet3d.py:165-166)
-            return g_in
-        g_ins, n0 = [], 0
-        for xh in s.xs:
-            n1 = n0 + xh.shape[0]
-            g_in = torch.empty_like(xh)
-            ops.image_to_act_backward(gx[n0:n1], g_in, fold=0)
-            ops.repeat_backward(gres[n0:n1], g_in, c)
-            g_ins.append(g_in)
-            n0 = n1
-        return tuple(g_ins)
+        # (each part: + the adjoint of x.repeat, vnet3d.py:165-166)
+        g_ins = self._act_grad_to_images(gx, s.xs, s.need, each=lambda g_in, n0, n1: ops.repeat_backward(gres[n0:n1], g_in, c))
+        return tuple(g_ins) if s.parts else g_ins[0]
 
     def _backward_up_path(self, s, g_img, want_w, skip_grad):
         """OutBlock and UpBlocks of a full pass: fills skip_grad, returns the gradient w.r.t. the last DownBlock's output"""
         ops, c, L = self.ops, self.c, self.L
-        grad = self._grad_buf()
-        dsl = (lambda name: self._slope(name, grad=True)) if want_w else (lambda name: None)
+        grad = self._grad_buf(s)
+        dsl = (lambda name: self._slope(s, name, grad=True)) if want_w else (lambda name: None)
         inv = s.inverse
         n_o1, s_o1, n_o2 = (self.n_o1_ba, self.s_o1_ba, self.n_o2_ba) if inv else (self.n_o1, self.s_o1, self.n_o2)
         bconv = (lambda b: (b.conv_ba, b.conv_slope_ba)) if inv else (lambda b: (b.conv, b.conv_slope))
         # OutBlock
         gz = torch.empty_like(s.z)
-        if not s.parts:
-            ops.act_to_image_backward(g_img.contiguous().float(), s.out_img, gz, act="tanh")
-        else:
-            n0 = 0
-            for gh, xh in zip(g_img, s.xs):      # one gradient per input batch
-                n1 = n0 + xh.shape[0]
-                if gh is None:
-                    gz[n0:n1].zero_()
-                else:
-                    ops.act_to_image_backward(gh.contiguous().float(), s.out_img[n0:n1], gz[n0:n1], act="tanh")
-                n0 = n1
+        self._image_grad_to_act(g_img, s.xs, s.out_img, gz)      # one gradient per input batch
         if want_w:
             self._wgrad(s, n_o2, s.t, gz)
             n_b = n_o2 + 1 if self.is_separable else n_o2       # (the bias behind which gz arrives)
@@ -774,8 +730,8 @@ class Vnet3D(NativeNet):
             ops.bias_grad(gz, sp.cout_p, grad[self.b_off[n_b]:self.b_off[n_b] + sp.cout_p])
         gt = self._dgrad(s, n_o2, gz)
         dy = torch.empty_like(s.y_o1)
-        ops.pnorm_backward(gt, s.y_o1, s.mr_o1, dy, C=2 * c, slope=self._slope(s_o1), dslope=dsl(s_o1),
-                           bias_grad=self._bias_slice(n_o1, want_w))
+        ops.pnorm_backward(gt, s.y_o1, s.mr_o1, dy, C=2 * c, slope=self._slope(s, s_o1), dslope=dsl(s_o1),
+                           bias_grad=self._bias_slice(s, n_o1, want_w))
         if want_w:
             self._wgrad(s, n_o1, s.o_in, dy)
         g_cur = self._dgrad(s, n_o1, dy)            # gradient w.r.t. the last UpBlock's output
@@ -787,8 +743,8 @@ class Vnet3D(NativeNet):
             skip_grad[i] = (G, h)
             nconv, sconv = bconv(blk)
             dy = torch.empty_like(rec.y)
-            ops.pnorm_backward(G, rec.y, rec.mr, dy, C=h, slope=self._slope(sconv),
-                               dslope=dsl(sconv), g_co=0, bias_grad=self._bias_slice(nconv, want_w))
+            ops.pnorm_backward(G, rec.y, rec.mr, dy, C=h, slope=self._slope(s, sconv),
+                               dslope=dsl(sconv), g_co=0, bias_grad=self._bias_slice(s, nconv, want_w))
             if want_w:
                 self._wgrad(s, nconv, rec.x_in, dy)
             g_cur = self._dgrad(s, nconv, dy)         # w.r.t. the previous UpBlock's output / the last DownBlock's

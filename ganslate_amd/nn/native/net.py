@@ -71,7 +71,9 @@ def attention_extras(prefix: str, C: int, dims: int = 3) -> List["Extra"]:
 
 
 class _Saved:
-    __slots__ = ("x_img", "acts", "ys", "mrs", "out_img", "lows", "N", "attn", "__weakref__")
+    """what one recorded pass keeps for its backward pass. `need`: which of the pass's input tensors want a gradient, set by
+    the autograd node that records the pass (None: a pass no node recorded)"""
+    __slots__ = ("x_img", "acts", "ys", "mrs", "out_img", "lows", "N", "attn", "need", "__weakref__")
 
 
 class NativeNet:
@@ -538,14 +540,13 @@ class NativeNet:
 
     # ---- forward ----------------------------------------------------------------------------------------------------------
     def forward(self, x):
+        return self._whole_pass(x)
+
+    def _whole_pass(self, x, **kw):
+        """kw: keywords of this executor's _forward that belong to the pass (Vnet3D: inverse)"""
         assert x.dim() == 2 + self.dims and x.shape[1] == self.in_channels, \
             f"expected N x {self.in_channels} x {'D x ' if self.dims == 3 else ''}H x W"
-        x = x.contiguous().float()
-        record = torch.is_grad_enabled() and (x.requires_grad or self.requires_grad)
-        if not record:
-            out, _ = self._forward(x.detach(), save=False)
-            return out
-        return _NetFn.apply(x, self._token, self)
+        return run_pass(PassForm(self, lambda ts: ts[0], lambda gx: (gx,), remember=True, **kw), (x.contiguous().float(),))
 
     def forward_parts(self, xs):
         """several batches through this network as ONE pass (they follow each other in the batch; per-sample InstanceNorm:
@@ -553,23 +554,16 @@ class NativeNet:
         cut.py:160-166."""
         xs = tuple(t.contiguous().float() for t in xs)
         assert all(t.shape[1:] == xs[0].shape[1:] for t in xs), "forward_parts: batches of one image shape"
-        record = torch.is_grad_enabled() and (self.requires_grad or any(t.requires_grad for t in xs))
-        if not record:
-            out, _ = self._forward(tuple(t.detach() for t in xs), save=False)
-            return _split_parts(out, xs)
-        return _PartsFn.apply(self._token, self, *xs)
+        return run_pass(PassForm(self, tuple, tuple, parts=xs, remember=True), xs)
 
     def forward_parts_cat(self, pairs):
         """forward_parts for batches that are each torch.cat([a, b], dim=1) of two images (the conditional discriminator:
         D(cat(real_A, fake_B)), pix2pix.py:70,80): the images are converted side by side into the first activation, no
         concatenated tensor exists -> one output per batch"""
         pairs = [(a.contiguous().float(), b.contiguous().float()) for a, b in pairs]
-        flat = [t for pair in pairs for t in pair]
-        record = torch.is_grad_enabled() and (self.requires_grad or any(t.requires_grad for t in flat))
-        if not record:
-            out, _ = self._forward(tuple(ChannelCat((a.detach(), b.detach())) for a, b in pairs), save=False)
-            return _split_parts(out, pairs_shape(pairs))
-        return _CatPartsFn.apply(self._token, self, *flat)
+        return run_pass(PassForm(self, lambda ts: pairs_shape(zip(ts[::2], ts[1::2])),
+                                 lambda gx: [g for pair in gx for g in pair], parts=pairs_shape(pairs)),
+                        [t for pair in pairs for t in pair])
 
     def supports_channel_sources(self):
         """True when images enter this network through the plain image conversion (gs_image_to_act), which the channel-source
@@ -588,7 +582,8 @@ class NativeNet:
         parts = [[(t, int(c0), int(c1)) for t, c0, c1 in part] for part in parts]
         if not parts or any(not part for part in parts):
             raise ValueError("forward_sources: every batch needs at least one channel source")
-        if len(parts) > 1 and type(self)._forward is not NativeNet._forward:
+        own = type(self)._forward is not NativeNet._forward        # (an executor of its own takes the one batch itself)
+        if len(parts) > 1 and own:
             raise NotImplementedError(f"{type(self).__name__} takes one batch per pass")
         flat, layout = [], []
         for part in parts:
@@ -605,36 +600,97 @@ class NativeNet:
                                  f"{type(self).__name__} takes {self.in_channels}")
             flat += [t for t, _, _ in part]
             layout.append(tuple((c0, c1) for _, c0, c1 in part))
-        layout = tuple(layout)
-        record = torch.is_grad_enabled() and (self.requires_grad or any(t.requires_grad for t in flat))
-        if not record:
-            xs = _sources(layout, [t.detach() for t in flat])
-            out, _ = self._forward(xs if type(self)._forward is NativeNet._forward else xs[0], save=False)
-            return _split_parts(out, xs)
-        return _SourcesFn.apply(self._token, self, layout, *flat)
+        return run_pass(PassForm(self, lambda ts: _sources(layout, ts)[0] if own else _sources(layout, ts),
+                                 lambda gx: list(gx) if own else [g for part in gx for g in part],
+                                 parts=_sources(layout, flat)), flat)
 
     def forward_taps(self, x, taps, ids):
         """sampled features of intermediate nodes: taps = [("x"|"y", node)], ids = [LongTensor[P]] (pixel indices);
         returns a tuple of [N, P, C] fp32 tensors that autograd can differentiate into the network"""
-        x = x.contiguous().float()
-        return _TapFn.apply(self._token, self, tuple(taps), (tuple(ids),), x)
+        return self._tap_pass((x,), taps, (ids,))
 
     def forward_taps_parts(self, xs, taps, ids_per_part):
         """forward_taps for several batches in ONE encoder pass, each with its own pixel ids -> per batch a tuple of
         [N_p, P, C] tensors"""
-        xs = tuple(t.contiguous().float() for t in xs)
-        outs = _TapFn.apply(self._token, self, tuple(taps), tuple(tuple(i) for i in ids_per_part), *xs)
-        k = len(taps)
+        outs, k = self._tap_pass(xs, taps, ids_per_part), len(taps)
         return [outs[p * k:(p + 1) * k] for p in range(len(xs))]
+
+    def _tap_pass(self, xs, taps, ids):
+        form = PassForm(self, lambda ts: ts if len(ts) > 1 else ts[0], lambda gx: gx if isinstance(gx, tuple) else (gx,),
+                        taps=tuple(taps), ids=tuple(tuple(i) for i in ids), stop=max(node for _, node in taps))
+        return _TapFn.apply(self._token, form, *(t.contiguous().float() for t in xs))
 
     def _tap_source(self, saved, kind, node):
         """(channels-last buffer of a recorded pass, its live channels) that tap (kind, node) samples rows of"""
         return (saved.ys[node] if kind == "y" else saved.acts[node + 1]), self.nodes[node].spec.cout
 
-    def _forward(self, x, save, stop=None, tw=None):
+    # ---- the image boundary, batch part by batch part (shared with the executors that walk their own graph) ----------
+    def _images_to_act(self, xs, a):
+        """the parts xs of a batch (tensors, ChannelCat pairs, ChannelSources) -> the first activation a"""
+        ops, sp0, n0 = self.ops, self.nodes[0].spec, 0
+        for xh in xs:
+            ah = a[n0:n0 + xh.shape[0]]
+            n0 += xh.shape[0]
+            if isinstance(xh, ChannelSources):
+                assert sp0.wfold != "in", "channel sources enter through the plain image conversion"
+                ops.image_cat_to_act(list(xh), ah)
+            elif isinstance(xh, ChannelCat):
+                assert sp0.wfold != "in", "channel pairs enter through the plain image conversion"
+                ops.image_pair_to_act(xh[0], xh[1], ah)
+            elif sp0.wfold == "in":      # the W taps of the stem become channels while the image is converted
+                ops.image_unfold(xh, ah, sp0.k, sp0.pad, sp0.pad_mode)
+            else:
+                ops.image_to_act(xh, ah)
+
+    def _image_grad_to_act(self, g_img, xs, out_img, ga):
+        """gradient of the output image (a tensor, or one per part of xs) -> gradient ga of the last activation"""
+        ops, spl, n0 = self.ops, self.nodes[-1].spec, 0
+        for gh, xh in zip((g_img,) if torch.is_tensor(g_img) else g_img, xs):
+            gah, outh = ga[n0:n0 + xh.shape[0]], out_img[n0:n0 + xh.shape[0]]
+            n0 += xh.shape[0]
+            if gh is None:           # this part's output took no part in the loss
+                gah.zero_()
+            elif spl.wfold == "out":
+                ops.shiftadd_to_image_backward(gh.contiguous().float(), outh, gah, spl.k, act=self.out_act)
+            else:
+                ops.act_to_image_backward(gh.contiguous().float(), outh, gah, act=self.out_act)
+
+    def _act_grad_to_images(self, gx, xs, need, fold=0, fold_mode="reflect", each=None):
+        """gradient gx of the first activation -> one input gradient per part of xs (a ChannelCat / ChannelSources part: one
+        per image of it that wants one by `need`, the mask over the pass's input tensors, None elsewhere).
+        each(g_in, n0, n1): what else the executor adds to a plain part's gradient, issued right behind its launch"""
+        ops, sp0 = self.ops, self.nodes[0].spec
+        g_ins, n0, k = [], 0, 0
+        for xh in xs:
+            n1 = n0 + xh.shape[0]
+            if isinstance(xh, (ChannelSources, ChannelCat)):     # (no padded stem in these forms)
+                assert fold == 0
+                want = need[k:k + len(xh)] if need is not None else (True,) * len(xh)
+                k += len(xh)
+                if isinstance(xh, ChannelSources):
+                    g_ins.append(xh.write_grads(ops, gx[n0:n1], want))
+                else:
+                    ga, gb = (torch.empty_like(t) if w else None for t, w in zip(xh, want))
+                    if ga is not None or gb is not None:
+                        ops.image_pair_to_act_backward(gx[n0:n1], ga, gb, xh[0].shape[1], xh[1].shape[1])
+                    g_ins.append((ga, gb))
+            else:
+                g_in = torch.empty_like(xh)
+                if sp0.wfold == "in":
+                    ops.image_unfold_backward(gx[n0:n1], g_in, sp0.k, sp0.pad, fold, sp0.pad_mode)
+                else:
+                    ops.image_to_act_backward(gx[n0:n1], g_in, fold=fold, fold_mode=fold_mode)
+                if each is not None:
+                    each(g_in, n0, n1)
+                g_ins.append(g_in)
+            n0 = n1
+        return g_ins
+
+    def _forward(self, x, save, stop=None, tw=None, inverse=False):
         """stop = index of the last node to run (encoder-only passes of CUT, cut.py:297-312); None = whole net.
         tw = a second network of identical architecture (nn/native/twin.py): x is then the pair (xa, xb) and the pass runs
         as ONE batch of 2N images, images [0, N) through this network's weights and [N, 2N) through tw's."""
+        assert not inverse, f"{type(self).__name__} has one direction"
         ops, dev = self.ops, self.device
         # twin: x = (images of this network, images of tw), each a tuple of tensors that follow each other in the batch
         # (one network: a tensor, or a tuple of batches that run as one pass — forward_parts)
@@ -653,20 +709,7 @@ class NativeNet:
             fpack_all = Twin(fpack_all, tw._get_packs(*sizes)["fpack"])
         sp0 = self.nodes[0].spec
         a = torch.empty(N, *sizes, sp0.cin_p, dtype=self.ops.act_dtype, device=dev)
-        n0 = 0
-        for xh in xs:
-            ah = a[n0:n0 + xh.shape[0]]
-            n0 += xh.shape[0]
-            if isinstance(xh, ChannelSources):
-                assert sp0.wfold != "in", "channel sources enter through the plain image conversion"
-                ops.image_cat_to_act(list(xh), ah)
-            elif isinstance(xh, ChannelCat):
-                assert sp0.wfold != "in", "channel pairs enter through the plain image conversion"
-                ops.image_pair_to_act(xh[0], xh[1], ah)
-            elif sp0.wfold == "in":      # the W taps of the stem become channels while the image is converted
-                ops.image_unfold(xh, ah, sp0.k, sp0.pad, sp0.pad_mode)
-            else:
-                ops.image_to_act(xh, ah)
+        self._images_to_act(xs, a)
         acts, ys, mrs, attn_saved = [a], [], [], {}
         for i, (nd, lw) in enumerate(zip(self.nodes, lows)):
             if stop is not None and i > stop:
@@ -714,7 +757,7 @@ class NativeNet:
             return out, None
         s = _Saved()
         s.x_img, s.acts, s.ys, s.mrs, s.out_img, s.lows, s.N = (x if torch.is_tensor(x) else xs), acts, ys, mrs, out, lows, N
-        s.attn = attn_saved
+        s.attn, s.need = attn_saved, None
         return out, s
 
     # ---- backward ---------------------------------------------------------------------------------------------------------
@@ -745,16 +788,7 @@ class NativeNet:
         pending = None
         if g_img is not None:
             ga = torch.empty_like(s.acts[-1])
-            n0 = 0
-            for gh, xh in zip(g_img if parts else (g_img,), x_imgs):     # one gradient per input part
-                gah, outh = ga[n0:n0 + xh.shape[0]], s.out_img[n0:n0 + xh.shape[0]]
-                n0 += xh.shape[0]
-                if gh is None:           # this part's output took no part in the loss
-                    gah.zero_()
-                elif nodes[-1].spec.wfold == "out":
-                    ops.shiftadd_to_image_backward(gh.contiguous().float(), outh, gah, nodes[-1].spec.k, act=self.out_act)
-                else:
-                    ops.act_to_image_backward(gh.contiguous().float(), outh, gah, act=self.out_act)
+            self._image_grad_to_act(g_img, x_imgs, s.out_img, ga)     # one gradient per input part
             pending = (ga, 0, None, "reflect")
         skip: Dict[int, torch.Tensor] = {}
         db_items = []        # bias gradients of the convs in front of norms: one batched launch at the end of the pass
@@ -903,34 +937,7 @@ class NativeNet:
         if not need_input_grad:
             return None
         gx, f, _, fmode = pending[:4]
-        sp0 = nodes[0].spec
-        g_ins, n0 = [], 0
-        need, k = getattr(self, "_cat_need", None), 0
-        for xh in x_imgs:
-            gxh = gx[n0:n0 + xh.shape[0]]
-            n0 += xh.shape[0]
-            if isinstance(xh, ChannelSources):           # (fold is 0 here too)
-                assert f == 0
-                want = need[k:k + len(xh)] if need is not None else (True,) * len(xh)
-                k += len(xh)
-                g_ins.append(xh.write_grads(ops, gxh, want))
-                continue
-            if isinstance(xh, ChannelCat):               # (fold is 0 here: the pair form has no padded stem)
-                assert f == 0
-                want = need[k:k + 2] if need is not None else (True, True)
-                k += 2
-                ga = torch.empty_like(xh[0]) if want[0] else None
-                gb = torch.empty_like(xh[1]) if want[1] else None
-                if ga is not None or gb is not None:
-                    ops.image_pair_to_act_backward(gxh, ga, gb, xh[0].shape[1], xh[1].shape[1])
-                g_ins.append((ga, gb))
-                continue
-            g_in = torch.empty_like(xh)
-            if sp0.wfold == "in":
-                ops.image_unfold_backward(gxh, g_in, sp0.k, sp0.pad, f, sp0.pad_mode)
-            else:
-                ops.image_to_act_backward(gxh, g_in, fold=f, fold_mode=fmode)
-            g_ins.append(g_in)
+        g_ins = self._act_grad_to_images(gx, x_imgs, s.need, f, fmode)
         return tuple(g_ins) if parts else g_ins[0]
 
     # ---- data parallelism (reference: DistributedDataParallel per network, base.py:172-189) -------------
@@ -1057,55 +1064,6 @@ def _split_parts(out, parts):
     return tuple(outs)
 
 
-class _TapFn(torch.autograd.Function):
-    """Encoder-only pass returning sampled feature patches [N, P, C] (fp32) of several nodes as one autograd node:
-    forward gathers rows of the NHWC activations (a patch is one pixel's channel vector), backward scatters the patch
-    gradients back and runs the partial backward pass. Several batches (each with its own pixel ids) ride in one pass;
-    outputs come batch by batch, tap by tap."""
-
-    @staticmethod
-    def forward(ctx, token, net, taps, ids, *xs):
-        stop = max(node for _, node in taps)
-        xs = tuple(t.detach() for t in xs)
-        _, saved = net._forward(xs if len(xs) > 1 else xs[0], save=True, stop=stop)
-        ctx.net, ctx.saved, ctx.taps, ctx.ids, ctx.stop = net, saved, taps, ids, stop
-        ctx.sizes = tuple(t.shape[0] for t in xs)
-        ctx.need_x = any(ctx.needs_input_grad[4:])
-        ctx.want_w = net.requires_grad
-        if ctx.want_w:
-            net._fw_pending += 1
-        outs, n0 = [], 0
-        for np_, pids in zip(ctx.sizes, ids):
-            for (kind, node), pid in zip(taps, pids):
-                src, ch = net._tap_source(saved, kind, node)
-                outs.append(net.ops.tap_gather(src[n0:n0 + np_], pid, ch))
-            n0 += np_
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        net, s = ctx.net, ctx.saved
-        if ctx.want_w:
-            net._fw_pending -= 1
-        inj = {"x": {}, "y": {}}
-        k, n0 = len(ctx.taps), 0
-        for p, (np_, pids) in enumerate(zip(ctx.sizes, ctx.ids)):
-            for (kind, node), pid, g in zip(ctx.taps, pids, grads[p * k:(p + 1) * k]):
-                if g is not None:       # sparse: (first image, images, pixel ids, [images, P, c] gradient)
-                    inj[kind].setdefault(node, []).append((n0, np_, pid, g))
-            n0 += np_
-        if ctx.want_w:      # passes that write parameter gradients are ordered per network
-            net._order_backward_begin()
-        gx = net._backward(s, None, ctx.need_x, ctx.want_w, start=ctx.stop, inj_x=inj["x"], inj_y=inj["y"])
-        if ctx.want_w:
-            net._order_backward_end()
-        ctx.saved = None
-        if gx is None:
-            return (None,) * (4 + len(ctx.sizes))
-        gx = gx if isinstance(gx, tuple) else (gx,)
-        return (None, None, None, None) + tuple(g if need else None for g, need in zip(gx, ctx.needs_input_grad[4:]))
-
-
 class ChannelCat(tuple):
     """(a, b): two image batches that enter a network side by side along the channel axis — torch.cat([a, b], dim=1) without
     the launch (NativeNet.forward_parts_cat); looks like the concatenated tensor where the executor asks for a shape"""
@@ -1142,143 +1100,116 @@ def _sources(layout, tensors):
     return tuple(out)
 
 
-class _SourcesFn(torch.autograd.Function):
-    """forward_parts over batches given as channel sources: the tensors come flattened, `layout` holds their windows"""
+# ---- a recorded pass as ONE autograd node ---------------------------------------------------------------------------------
+class PassForm:
+    """What tells one input form of a pass from another. The node below sees the tensors of a pass as flat arguments:
+      pack(tensors) -> what `_forward` takes (a tensor, a tuple of batches / ChannelCat / ChannelSources, a twin pass's pair),
+      flat(gx)      -> what `_backward` returned, laid back onto those arguments, one entry per tensor,
+      parts         -> the batches the output is split along (None: the pass returns its one output whole),
+      tw            -> the second network of a twin pass;  remember: the pass is one `recorded_pass` may hand out,
+      kw            -> keywords of `_forward` that belong to this pass (stop, inverse);  taps, ids: see _TapFn."""
 
-    @staticmethod
-    def forward(ctx, token, net, layout, *ts):
-        xs = _sources(layout, [t.detach() for t in ts])
-        ctx.parts = type(net)._forward is NativeNet._forward        # (an executor of its own takes the one batch itself)
-        out, saved = net._forward(xs if ctx.parts else xs[0], save=True)
-        ctx.net, ctx.saved = net, saved
-        ctx.need = tuple(ctx.needs_input_grad[3:])
-        ctx.want_w = net.requires_grad
-        if ctx.want_w:
-            net._fw_pending += 1
-        ctx.set_materialize_grads(False)
-        return _split_parts(out, xs)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        net = ctx.net
-        if ctx.want_w:
-            net._fw_pending -= 1
-            net._order_backward_begin()
-        for g in grads:
-            if g is not None and g.is_cuda:
-                g.record_stream(torch.cuda.current_stream())
-        net._cat_need = ctx.need                       # which sources want a gradient (the executor's _backward reads it)
-        try:
-            gx = net._backward(ctx.saved, grads if ctx.parts else grads[0], any(ctx.need), ctx.want_w)
-        finally:
-            net._cat_need = None
-        if ctx.want_w:
-            net._order_backward_end()
-        ctx.saved = None
-        if gx is None:
-            return (None,) * (3 + len(ctx.need))
-        flat = [t for part in (gx if ctx.parts else (gx,)) for t in part]
-        return (None, None, None) + tuple(g if need else None for g, need in zip(flat, ctx.need))
+    def __init__(self, net, pack, flat, parts=None, tw=None, remember=False, taps=None, ids=None, **kw):
+        self.net, self.pack, self.flat, self.parts, self.tw, self.remember = net, pack, flat, parts, tw, remember
+        self.nets = (net,) if tw is None else (net, tw)
+        self.taps, self.ids, self.kw = taps, ids, kw
 
 
-class _CatPartsFn(torch.autograd.Function):
-    """forward_parts over batches given as channel pairs: inputs come flattened (a_0, b_0, a_1, b_1, ...)"""
-
-    @staticmethod
-    def forward(ctx, token, net, *ts):
-        xs = tuple(ChannelCat((ts[i].detach(), ts[i + 1].detach())) for i in range(0, len(ts), 2))
-        out, saved = net._forward(xs, save=True)
-        ctx.net, ctx.saved = net, saved
-        ctx.need = tuple(ctx.needs_input_grad[2:])
-        ctx.want_w = net.requires_grad
-        if ctx.want_w:
-            net._fw_pending += 1
-        ctx.set_materialize_grads(False)
-        return _split_parts(out, xs)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        net = ctx.net
-        if ctx.want_w:
-            net._fw_pending -= 1
-            net._order_backward_begin()
-        for g in grads:
-            if g is not None and g.is_cuda:
-                g.record_stream(torch.cuda.current_stream())
-        net._cat_need = ctx.need                       # which images want a gradient (NativeNet._backward reads it)
-        gx = net._backward(ctx.saved, grads, any(ctx.need), ctx.want_w)
-        net._cat_need = None
-        if ctx.want_w:
-            net._order_backward_end()
-        ctx.saved = None
-        if gx is None:
-            return (None,) * (2 + len(ctx.need))
-        flat = [t for pair in gx for t in pair]
-        return (None, None) + tuple(g if need else None for g, need in zip(flat, ctx.need))
+def recording(tensors, *nets):
+    """autograd semantics: a pass is recorded when anything it touches may want a gradient"""
+    return torch.is_grad_enabled() and (any(n.requires_grad for n in nets) or any(t.requires_grad for t in tensors))
 
 
-class _PartsFn(torch.autograd.Function):
-    """several batches through the whole network as one autograd node (NativeNet.forward_parts)"""
+def run_pass(form, tensors):
+    """one pass over `tensors` (contiguous fp32), recorded as one autograd node where a gradient may be asked for"""
+    if recording(tensors, *form.nets):
+        return _PassFn.apply(form.net._token, form, *tensors)
+    out, _ = form.net._forward(form.pack(tuple(t.detach() for t in tensors)), save=False, tw=form.tw, **form.kw)
+    return out if form.parts is None else _split_parts(out, form.parts)
 
-    @staticmethod
-    def forward(ctx, token, net, *xs):
-        xs = tuple(t.detach() for t in xs)
-        out, saved = net._forward(xs, save=True)
+
+def _record(ctx, form, tensors):
+    """forward half of a node: runs the pass and keeps what its backward needs. What is a fact of THIS pass goes into its
+    saved record (which inputs want a gradient), not onto the network — other passes of the network are recorded and replayed
+    in between."""
+    tensors = tuple(t.detach() for t in tensors)
+    out, saved = form.net._forward(form.pack(tensors), save=True, tw=form.tw, **form.kw)
+    saved.need = tuple(ctx.needs_input_grad[2:])
+    if form.remember:
         n0 = 0
-        for t in xs:
-            net._remember_pass(t, saved, n0)
+        for t in tensors:
+            form.net._remember_pass(t, saved, n0)
             n0 += t.shape[0]
-        ctx.net, ctx.saved = net, saved
-        ctx.need = tuple(ctx.needs_input_grad[2:])
-        ctx.want_w = net.requires_grad
-        if ctx.want_w:
+    ctx.form, ctx.saved = form, saved
+    ctx.want_w = form.net.requires_grad     # autograd semantics: decided when the graph is recorded
+    if ctx.want_w:
+        for net in form.nets:
             net._fw_pending += 1
-        ctx.set_materialize_grads(False)
-        return _split_parts(out, xs)
+    return out, saved
+
+
+def _replay(ctx, grads, g_img, **kw):
+    """backward half of a node. Merged weight-gradient launches (_deferred), the bucketed all-reduce (final_pass) and the
+    cross-stream ordering all hang on _fw_pending and the begin / end bracket: every form goes through here."""
+    form, s = ctx.form, ctx.saved
+    if ctx.want_w:      # passes that write parameter gradients are ordered per network
+        for net in form.nets:
+            net._fw_pending -= 1
+        for net in form.nets:
+            net._order_backward_begin()
+    for g in grads:
+        if g is not None and g.is_cuda:       # an incoming gradient may come from another stream's allocator pool
+            g.record_stream(torch.cuda.current_stream())
+    gx = form.net._backward(s, g_img, any(s.need), ctx.want_w, tw=form.tw, **kw)
+    if ctx.want_w:
+        for net in form.nets:
+            net._order_backward_end()
+    ctx.saved = None
+    if gx is None:
+        return (None,) * (2 + len(s.need))
+    return (None, None) + tuple(g if need else None for g, need in zip(form.flat(gx), s.need))
+
+
+class _PassFn(torch.autograd.Function):
+    """A whole pass — one network or a twin pair, whatever form its images come in — as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, token, form, *tensors):
+        out, _ = _record(ctx, form, tensors)
+        ctx.set_materialize_grads(False)      # (an output that took no part in the loss: None, the executors' zero rule)
+        return out if form.parts is None else _split_parts(out, form.parts)
 
     @staticmethod
     def backward(ctx, *grads):
-        net = ctx.net
-        if ctx.want_w:
-            net._fw_pending -= 1
-            net._order_backward_begin()
-        for g in grads:
-            if g is not None and g.is_cuda:
-                g.record_stream(torch.cuda.current_stream())
-        gx = net._backward(ctx.saved, grads, any(ctx.need), ctx.want_w)
-        if ctx.want_w:
-            net._order_backward_end()
-        ctx.saved = None
-        if gx is None:
-            return (None,) * (2 + len(grads))
-        return (None, None) + tuple(g if need else None for g, need in zip(gx, ctx.need))
+        return _replay(ctx, grads, grads[0] if ctx.form.parts is None else grads)
 
 
-class _NetFn(torch.autograd.Function):
-    """The whole network as one autograd node."""
+class _TapFn(torch.autograd.Function):
+    """Encoder-only pass returning sampled feature patches [N, P, C] (fp32) of several nodes as one autograd node:
+    forward gathers rows of the NHWC activations (a patch is one pixel's channel vector), backward scatters the patch
+    gradients back and runs the partial backward pass. Several batches (each with its own pixel ids) ride in one pass;
+    outputs come batch by batch, tap by tap."""
 
     @staticmethod
-    def forward(ctx, x, token, net: NativeNet):
-        out, saved = net._forward(x.detach(), save=True)
-        net._remember_pass(x, saved)
-        ctx.net, ctx.saved = net, saved
-        ctx.need_x = ctx.needs_input_grad[0]
-        ctx.want_w = net.requires_grad     # autograd semantics: decided when the graph is recorded
-        if ctx.want_w:
-            net._fw_pending += 1
-        return out
+    def forward(ctx, token, form, *xs):
+        _, saved = _record(ctx, form, xs)
+        outs, n0 = [], 0
+        for xh, pids in zip(xs, form.ids):
+            for (kind, node), pid in zip(form.taps, pids):
+                src, ch = form.net._tap_source(saved, kind, node)
+                outs.append(form.net.ops.tap_gather(src[n0:n0 + xh.shape[0]], pid, ch))
+            n0 += xh.shape[0]
+        ctx.sizes = tuple(t.shape[0] for t in xs)
+        return tuple(outs)
 
     @staticmethod
-    def backward(ctx, g):
-        net = ctx.net
-        if ctx.want_w:
-            net._fw_pending -= 1
-        if ctx.want_w:      # passes that write parameter gradients are ordered per network
-            net._order_backward_begin()
-        if g.is_cuda:           # the incoming gradient may come from another stream's allocator pool
-            g.record_stream(torch.cuda.current_stream())
-        gx = net._backward(ctx.saved, g, ctx.need_x, ctx.want_w)
-        if ctx.want_w:
-            net._order_backward_end()
-        ctx.saved = None
-        return gx, None, None
+    def backward(ctx, *grads):
+        form = ctx.form
+        inj = {"x": {}, "y": {}}
+        k, n0 = len(form.taps), 0
+        for p, (np_, pids) in enumerate(zip(ctx.sizes, form.ids)):
+            for (kind, node), pid, g in zip(form.taps, pids, grads[p * k:(p + 1) * k]):
+                if g is not None:       # sparse: (first image, images, pixel ids, [images, P, c] gradient)
+                    inj[kind].setdefault(node, []).append((n0, np_, pid, g))
+            n0 += np_
+        return _replay(ctx, grads, None, start=form.kw["stop"], inj_x=inj["x"], inj_y=inj["y"])

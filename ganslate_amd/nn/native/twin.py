@@ -13,7 +13,6 @@ prologue of the second tile hides under the first one's K loop (csrc/hconvw.hip)
 tensor. Ops that have no native twin form run the two halves one after the other (`TwinSplit`), which is what two
 separate passes would do: same arithmetic, same summation order.
 """
-import torch
 
 
 class Twin:
@@ -156,59 +155,10 @@ class TwinNet:
         pb = tuple(t.contiguous().float() for t in pb)
         assert sum(t.shape[0] for t in pa) == sum(t.shape[0] for t in pb) and \
             all(t.shape[1:] == pa[0].shape[1:] for t in pa + pb), "TwinNet: both networks take batches of one shape"
-        record = torch.is_grad_enabled() and (a.requires_grad or b.requires_grad or any(t.requires_grad for t in pa + pb))
-        if record and a.requires_grad != b.requires_grad:
+        from .net import PassForm, recording, run_pass
+        if recording(pa + pb, a, b) and a.requires_grad != b.requires_grad:
             raise RuntimeError("TwinNet: both networks must be trainable or both frozen in one pass")
-        if record:
-            outs = _TwinFn.apply(a._token, self, len(pa), *pa, *pb)
-        else:
-            out, _ = a._forward((tuple(t.detach() for t in pa), tuple(t.detach() for t in pb)), save=False, tw=b)
-            outs = _split_parts(out, pa + pb)
+        # both networks as one autograd node (one input and one output per batch part)
+        outs = run_pass(PassForm(a, lambda ts: (ts[:len(pa)], ts[len(pa):]), tuple, parts=pa + pb, tw=b), pa + pb)
         oa, ob = outs[:len(pa)], outs[len(pa):]
         return (oa if isinstance(xa, (tuple, list)) else oa[0]), (ob if isinstance(xb, (tuple, list)) else ob[0])
-
-
-def _split_parts(out, parts):
-    outs, n0 = [], 0
-    for t in parts:
-        outs.append(out[n0:n0 + t.shape[0]])
-        n0 += t.shape[0]
-    return tuple(outs)
-
-
-class _TwinFn(torch.autograd.Function):
-    """both networks of a TwinNet as one autograd node (one input and one output per batch part)"""
-
-    @staticmethod
-    def forward(ctx, token, twin, na, *parts):
-        a, b = twin.a, twin.b
-        parts = tuple(t.detach() for t in parts)
-        out, saved = a._forward((parts[:na], parts[na:]), save=True, tw=b)
-        ctx.twin, ctx.saved = twin, saved
-        ctx.need = tuple(ctx.needs_input_grad[3:])
-        ctx.want_w = a.requires_grad
-        if ctx.want_w:
-            a._fw_pending += 1
-            b._fw_pending += 1
-        ctx.set_materialize_grads(False)
-        return _split_parts(out, parts)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        a, b = ctx.twin.a, ctx.twin.b
-        if ctx.want_w:
-            a._fw_pending -= 1
-            b._fw_pending -= 1
-            a._order_backward_begin()
-            b._order_backward_begin()
-        for g in grads:
-            if g is not None and g.is_cuda:
-                g.record_stream(torch.cuda.current_stream())
-        gx = a._backward(ctx.saved, grads, any(ctx.need), ctx.want_w, tw=b)
-        if ctx.want_w:
-            a._order_backward_end()
-            b._order_backward_end()
-        ctx.saved = None
-        if gx is None:
-            return (None,) * (3 + len(grads))
-        return (None, None, None) + tuple(g if need else None for g, need in zip(gx, ctx.need))
