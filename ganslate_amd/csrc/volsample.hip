@@ -25,6 +25,11 @@
 // one IEEE fp32 operation per step (no contraction), the focal point read from device memory, the start clamped into the
 // volume so that no point can make the kernel read outside it.
 //
+// gs_patch_affine_clip_minmax / gs_patch_affine — the same crop through a 3 x 3 matrix (random flips, rotation, zoom: data/
+// utils/patch_affine.py): per output voxel float64 source coordinates round the patch centre, the eight corners masked and
+// bounds-checked one by one, three rounded-step fp32 lerps (W, H, D), then the same chain (or none, for the raw gather that
+// feeds gs_patch_zscore). One thread per voxel, the modalities looped inside it; no contraction anywhere in the definition.
+//
 // gs_volume_prepare — a whole case for the val / test engines (data/multimodal_valtest.py): the same mask step and the same
 // per-voxel chain (one device function, clip_minmax), with centred padding up to a target shape in between; the pad value is
 // the minimum of the masked volume over the case, NaN-propagating like np.min, each mask padded with its own minimum. Two
@@ -313,6 +318,147 @@ __global__ __launch_bounds__(256) void patch_clip_minmax_kernel(const ClipK k, f
   }
 }
 
+// ---- gs_patch_affine_clip_minmax / gs_patch_affine --------------------------------------------------------------------
+// The augmented patch (ganslate_hip.h states the definition): one thread per output voxel, W fastest, so the 64 lanes of a
+// wave walk one line of the source and their eight corner reads fall into a few neighbouring rows. Coordinates (float64),
+// the in-bounds tests and the mask bytes are per voxel; the modalities are looped inside the thread, each plane's store
+// coalesced. hipcc contracts a * b + c to an fma by default, through __fmul_rn / __fadd_rn too (slidewin.hip), so the
+// coordinate and lerp bodies switch contraction off.
+struct AffK {
+  const void* vol[PC_MAX];
+  int dtype[PC_MAX];
+  float outside[PC_MAX], divisor[PC_MAX], lo[PC_MAX], hi[PC_MAX];
+  const uint8_t* mask;             // nullptr: no mask (gs_patch_affine)
+  const int32_t* point;            // device focal point; nullptr: start[] is the patch start
+  int start[3];
+  double M[9];
+  int C, D, H, W, pd, ph, pw;
+  long long n;
+};
+
+__device__ __forceinline__ double affine_coord(const double* m, double r0, double r1, double r2, double base) {
+#pragma clang fp contract(off)
+  const double a = m[0] * r0;
+  const double b = m[1] * r1;
+  const double c = m[2] * r2;
+  const double ab = a + b;
+  const double abc = ab + c;
+  return abc + base;
+}
+
+__device__ __forceinline__ float lerp_rn(float a, float b, float t) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  const float p = t * d;
+  return a + p;
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(256) void patch_affine_kernel(const AffK k, float* out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= k.n) return;
+  const int size[3] = {k.D, k.H, k.W}, patch[3] = {k.pd, k.ph, k.pw};
+  int o[3];
+  o[2] = (int)(i % k.pw);
+  const long long row = i / k.pw;
+  o[1] = (int)(row % k.ph);
+  o[0] = (int)(row / k.ph);
+  double r[3], base[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    int s = k.start[a];
+    if (k.point) {
+      s = k.point[a] - patch[a] / 2;
+      const int top = size[a] - patch[a];
+      s = s > top ? top : s;
+      s = s < 0 ? 0 : s;
+    }
+    const double c = (double)(patch[a] - 1) * 0.5;       // exact
+    r[a] = (double)o[a] - c;                             // exact
+    base[a] = (double)s + c;                             // exact
+  }
+  int ix[3];
+  float t[3];
+  bool reach = true;                                     // false: all eight corners are outside
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double s = affine_coord(k.M + 3 * a, r[0], r[1], r[2], base[a]);
+    const double f = floor(s);
+    t[a] = (float)__dsub_rn(s, f);
+    const bool in = s >= -1.0 && s < (double)size[a];    // NaN: outside
+    reach = reach && in;
+    ix[a] = in ? (int)f : 0;                             // in [-1, size - 1]
+  }
+  // off[q], q = dz * 4 + dy * 2 + dx: where corner q is read. A corner that takes the outside value reads voxel 0 instead
+  // (there always is one) and drops it: every load is unconditional, so the eight of a stage are in flight together
+  // instead of one round trip per branch.
+  const long long off0 = ((long long)ix[0] * k.H + ix[1]) * k.W + ix[2];
+  const long long sz = (long long)k.H * k.W, sy = k.W;
+  long long off[8];
+  unsigned valid = 0;                                    // bit q: corner q is read
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int z = ix[0] + (q >> 2), y = ix[1] + ((q >> 1) & 1), x = ix[2] + (q & 1);
+    const bool in = reach && (unsigned)z < (unsigned)k.D && (unsigned)y < (unsigned)k.H && (unsigned)x < (unsigned)k.W;
+    off[q] = in ? off0 + (q >> 2) * sz + ((q >> 1) & 1) * sy + (q & 1) : 0;
+    valid |= in ? 1u << q : 0u;
+  }
+  if (k.mask) {
+    uint8_t m[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) m[q] = k.mask[off[q]];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (!m[q]) {
+        valid &= ~(1u << q);
+        off[q] = 0;
+      }
+    }
+  }
+  for (int c = 0; c < k.C; ++c) {
+    const float outside = k.outside[c];
+    float v[8];
+    if (k.dtype[c] == GS_VOL_F32) {
+      const float* vol = static_cast<const float*>(k.vol[c]);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = vol[off[q]];
+    } else {
+      const short* vol = static_cast<const short*>(k.vol[c]);
+      short raw[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) raw[q] = vol[off[q]];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = (float)raw[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = (valid >> q) & 1u ? v[q] : outside;
+    const float c00 = lerp_rn(v[0], v[1], t[2]), c01 = lerp_rn(v[2], v[3], t[2]);
+    const float c10 = lerp_rn(v[4], v[5], t[2]), c11 = lerp_rn(v[6], v[7], t[2]);
+    float g = lerp_rn(lerp_rn(c00, c01, t[1]), lerp_rn(c10, c11, t[1]), t[0]);
+    if constexpr (CLIP) g = clip_minmax(g, k.divisor[c], k.lo[c], k.hi[c], __fsub_rn(k.hi[c], k.lo[c]));
+    out[(long long)c * k.n + i] = g;
+  }
+}
+
+int launch_affine(AffK& k, const int32_t* patch, const double* M, float* out, bool clip, void* stream) {
+  for (int j = 0; j < 9; ++j) k.M[j] = M[j];
+  k.pd = patch[0]; k.ph = patch[1]; k.pw = patch[2];
+  k.n = (long long)patch[0] * patch[1] * patch[2];
+  const long long blocks = (k.n + 255) / 256;            // one voxel per thread
+  GS_REQUIRE(blocks <= 0x7fffffffLL, "gs_patch_affine: %lld voxels do not fit one grid", k.n);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (clip) hipLaunchKernelGGL(patch_affine_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, k, out);
+  else hipLaunchKernelGGL(patch_affine_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, k, out);
+  GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+inline bool finite9(const double* M) {
+  for (int j = 0; j < 9; ++j)
+    if (!(M[j] - M[j] == 0.0)) return false;             // inf - inf and NaN - NaN are NaN
+  return true;
+}
+
 // ---- gs_volume_prepare ---------------------------------------------------------------------------------------------
 constexpr int VP_MAX_MASKS = 1 + GS_VM_MAX_LABELS;
 constexpr int VP_PARTS = 256;              // workgroups of the minimum pass per volume / mask
@@ -479,6 +625,63 @@ extern "C" int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtyp
                      static_cast<hipStream_t>(stream), k, out);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int gs_patch_affine_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
+                                           int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch,
+                                           const double* M, const float* outside, const float* divisor, const float* lo,
+                                           const float* hi, float* out, void* stream) {
+  GS_REQUIRE(vols && dtypes && mask && point && patch && M && outside && divisor && lo && hi && out,
+             "gs_patch_affine_clip_minmax: null argument");
+  GS_REQUIRE(C >= 1 && C <= PC_MAX, "gs_patch_affine_clip_minmax: between 1 and %d modalities per call; got %d", PC_MAX, C);
+  GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
+                 patch[2] <= W,
+             "gs_patch_affine_clip_minmax: patch %d x %d x %d does not fit the %d x %d x %d volume", patch[0], patch[1],
+             patch[2], D, H, W);
+  GS_REQUIRE(finite9(M), "gs_patch_affine_clip_minmax: the matrix has a non-finite entry");
+  AffK k;
+  for (int c = 0; c < PC_MAX; ++c) {
+    const int s = c < C ? c : 0;
+    GS_REQUIRE(vols[s], "gs_patch_affine_clip_minmax: null volume %d", s);
+    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16,
+               "gs_patch_affine_clip_minmax: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", dtypes[s], s);
+    GS_REQUIRE(hi[s] > lo[s], "gs_patch_affine_clip_minmax: clip range [%g, %g] of volume %d is empty", lo[s], hi[s], s);
+    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "gs_patch_affine_clip_minmax: divisor %g of volume %d",
+               divisor[s], s);
+    k.vol[c] = vols[s];
+    k.dtype[c] = dtypes[s];
+    k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
+  }
+  k.mask = mask;
+  k.point = point;
+  k.start[0] = k.start[1] = k.start[2] = 0;
+  k.C = C; k.D = D; k.H = H; k.W = W;
+  return launch_affine(k, patch, M, out, true, stream);
+}
+
+extern "C" int gs_patch_affine(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                               const int32_t* size, const double* M, float fill, float* out, void* stream) {
+  GS_REQUIRE(vol && start && size && M && out, "gs_patch_affine: null argument");
+  GS_REQUIRE(dtype == GS_VOL_F32 || dtype == GS_VOL_I16, "gs_patch_affine: dtype %d (GS_VOL_F32 / GS_VOL_I16)", dtype);
+  GS_REQUIRE(D > 0 && H > 0 && W > 0 && size[0] > 0 && size[1] > 0 && size[2] > 0 && size[0] <= D && size[1] <= H &&
+                 size[2] <= W,
+             "gs_patch_affine: patch %d x %d x %d does not fit the %d x %d x %d volume", size[0], size[1], size[2], D, H, W);
+  GS_REQUIRE(start[0] >= 0 && start[1] >= 0 && start[2] >= 0 && start[0] <= D - size[0] && start[1] <= H - size[1] &&
+                 start[2] <= W - size[2],
+             "gs_patch_affine: patch [%d+%d, %d+%d, %d+%d] outside the %d x %d x %d volume", start[0], size[0], start[1],
+             size[1], start[2], size[2], D, H, W);
+  GS_REQUIRE(finite9(M), "gs_patch_affine: the matrix has a non-finite entry");
+  AffK k;
+  for (int c = 0; c < PC_MAX; ++c) {
+    k.vol[c] = vol;
+    k.dtype[c] = dtype;
+    k.outside[c] = fill; k.divisor[c] = 1.f; k.lo[c] = 0.f; k.hi[c] = 1.f;
+  }
+  k.mask = nullptr;
+  k.point = nullptr;
+  k.start[0] = start[0]; k.start[1] = start[1]; k.start[2] = start[2];
+  k.C = 1; k.D = D; k.H = H; k.W = W;
+  return launch_affine(k, size, M, out, false, stream);
 }
 
 extern "C" int64_t gs_volume_prepare_ws_bytes(void) { return (int64_t)(PC_MAX + VP_MAX_MASKS) * VP_PARTS * 4; }

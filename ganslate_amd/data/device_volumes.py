@@ -1,7 +1,9 @@
 """Device-side training-patch pipeline of the 3-D volume datasets: volumes resident in HBM, per
 iteration only patch coordinates arrive from the loader (data/volume_datasets.py RawPatch), crop + z-score + range
 scaling run as gs_patch_zscore (csrc/volproc.hip) and write straight into the fp32 [N, 1, d, h, w] batch `set_input`
-takes. Reference path being replaced: projects/brats_mri_sequence_translation/datasets/train_dataset.py:83-92."""
+takes. Reference path being replaced: projects/brats_mri_sequence_translation/datasets/train_dataset.py:83-92.
+With `augmentation` a sample also carries a 3 x 3 matrix: gs_patch_affine (csrc/volsample.hip) gathers the patch through
+it into a scratch patch, and gs_patch_zscore normalises that as a volume of its own."""
 import numpy as np
 import torch
 
@@ -48,7 +50,14 @@ class DeviceVolumePipeline:
                 continue
             dst = torch.empty((len(items), 1, *self.size), dtype=torch.float32, device=self.device)
             for n, r in enumerate(items):
-                self.ops.patch_zscore(self.volume(r.domain, r.index), r.start, self.size, dst[n, 0], (-1.0, 1.0))
+                if r.matrix is None:
+                    self.ops.patch_zscore(self.volume(r.domain, r.index), r.start, self.size, dst[n, 0], (-1.0, 1.0))
+                    continue
+                # augmented: the raw gather into a dense patch, which patch_zscore then takes as a volume of its own
+                raw = torch.empty(tuple(self.size), dtype=torch.float32, device=self.device)
+                self.ops.patch_affine(self.volume(r.domain, r.index), r.start, self.size, r.matrix,
+                                      self.dataset.augmentation.fill, raw)
+                self.ops.patch_zscore(raw, (0, 0, 0), self.size, dst[n, 0], (-1.0, 1.0))
             out[key] = dst.squeeze(2) if self.squeeze else dst
         return out
 
@@ -59,7 +68,8 @@ class DeviceMultiModalPipeline:
     indices and uniforms arrive. Per sample: one gs_voxel_draw per domain when unpaired (B's reads A's point from device
     memory), one in total when paired, and one gs_patch_clip_minmax per domain writing all of its modalities straight into
     the batch (csrc/volsample.hip). Nothing synchronises per iteration; the empty-zone check of a case runs once, when its
-    mask is first uploaded. Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
+    mask is first uploaded. A sample that carries an augmentation matrix takes gs_patch_affine_clip_minmax instead: the
+    same crop as one trilinear gather through the matrix (data/utils/patch_affine.py). Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
     train_dataset.py:106-188 with datasets/utils/patch_samplers.py."""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
@@ -109,12 +119,15 @@ class DeviceMultiModalPipeline:
             self.checked.add((domain, index))
         return mask, weight, [self.volume(n, index) for n in ds.modalities[domain]]
 
-    def _patch(self, domain, index, vols, mask, point, dst):
+    def _patch(self, domain, index, vols, mask, point, dst, matrix=None):
         ds = self.dataset
         names = ds.modalities[domain]
-        self.ops.patch_clip_minmax(vols, mask, point, self.size, [ds.outside_value[n] for n in names],
-                                   [ds.divisor(n, index) for n in names], [ds.clip_range[n][0] for n in names],
-                                   [ds.clip_range[n][1] for n in names], dst)
+        cols = ([ds.outside_value[n] for n in names], [ds.divisor(n, index) for n in names],
+                [ds.clip_range[n][0] for n in names], [ds.clip_range[n][1] for n in names])
+        if matrix is None:
+            self.ops.patch_clip_minmax(vols, mask, point, self.size, *cols, dst)
+        else:
+            self.ops.patch_affine_clip_minmax(vols, mask, point, self.size, matrix, *cols, dst)
 
     def __call__(self, batch):
         from .multimodal_volumes import RawCase
@@ -128,16 +141,16 @@ class DeviceMultiModalPipeline:
         for i, (a, b) in enumerate(zip(items_A, items_B)):
             mask_A, weight, vols_A = self.case("A", a.index)
             self.ops.voxel_draw(mask_A, weight, self.size, a.u, points[i, 0])
-            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i])
+            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i], a.matrix)
             if ds.paired:                                   # the same point, A's mask and A's case
                 points[i, 1].copy_(points[i, 0])
                 self._patch("B", a.index, [self.volume(m, a.index) for m in ds.modalities["B"]], mask_A, points[i, 0],
-                            dst["B"][i])
+                            dst["B"][i], b.matrix)
             else:
                 mask_B, _, vols_B = self.case("B", b.index)
                 self.ops.voxel_draw(mask_B, None, self.size, b.u, points[i, 1], focal_A=points[i, 0],
                                     dims_A=tuple(mask_A.shape), proportion=ds.focal_region_proportion)
-                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i])
+                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i], b.matrix)
         self.points = points
         out.update(dst)
         return out

@@ -14,7 +14,12 @@ variant: B's point is drawn uniformly inside the body within a box around the co
 
 The selection rule — shared by this host path, the device kernel (csrc/volsample.hip, gs_voxel_draw) and the test oracle —
 is stated at `draw_focal_point`. With `device_transforms: true` a sample is only case indices and uniforms; the volumes
-stay resident in HBM and `DeviceMultiModalPipeline` (data/device_volumes.py) draws, crops and normalises on the GPU."""
+stay resident in HBM and `DeviceMultiModalPipeline` (data/device_volumes.py) draws, crops and normalises on the GPU.
+
+`augmentation` (not in the reference; data/utils/patch_affine.py) turns the crop into one trilinear gather through a random
+3 x 3 matrix — flips, rotation, zoom — round the same patch centre: mask, then interpolate, then the same normalisation.
+Its eight `np.random` uniforms per matrix follow the sample's draws above (one matrix for a paired sample, A's then B's
+otherwise); without the field nothing changes, the random streams included."""
 import json
 import math
 import random
@@ -28,6 +33,7 @@ from torch.utils.data import Dataset
 
 from .. import configs
 from .utils.normalization import min_max_normalize
+from .utils.patch_affine import draw_params, matrix_tuple, parse_augmentation, sample_patch
 
 PAIRED_SAMPLING_SCHEMES = ("uniform-random-within-body", "fdg-pet-weighted")
 UNPAIRED_SAMPLING_SCHEMES = ("uniform-random-within-body-sf", "fdg-pet-weighted-sf")
@@ -49,6 +55,9 @@ class MultiModalVolumeDatasetConfig(configs.base.BaseDatasetConfig):
     focal_region_proportion: Tuple[float, float, float] = (0.6, 0.3, 0.3)   # DHW, unpaired only
     # not in the reference: volumes resident in HBM, draw + crop + normalisation on the GPU (data/device_volumes.py)
     device_transforms: bool = False
+    # not in the reference: random flips / rotation / zoom of every patch as one trilinear gather (data/utils/
+    # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W]}
+    augmentation: Optional[Dict[str, Any]] = None
 
 
 def valid_zone(size, patch):
@@ -109,11 +118,13 @@ def draw_focal_point(mask, weight, patch, u, box=None):
 
 
 class RawCase:
-    """what a worker hands over with device_transforms on: which case, and the uniform its focal point is drawn from"""
-    __slots__ = ("domain", "index", "u")
+    """what a worker hands over with device_transforms on: which case, the uniform its focal point is drawn from, and the
+    augmentation matrix of its patch (9 floats, row-major) or None"""
+    __slots__ = ("domain", "index", "u", "matrix")
 
-    def __init__(self, domain, index, u):
+    def __init__(self, domain, index, u, matrix=None):
         self.domain, self.index, self.u = domain, int(index), (None if u is None else float(u))
+        self.matrix = None if matrix is None else matrix_tuple(matrix)
 
 
 def collate_raw(samples):
@@ -168,6 +179,7 @@ class MultiModalVolumeDataset(Dataset):
         path = _field(d, "divisors")
         self.divisors = json.loads(Path(path).read_text()) if path else {}
         self.raw = bool(_field(d, "device_transforms", False))
+        self.augmentation = parse_augmentation(_field(d, "augmentation"), fill_allowed=False)
 
     def __len__(self):
         return len(self.cases)
@@ -198,8 +210,13 @@ class MultiModalVolumeDataset(Dataset):
         v = v / self.divisor(name, index)
         return min_max_normalize(torch.clamp(v, lo, hi), lo, hi)
 
-    def crop(self, domain, index, mask, focal):
+    def crop(self, domain, index, mask, focal, matrix=None):
         start = [f - p // 2 for f, p in zip(focal, self.patch_size)]
+        if matrix is not None:              # mask, then interpolate (sample_patch), then the same chain
+            full = np.ones(self.patch_size, bool)
+            return torch.stack([self.normalize(n, index, sample_patch(self.load(n, index), mask, start, self.patch_size,
+                                                                      matrix, self.outside_value[n]), full)
+                                for n in self.modalities[domain]])
         win = tuple(slice(s, s + p) for s, p in zip(start, self.patch_size))
         m = mask[win]
         return torch.stack([self.normalize(n, index, self.load(n, index)[win], m) for n in self.modalities[domain]])
@@ -220,17 +237,27 @@ class MultiModalVolumeDataset(Dataset):
             raise self.empty_zone_error("B", index_B)
         return (focal_A, focal_B), flag
 
+    def draw_matrices(self):
+        """(M_A, M_B) after the sample's other draws: none without `augmentation`, one set of eight uniforms shared by A and
+        B when paired, A's set then B's set when unpaired"""
+        if self.augmentation is None:
+            return None, None
+        M_A = draw_params(self.augmentation)
+        return M_A, (M_A if self.paired else draw_params(self.augmentation))
+
     def __getitem__(self, index):
         index_A = index % len(self.cases)
         index_B = index_A if self.paired else random.randint(0, len(self.cases) - 1)
         if self.raw:
             u_A = np.random.random_sample()
             u_B = None if self.paired else np.random.random_sample()
-            return {"A": RawCase("A", index_A, u_A), "B": RawCase("B", index_B, u_B)}
+            M_A, M_B = self.draw_matrices()
+            return {"A": RawCase("A", index_A, u_A, M_A), "B": RawCase("B", index_B, u_B, M_B)}
         (focal_A, focal_B), _ = self.sample_points(index_A, index_B)
+        M_A, M_B = self.draw_matrices()
         mask_A = self.load(self.body_mask["A"], index_A)
         mask_B = mask_A if self.paired else self.load(self.body_mask["B"], index_B)
-        return {"A": self.crop("A", index_A, mask_A, focal_A), "B": self.crop("B", index_B, mask_B, focal_B)}
+        return {"A": self.crop("A", index_A, mask_A, focal_A, M_A), "B": self.crop("B", index_B, mask_B, focal_B, M_B)}
 
     # ---- picked up by build_loader / Trainer ----------------------------------------------------------------------
     @property

@@ -9,11 +9,15 @@ the channel axis. Their file readers are SimpleITK, which this image does not ha
 
 With `device_transforms: true` the volumes live in HBM (uploaded on first use and kept — a few hundred 36-MB volumes are
 nothing against 288 GB) and a sample is only ("A", index, start) coordinates: `DeviceVolumePipeline` crops and
-normalises on the GPU (csrc/volproc.hip) in front of `set_input`, through the same Trainer hook as the image pipeline."""
+normalises on the GPU (csrc/volproc.hip) in front of `set_input`, through the same Trainer hook as the image pipeline.
+
+`augmentation` (not in the reference; data/utils/patch_affine.py, 3-D patch sizes only) replaces the crop by one trilinear
+gather through a random 3 x 3 matrix per domain — flips, rotation, zoom, `fill` outside the volume — in front of the same
+z-score; the patch starts still come from `random`, the matrices from `np.random` (A's eight uniforms, then B's)."""
 import random
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Tuple
+from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -21,6 +25,7 @@ from torch.utils.data import Dataset
 
 from .. import configs
 from .utils.normalization import z_score_normalize
+from .utils.patch_affine import draw_params, matrix_tuple, parse_augmentation, sample_patch
 from .utils.stochastic_focal_patching import StochasticFocalPatchSampler
 
 EXTENSIONS = [".npy"]
@@ -33,14 +38,19 @@ class UnpairedVolumeDatasetConfig(configs.base.BaseDatasetConfig):
     focal_region_proportion: float = 0
     # not in the reference: volumes resident in HBM, crop + normalisation on the GPU (data/device_volumes.py)
     device_transforms: bool = False
+    # not in the reference: random flips / rotation / zoom of every patch as one trilinear gather (data/utils/
+    # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W], fill}
+    augmentation: Optional[Dict[str, Any]] = None
 
 
 class RawPatch:
-    """what a worker hands over with device_transforms on: which volume, and where the patch starts"""
-    __slots__ = ("domain", "index", "start")
+    """what a worker hands over with device_transforms on: which volume, where the patch starts, and its augmentation
+    matrix (9 floats, row-major) or None"""
+    __slots__ = ("domain", "index", "start", "matrix")
 
-    def __init__(self, domain, index, start):
+    def __init__(self, domain, index, start, matrix=None):
         self.domain, self.index, self.start = domain, int(index), tuple(int(v) for v in start)
+        self.matrix = None if matrix is None else matrix_tuple(matrix)
 
 
 def collate_raw(samples):
@@ -60,6 +70,13 @@ class UnpairedVolumeDataset(Dataset):
             self.raw = bool(d["device_transforms"])
         except (KeyError, AttributeError):
             self.raw = False
+        try:
+            node = d["augmentation"]
+        except (KeyError, AttributeError):
+            node = None
+        self.augmentation = parse_augmentation(node, fill_allowed=True)
+        if self.augmentation is not None and self.patch_sampler.dims != 3:
+            raise ValueError(f"augmentation needs a 3-D patch_size (D, H, W); got {[int(v) for v in self.patch_size]}")
         self._shapes = {}
 
     def load(self, domain, index):
@@ -77,11 +94,19 @@ class UnpairedVolumeDataset(Dataset):
     def __getitem__(self, index):
         index_A = index % len(self.paths["A"])
         index_B = random.randint(0, len(self.paths["B"]) - 1)
+        aug = self.augmentation
         if self.raw:
             start_A, start_B = self.patch_sampler.get_start_pair(self.shape("A", index_A), self.shape("B", index_B))
-            return {"A": RawPatch("A", index_A, start_A), "B": RawPatch("B", index_B, start_B)}
+            M_A, M_B = (draw_params(aug), draw_params(aug)) if aug else (None, None)       # A's set, then B's set
+            return {"A": RawPatch("A", index_A, start_A, M_A), "B": RawPatch("B", index_B, start_B, M_B)}
         A, B = self.load("A", index_A).float(), self.load("B", index_B).float()
-        A, B = self.patch_sampler.get_patch_pair(A, B)
+        if aug:
+            start_A, start_B = self.patch_sampler.get_start_pair(A.shape, B.shape)
+            size = [int(v) for v in self.patch_size]
+            A = torch.from_numpy(sample_patch(A.numpy(), None, start_A, size, draw_params(aug), aug.fill))
+            B = torch.from_numpy(sample_patch(B.numpy(), None, start_B, size, draw_params(aug), aug.fill))
+        else:
+            A, B = self.patch_sampler.get_patch_pair(A, B)
         A = z_score_normalize(A, scale_to_range=(-1, 1))
         B = z_score_normalize(B, scale_to_range=(-1, 1))
         return {"A": A.unsqueeze(0), "B": B.unsqueeze(0)}

@@ -1127,6 +1127,47 @@ class HipOps(TwinSplit):
                                               _ptr(point), fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
                 "gs_patch_clip_minmax")
 
+    @staticmethod
+    def _matrix(matrix):
+        m = [float(v) for row in matrix for v in (row if hasattr(row, "__len__") else [row])]
+        if len(m) != 9:
+            raise ValueError(f"matrix: expected 9 numbers (3 x 3, row-major); got {len(m)}")
+        return (C.c_double * 9)(*m)
+
+    def patch_affine_clip_minmax(self, volumes, mask, point, patch, matrix, outside, divisor, lo, hi, out):
+        """gs_patch_affine_clip_minmax: patch_clip_minmax through a 3 x 3 matrix — the trilinear gather of
+        data/utils/patch_affine.py (mask, then interpolate), then the same chain. matrix: 9 numbers, row-major, or 3 x 3."""
+        n = len(volumes)
+        if n < 1:
+            raise ValueError("patch_affine_clip_minmax: at least one volume")
+        self._case_volume("mask", mask, (torch.uint8,))
+        for i, v in enumerate(volumes):
+            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        self._point("point", point, 3)
+        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
+            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == (n, *[int(v) for v in patch])):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *[int(v) for v in patch])}")
+        fl = lambda vals: (C.c_float * n)(*[float(v) for v in vals])
+        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in volumes])
+        dts = (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes])
+        L.check(self.lib.gs_patch_affine_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, _ptr(point),
+                                                     (C.c_int32 * 3)(*[int(v) for v in patch]), self._matrix(matrix),
+                                                     fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
+                "gs_patch_affine_clip_minmax")
+
+    def patch_affine(self, volume, start, size, matrix, fill, out):
+        """gs_patch_affine: out (d, h, w) fp32 = the raw trilinear gather of the window [start, start + size) of a dense
+        (D, H, W) fp32 / int16 device volume through `matrix`, `fill` outside the volume; no mask, no normalisation"""
+        self._case_volume("volume", volume, tuple(self.VOL_DTYPES))
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == tuple(int(v) for v in size)):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {tuple(int(v) for v in size)}")
+        st, sz = (C.c_int32 * 3)(*[int(v) for v in start]), (C.c_int32 * 3)(*[int(v) for v in size])
+        L.check(self.lib.gs_patch_affine(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
+                                         self._matrix(matrix), float(fill), _ptr(out), _stream()), "gs_patch_affine")
+
     def volume_prepare(self, volumes, mask, extra_masks, target, outside, divisor, lo, hi, out=None, masks_out=None):
         """gs_volume_prepare: one whole case for the val / test engines -> (out, [masks]). volumes: C fp32 / int16
         (D, H, W) device tensors; mask: the body mask (uint8, non-zero = inside); extra_masks: up to VM_MAX_LABELS further

@@ -578,6 +578,44 @@ int gs_voxel_draw(const uint8_t* mask, const void* weight, int32_t wdtype, int32
 int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask, int32_t D,
                          int32_t H, int32_t W, const int32_t* patch, const int32_t* point, const float* outside,
                          const float* divisor, const float* lo, const float* hi, float* out, void* stream);
+/* Random affine augmentation of a training patch: one trilinear gather through a 3 x 3 matrix, in the launch that crops.
+ * THE DEFINITION (data/utils/patch_affine.py states it in numpy, tests/patch_affine_ref.py as a per-voxel loop). For a
+ * dense volume of size (D, H, W), a patch p = (d, h, w) starting at `start`, and M (host double[9], row-major, maps patch
+ * offsets to source offsets; data/utils/patch_affine.py affine_matrix builds it from flips, angles, zoom and spacing):
+ *   c_a = (p_a - 1) / 2                                                               float64, exact
+ *   r = o - c for output voxel o                                                      float64, exact
+ *   s_a = ((M[a][0] r_0 + M[a][1] r_1) + M[a][2] r_2) + (start_a + c_a)               float64, one IEEE operation per step,
+ *                                                                                     no fused multiply-add
+ *   i_a = floor(s_a), t_a = (float)(s_a - i_a)
+ *   if any s_a < -1 or s_a >= size_a (float64, before any integer conversion; a NaN s_a counts as such): all eight
+ *   corners are outside
+ *   corner (i_0 + dz, i_1 + dy, i_2 + dx) has the value (float)vol[corner] when it lies inside the volume and, with a
+ *   mask, mask[corner] != 0; otherwise the `outside` value (mask, then interpolate: continuous, no nearest-neighbour
+ *   rounding)
+ *   lerp(a, b, t) = a + t * (b - a) in float32: sub, mul, add, each rounded; along W first (c00, c01, c10, c11), then
+ *   along H, then along D
+ * M = I gives the plain crop, M = diag(+-1) the flipped crop, a signed permutation matrix on a patch with equal sides in
+ * the rotated plane np.rot90 of the crop — as equal numbers (a zero may come out with the other sign: an upper corner of
+ * weight 0 still enters as 0 * (b - a)).
+ *
+ * gs_patch_affine_clip_minmax: the gather, then the per-voxel chain of gs_patch_clip_minmax unchanged (/ divisor, clamp,
+ * min-max to [-1, 1]) for all C (1..GS_PATCH_MAX_MODALITIES) modalities of one case. Arguments as gs_patch_clip_minmax
+ * (point: DEVICE int32[3]; start = point - floor(patch / 2) clamped to [0, size - patch]) plus M. out: dense
+ * [C, d, h, w] fp32, every element written exactly once.
+ * gs_patch_affine: the raw gather of one volume, no mask, no normalisation, `fill` outside the volume; start / size: host
+ * int32[3], the window inside the volume as for gs_patch_zscore. out: [d, h, w] fp32 — a dense patch that
+ * gs_patch_zscore then takes as a volume of its own with start 0 (UnpairedVolumeDataset's z-score follows the gather).
+ * One thread per output voxel, W fastest: coordinates, in-bounds tests and the eight mask bytes once per voxel, the
+ * modalities looped inside the thread. M and the per-modality constants travel in the kernel argument. No atomics, no
+ * workspace, no host synchronisation. Null pointers, C out of range, non-positive sizes, a patch larger than the volume
+ * on any axis (or, for gs_patch_affine, a window that leaves it), an unknown dtype, a non-finite entry of M, lo >= hi and
+ * a zero or NaN divisor are refused before any launch. */
+int gs_patch_affine_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask, int32_t D,
+                                int32_t H, int32_t W, const int32_t* point, const int32_t* patch, const double* M,
+                                const float* outside, const float* divisor, const float* lo, const float* hi, float* out,
+                                void* stream);
+int gs_patch_affine(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                    const int32_t* size, const double* M, float fill, float* out, void* stream);
 /* gs_volume_prepare: one whole case for the val / test engines (the reference's val_test_dataset.py:136-161): body
  * masking, centred padding to a target shape and the per-voxel chain of gs_patch_clip_minmax, for all C
  * (1..GS_PATCH_MAX_MODALITIES) volumes and M (1..1 + GS_VM_MAX_LABELS) byte masks of a D x H x W case. masks[0] is the

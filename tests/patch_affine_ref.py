@@ -1,0 +1,134 @@
+"""CPU reference of the affine patch gather (gs_patch_affine_clip_minmax / gs_patch_affine, csrc/volsample.hip; host path
+ganslate_amd/data/utils/patch_affine.py), restated from the definition in include/ganslate_hip.h as a plain per-voxel loop:
+Python floats for the float64 steps (IEEE doubles, one rounding per operation, no fused multiply-add), numpy float32
+scalars for the float32 steps. Nothing here calls the package's sampling code or the kernels. `RefAffineOps` carries
+HipOps' signatures, so the device pipelines run their control flow on CPU tensors (tests/mmvol_ref.py RefMMOps for the
+draw and the plain crop, the op-level oracle for the z-score that follows the raw gather)."""
+import math
+
+import numpy as np
+import torch
+
+from tests.mmvol_ref import RefMMOps
+
+F = np.float32
+
+
+def start_of(point, patch, size):
+    """gs_patch_clip_minmax's start rule: point - floor(patch / 2), clamped to [0, size - patch]"""
+    return [min(max(int(point[a]) - patch[a] // 2, 0), size[a] - patch[a]) for a in range(3)]
+
+
+def coords(size, patch, start, M):
+    """per output voxel in C order: (reach, (i_0, i_1, i_2), (t_0, t_1, t_2)) — independent of the volume's values"""
+    M = [[float(M[a][b]) for b in range(3)] for a in range(3)]
+    c = [(patch[a] - 1) / 2.0 for a in range(3)]
+    base = [float(start[a]) + c[a] for a in range(3)]
+    rows = []
+    for oz in range(patch[0]):
+        for oy in range(patch[1]):
+            for ox in range(patch[2]):
+                r = (oz - c[0], oy - c[1], ox - c[2])
+                reach, idx, t = True, [], []
+                for a in range(3):
+                    p0 = M[a][0] * r[0]
+                    p1 = M[a][1] * r[1]
+                    p2 = M[a][2] * r[2]
+                    s = ((p0 + p1) + p2) + base[a]
+                    if not (s >= -1.0 and s < float(size[a])):         # NaN included
+                        reach = False
+                        idx.append(0)
+                        t.append(F(s - math.floor(s)) if math.isfinite(s) else F(np.nan))
+                        continue
+                    fl = math.floor(s)
+                    idx.append(int(fl))
+                    t.append(F(s - fl))
+                rows.append((reach, idx, t))
+    return rows
+
+
+def lerp(a, b, t):
+    d = F(b - a)
+    p = F(t * d)
+    return F(a + p)
+
+
+def gather(volumes, mask, start, patch, M, outside):
+    """[C, d, h, w] float32: mask, then interpolate; the coordinates once per voxel, the modalities inside"""
+    size = volumes[0].shape
+    out = np.empty((len(volumes), patch[0] * patch[1] * patch[2]), np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for n, (reach, (z, y, x), t) in enumerate(coords(size, patch, start, M)):
+            ok = []
+            for dz in (0, 1):
+                for dy in (0, 1):
+                    for dx in (0, 1):
+                        zz, yy, xx = z + dz, y + dy, x + dx
+                        inside = reach and 0 <= zz < size[0] and 0 <= yy < size[1] and 0 <= xx < size[2]
+                        if inside and mask is not None:
+                            inside = mask[zz, yy, xx] != 0
+                        ok.append((zz, yy, xx) if inside else None)
+            for c, vol in enumerate(volumes):
+                v = [F(outside[c]) if at is None else F(vol[at]) for at in ok]
+                c00, c01 = lerp(v[0], v[1], t[2]), lerp(v[2], v[3], t[2])
+                c10, c11 = lerp(v[4], v[5], t[2]), lerp(v[6], v[7], t[2])
+                out[c, n] = lerp(lerp(c00, c01, t[1]), lerp(c10, c11, t[1]), t[0])
+    return out.reshape(len(volumes), *patch)
+
+
+def clip_minmax(v, divisor, lo, hi):
+    """the five fp32 operations behind the mask of gs_patch_clip_minmax, one numpy operation each (tests/mmvol_ref.py)"""
+    v = v / F(divisor)
+    v = np.minimum(np.maximum(v, F(lo)), F(hi))
+    v = (v - F(lo)) / (F(hi) - F(lo))
+    v = F(2) * v - F(1)
+    assert v.dtype == np.float32
+    return v
+
+
+def patch_affine_clip_minmax(volumes, mask, point, patch, M, outside, divisor, lo, hi):
+    patch = [int(p) for p in patch]
+    g = gather(volumes, mask, start_of(point, patch, mask.shape), patch, M, outside)
+    return np.stack([clip_minmax(g[c], divisor[c], lo[c], hi[c]) for c in range(len(volumes))])
+
+
+def patch_affine(volume, start, size, M, fill):
+    return gather([volume], None, [int(v) for v in start], [int(v) for v in size], M, [fill])[0]
+
+
+def rot90_matrix(axis, k=1):
+    """the signed permutation matrix of k quarter turns in the plane of the other two axes"""
+    i, j = [a for a in range(3) if a != axis]
+    Q = np.eye(3)
+    Q[i, i], Q[i, j], Q[j, i], Q[j, j] = 0.0, -1.0, 1.0, 0.0
+    return np.linalg.matrix_power(Q, k)
+
+
+def rot_zoom_matrix(deg=30.0, zoom=1.1, axis=0):
+    """rotation by `deg` about `axis` times a source step of `zoom` (the issue's 30 degrees x 1.1)"""
+    th = math.radians(deg)
+    i, j = [a for a in range(3) if a != axis]
+    Q = np.eye(3)
+    Q[i, i], Q[i, j], Q[j, i], Q[j, j] = math.cos(th), -math.sin(th), math.sin(th), math.cos(th)
+    return Q * zoom
+
+
+SHEAR = np.array([[0.9, 0.15, -0.05], [-0.2, 1.2, 0.3], [0.1, -0.25, 0.8]])      # general, anisotropic, sheared
+FLIPS = [np.diag([sz, sy, sx]) for sz in (1.0, -1.0) for sy in (1.0, -1.0) for sx in (1.0, -1.0)]
+
+
+class RefAffineOps(RefMMOps):
+    """the two affine ops (and the z-score that follows the raw gather) on CPU tensors, with HipOps' signatures"""
+
+    def patch_affine_clip_minmax(self, volumes, mask, point, patch, matrix, outside, divisor, lo, hi, out):
+        M = np.asarray(matrix, dtype=np.float64).reshape(3, 3)
+        out.copy_(torch.from_numpy(patch_affine_clip_minmax([v.numpy() for v in volumes], mask.numpy(),
+                                                            [int(v) for v in point[:3]], patch, M, outside, divisor, lo, hi)))
+
+    def patch_affine(self, volume, start, size, matrix, fill, out):
+        M = np.asarray(matrix, dtype=np.float64).reshape(3, 3)
+        out.copy_(torch.from_numpy(patch_affine(volume.numpy(), start, size, M, fill)))
+
+    def patch_zscore(self, volume, start, size, out, scale_to_range=(-1.0, 1.0)):
+        from oracle.ops_ref import RefOps
+        RefOps().patch_zscore(volume, start, size, out, scale_to_range)
