@@ -270,7 +270,9 @@ __device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v,
   X(PWISE, "pwise", 8)                         /* pwise.hip: register-operand kernels for one-tap layers with <= 8 channels on one side (smallest volume in 2048-voxel units, 0 = off) */ \
   X(DAXIS, "daxis", 8192)                         /* daxis.hip: streaming kernel for layers whose taps all lie on the row axis, 8..64 channels (the (k,1,1) half of a */ \
                                                /* separable volume conv and its data gradient): smallest launch in 64-voxel units (default: 2^19 voxels, where it measured */ \
-                                               /* 2.9 x the other kernels; a tie at 2^18 voxels x 32 channels, a loss at 2^15 x 64: DESIGN.md 4.6), 0 = off */
+                                               /* 2.9 x the other kernels; a tie at 2^18 voxels x 32 channels, a loss at 2^15 x 64: DESIGN.md 4.6), 0 = off */ \
+  X(ELASTIC_ROWS, "elastic_rows", 32768)       /* volsample.hip: largest per-workgroup row table (bytes of LDS, at most 65536) with which the elastic gather runs */ \
+                                               /* its row-shared form; beyond it, and with 0 always, the per-voxel form (tests and the timing tool force it) */
 enum GsOpt {
 #define GS_OPT_ENUM(id, name, def) GS_OPT_##id,
   GS_OPTIONS(GS_OPT_ENUM)

@@ -29,6 +29,8 @@
 // utils/patch_affine.py): per output voxel float64 source coordinates round the patch centre, the eight corners masked and
 // bounds-checked one by one, three rounded-step fp32 lerps (W, H, D), then the same chain (or none, for the raw gather that
 // feeds gs_patch_zscore). One thread per voxel, the modalities looped inside it; no contraction anywhere in the definition.
+// gs_patch_elastic_clip_minmax / gs_patch_elastic — the same kernel with a free-form deformation (a lattice of control-point
+// displacements, cubic B-splines) added to the patch offset in front of the matrix: a compile-time variant of that kernel.
 //
 // gs_volume_prepare — a whole case for the val / test engines (data/multimodal_valtest.py): the same mask step and the same
 // per-voxel chain (one device function, clip_minmax), with centred padding up to a target shape in between; the pad value is
@@ -353,9 +355,128 @@ __device__ __forceinline__ float lerp_rn(float a, float b, float t) {
   return a + p;
 }
 
-template <bool CLIP>
-__global__ __launch_bounds__(256) void patch_affine_kernel(const AffK k, float* out) {
+// ---- the elastic variant (gs_patch_elastic_clip_minmax / gs_patch_elastic) ---------------------------------------------
+// A free-form deformation in front of the matrix (ganslate_hip.h states the definition): r'_a = r_a + u_a(o), u the cubic
+// B-spline interpolation of a coarse lattice of displacements that spans the patch. The lattice (up to 24 KB of float64)
+// arrives as a device buffer. Two forms, the same bits by construction (the definition sums D innermost, W outermost, so
+// R[a][n] of a lattice column is a function of the output row (o_0, o_1) alone):
+//   ELA_ROWS   a workgroup's 256 consecutive voxels cover at most 255 / w + 2 rows; its threads compute R[row][a][k] for
+//              every lattice column k of those rows once, from the lattice through L2, into LDS (rows * 3 * G_2 doubles);
+//              a voxel then takes its W weights and 4 multiplies per component. Used when that table fits the option
+//              elastic_rows (32 KB).
+//   ELA_VOXEL  the lattice staged to LDS per workgroup, all 64 + 16 + 4 products per component in every thread: for short
+//              rows under a wide lattice, whose row table would not fit.
+struct ElaK : AffK {
+  const double* field;             // DEVICE double[3][G0][G1][G2], voxels
+  int G[3];
+};
+
+enum { ELA_NONE = 0, ELA_VOXEL = 1, ELA_ROWS = 2 };
+
+// the interval j and the four uniform cubic B-spline weights of output index o on an axis of p voxels over G control
+// points: f = (o (G - 3) - j (p - 1)) / (p - 1), one correctly rounded division of two exact integers
+__device__ __forceinline__ int bspline_axis(int o, int p, int G, double B[4]) {
+#pragma clang fp contract(off)
+  const int num = o * (G - 3), den = p - 1;              // the host refused (p - 1) (G - 3) > INT_MAX
+  int j = num / den;
+  j = j > G - 4 ? G - 4 : j;
+  const double f = __ddiv_rn((double)(num - j * den), (double)den);
+  const double f2 = f * f;
+  const double f3 = f2 * f;
+  const double g = 1.0 - f;
+  const double gg = g * g;
+  const double t1 = 3.0 * f3;
+  const double t2 = 6.0 * f2;
+  const double t3 = 3.0 * f2;
+  const double t4 = 3.0 * f;
+  B[0] = __ddiv_rn(gg * g, 6.0);
+  B[1] = __ddiv_rn((t1 - t2) + 4.0, 6.0);
+  B[2] = __ddiv_rn(((t3 - t1) + t4) + 1.0, 6.0);
+  B[3] = __ddiv_rn(f3, 6.0);
+  return j;
+}
+
+__device__ __forceinline__ double dot4(const double B[4], double a0, double a1, double a2, double a3) {
+#pragma clang fp contract(off)
+  const double p0 = B[0] * a0;
+  const double p1 = B[1] * a1;
+  const double p2 = B[2] * a2;
+  const double p3 = B[3] * a3;
+  const double s1 = p0 + p1;
+  const double s2 = s1 + p2;
+  return s2 + p3;
+}
+
+// R of one lattice column: D innermost (Bz), then H (By). F: one component of the lattice at (j0, j1, column), in LDS or
+// in global memory
+__device__ __forceinline__ double lattice_R(const double* F, int G1, int G2, const double Bz[4], const double By[4]) {
+  double q[4];
+  const int sz = G1 * G2;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) q[m] = dot4(Bz, F[m * G2], F[sz + m * G2], F[2 * sz + m * G2], F[3 * sz + m * G2]);
+  return dot4(By, q[0], q[1], q[2], q[3]);
+}
+
+// cooperative part, every thread of the workgroup: fills the LDS of its form and synchronises
+template <int E>
+__device__ __forceinline__ void elastic_stage(const ElaK& k, double* lds) {
+  const int GN = k.G[0] * k.G[1] * k.G[2];
+  if constexpr (E == ELA_VOXEL) {
+    for (int e = threadIdx.x; e < 3 * GN; e += 256) lds[e] = k.field[e];
+  } else {
+    const long long first = (long long)blockIdx.x * 256;
+    long long last = first + 255;
+    last = last < k.n ? last : k.n - 1;
+    const long long row0 = first / k.pw;
+    const int rows = (int)(last / k.pw - row0) + 1;        // <= min(d h, 255 / w + 2), what the host sized the table for
+    const int per = 3 * k.G[2];
+    for (int e = threadIdx.x; e < rows * per; e += 256) {
+      const int rl = e / per, a = (e % per) / k.G[2], col = e % k.G[2];
+      const long long row = row0 + rl;
+      double Bz[4], By[4];
+      const int j0 = bspline_axis((int)(row / k.ph), k.pd, k.G[0], Bz);
+      const int j1 = bspline_axis((int)(row % k.ph), k.ph, k.G[1], By);
+      lds[e] = lattice_R(k.field + (long long)a * GN + (j0 * k.G[1] + j1) * k.G[2] + col, k.G[1], k.G[2], Bz, By);
+    }
+  }
+  __syncthreads();
+}
+
+// u_a of output voxel o, added to r_a: one float64 add per axis
+template <int E>
+__device__ __forceinline__ void elastic_displace(const ElaK& k, const double* lds, const int o[3], long long i, double r[3]) {
+#pragma clang fp contract(off)
+  double Bx[4];
+  const int j2 = bspline_axis(o[2], k.pw, k.G[2], Bx);
+  double u[3];
+  if constexpr (E == ELA_VOXEL) {
+    const int GN = k.G[0] * k.G[1] * k.G[2];
+    double Bz[4], By[4];
+    const int j0 = bspline_axis(o[0], k.pd, k.G[0], Bz);
+    const int j1 = bspline_axis(o[1], k.ph, k.G[1], By);
+    const double* F = lds + (j0 * k.G[1] + j1) * k.G[2] + j2;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double R[4];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) R[n] = lattice_R(F + a * GN + n, k.G[1], k.G[2], Bz, By);
+      u[a] = dot4(Bx, R[0], R[1], R[2], R[3]);
+    }
+  } else {
+    const int rl = (int)(i / k.pw - ((long long)blockIdx.x * 256) / k.pw);
+    const double* R = lds + rl * 3 * k.G[2] + j2;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) u[a] = dot4(Bx, R[a * k.G[2]], R[a * k.G[2] + 1], R[a * k.G[2] + 2], R[a * k.G[2] + 3]);
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) r[a] = r[a] + u[a];
+}
+
+template <bool CLIP, int E, typename K>
+__global__ __launch_bounds__(256) void patch_affine_kernel(const K k, float* out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double ela_lds[];
+  if constexpr (E != ELA_NONE) elastic_stage<E>(k, ela_lds);
   if (i >= k.n) return;
   const int size[3] = {k.D, k.H, k.W}, patch[3] = {k.pd, k.ph, k.pw};
   int o[3];
@@ -377,6 +498,7 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const AffK k, float* 
     r[a] = (double)o[a] - c;                             // exact
     base[a] = (double)s + c;                             // exact
   }
+  if constexpr (E != ELA_NONE) elastic_displace<E>(k, ela_lds, o, i, r);
   int ix[3];
   float t[3];
   bool reach = true;                                     // false: all eight corners are outside
@@ -388,6 +510,9 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const AffK k, float* 
     const bool in = s >= -1.0 && s < (double)size[a];    // NaN: outside
     reach = reach && in;
     ix[a] = in ? (int)f : 0;                             // in [-1, size - 1]
+    // a NaN or infinite displacement: s - floor(s) is no number. The corners are all `outside` then, which any finite t
+    // lerps to `outside` itself, so 0 changes no finite case
+    if constexpr (E != ELA_NONE) t[a] = in ? t[a] : 0.f;
   }
   // off[q], q = dz * 4 + dy * 2 + dx: where corner q is read. A corner that takes the outside value reads voxel 0 instead
   // (there always is one) and drops it: every load is unconditional, so the eight of a stage are in flight together
@@ -440,16 +565,53 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const AffK k, float* 
   }
 }
 
-int launch_affine(AffK& k, const int32_t* patch, const double* M, float* out, bool clip, void* stream) {
+// grid (nullptr: no elastic part) and field: the lattice of gs_patch_elastic*, checked by the caller
+int launch_affine(AffK& k, const int32_t* patch, const double* M, const int32_t* grid, const double* field, float* out,
+                  bool clip, void* stream) {
   for (int j = 0; j < 9; ++j) k.M[j] = M[j];
   k.pd = patch[0]; k.ph = patch[1]; k.pw = patch[2];
   k.n = (long long)patch[0] * patch[1] * patch[2];
   const long long blocks = (k.n + 255) / 256;            // one voxel per thread
   GS_REQUIRE(blocks <= 0x7fffffffLL, "gs_patch_affine: %lld voxels do not fit one grid", k.n);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (clip) hipLaunchKernelGGL(patch_affine_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, k, out);
-  else hipLaunchKernelGGL(patch_affine_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, k, out);
+  const dim3 g((unsigned)blocks), b(256);
+  if (!grid) {
+    if (clip) hipLaunchKernelGGL((patch_affine_kernel<true, ELA_NONE, AffK>), g, b, 0, st, k, out);
+    else hipLaunchKernelGGL((patch_affine_kernel<false, ELA_NONE, AffK>), g, b, 0, st, k, out);
+  } else {
+    ElaK e;
+    static_cast<AffK&>(e) = k;
+    e.field = field;
+    e.G[0] = grid[0]; e.G[1] = grid[1]; e.G[2] = grid[2];
+    const long long rows_all = (long long)patch[0] * patch[1], rows_wg = 255 / patch[2] + 2;
+    const size_t table = (size_t)(rows_all < rows_wg ? rows_all : rows_wg) * 3 * grid[2] * sizeof(double);
+    int fits = gs_opt(GS_OPT_ELASTIC_ROWS);
+    fits = fits < 0 ? 0 : (fits > 65536 ? 65536 : fits);
+    if (table <= (size_t)fits) {
+      if (clip) hipLaunchKernelGGL((patch_affine_kernel<true, ELA_ROWS, ElaK>), g, b, table, st, e, out);
+      else hipLaunchKernelGGL((patch_affine_kernel<false, ELA_ROWS, ElaK>), g, b, table, st, e, out);
+    } else {
+      const size_t lattice = (size_t)3 * grid[0] * grid[1] * grid[2] * sizeof(double);
+      if (clip) hipLaunchKernelGGL((patch_affine_kernel<true, ELA_VOXEL, ElaK>), g, b, lattice, st, e, out);
+      else hipLaunchKernelGGL((patch_affine_kernel<false, ELA_VOXEL, ElaK>), g, b, lattice, st, e, out);
+    }
+  }
   GS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// what the elastic entries refuse on top of the affine ones
+int check_lattice(const char* who, const int32_t* patch, const int32_t* grid, const double* field) {
+  GS_REQUIRE(grid && field, "%s: null grid or field", who);
+  GS_REQUIRE(grid[0] >= 4 && grid[1] >= 4 && grid[2] >= 4, "%s: the lattice needs at least 4 control points per axis; got %d x %d x %d",
+             who, grid[0], grid[1], grid[2]);
+  GS_REQUIRE((long long)grid[0] * grid[1] * grid[2] <= GS_ELASTIC_MAX_POINTS,
+             "%s: a lattice of %d x %d x %d control points exceeds %d", who, grid[0], grid[1], grid[2], GS_ELASTIC_MAX_POINTS);
+  GS_REQUIRE(patch[0] >= 2 && patch[1] >= 2 && patch[2] >= 2, "%s: an elastic patch needs at least 2 voxels per axis; got %d x %d x %d",
+             who, patch[0], patch[1], patch[2]);
+  for (int a = 0; a < 3; ++a)
+    GS_REQUIRE((long long)(patch[a] - 1) * (grid[a] - 3) <= 0x7fffffffLL, "%s: patch axis %d of %d voxels is too long for %d "
+               "control points", who, a, patch[a], grid[a]);
   return 0;
 }
 
@@ -627,27 +789,26 @@ extern "C" int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtyp
   return 0;
 }
 
-extern "C" int gs_patch_affine_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
-                                           int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch,
-                                           const double* M, const float* outside, const float* divisor, const float* lo,
-                                           const float* hi, float* out, void* stream) {
-  GS_REQUIRE(vols && dtypes && mask && point && patch && M && outside && divisor && lo && hi && out,
-             "gs_patch_affine_clip_minmax: null argument");
-  GS_REQUIRE(C >= 1 && C <= PC_MAX, "gs_patch_affine_clip_minmax: between 1 and %d modalities per call; got %d", PC_MAX, C);
+namespace {
+// the bodies of the affine and the elastic entry points: grid == nullptr is the affine one, `who` names the entry in messages
+int gather_clip_minmax(const char* who, const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
+                       int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch, const double* M,
+                       const int32_t* grid, const double* field, const float* outside, const float* divisor, const float* lo,
+                       const float* hi, float* out, void* stream) {
+  GS_REQUIRE(vols && dtypes && mask && point && patch && M && outside && divisor && lo && hi && out, "%s: null argument", who);
+  GS_REQUIRE(C >= 1 && C <= PC_MAX, "%s: between 1 and %d modalities per call; got %d", who, PC_MAX, C);
   GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
                  patch[2] <= W,
-             "gs_patch_affine_clip_minmax: patch %d x %d x %d does not fit the %d x %d x %d volume", patch[0], patch[1],
-             patch[2], D, H, W);
-  GS_REQUIRE(finite9(M), "gs_patch_affine_clip_minmax: the matrix has a non-finite entry");
+             "%s: patch %d x %d x %d does not fit the %d x %d x %d volume", who, patch[0], patch[1], patch[2], D, H, W);
+  GS_REQUIRE(finite9(M), "%s: the matrix has a non-finite entry", who);
   AffK k;
   for (int c = 0; c < PC_MAX; ++c) {
     const int s = c < C ? c : 0;
-    GS_REQUIRE(vols[s], "gs_patch_affine_clip_minmax: null volume %d", s);
-    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16,
-               "gs_patch_affine_clip_minmax: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", dtypes[s], s);
-    GS_REQUIRE(hi[s] > lo[s], "gs_patch_affine_clip_minmax: clip range [%g, %g] of volume %d is empty", lo[s], hi[s], s);
-    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "gs_patch_affine_clip_minmax: divisor %g of volume %d",
-               divisor[s], s);
+    GS_REQUIRE(vols[s], "%s: null volume %d", who, s);
+    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16, "%s: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", who,
+               dtypes[s], s);
+    GS_REQUIRE(hi[s] > lo[s], "%s: clip range [%g, %g] of volume %d is empty", who, lo[s], hi[s], s);
+    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "%s: divisor %g of volume %d", who, divisor[s], s);
     k.vol[c] = vols[s];
     k.dtype[c] = dtypes[s];
     k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
@@ -656,21 +817,22 @@ extern "C" int gs_patch_affine_clip_minmax(const void* const* vols, const int32_
   k.point = point;
   k.start[0] = k.start[1] = k.start[2] = 0;
   k.C = C; k.D = D; k.H = H; k.W = W;
-  return launch_affine(k, patch, M, out, true, stream);
+  return launch_affine(k, patch, M, grid, field, out, true, stream);
 }
 
-extern "C" int gs_patch_affine(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
-                               const int32_t* size, const double* M, float fill, float* out, void* stream) {
-  GS_REQUIRE(vol && start && size && M && out, "gs_patch_affine: null argument");
-  GS_REQUIRE(dtype == GS_VOL_F32 || dtype == GS_VOL_I16, "gs_patch_affine: dtype %d (GS_VOL_F32 / GS_VOL_I16)", dtype);
+int gather_raw(const char* who, const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+               const int32_t* size, const double* M, const int32_t* grid, const double* field, float fill, float* out,
+               void* stream) {
+  GS_REQUIRE(vol && start && size && M && out, "%s: null argument", who);
+  GS_REQUIRE(dtype == GS_VOL_F32 || dtype == GS_VOL_I16, "%s: dtype %d (GS_VOL_F32 / GS_VOL_I16)", who, dtype);
   GS_REQUIRE(D > 0 && H > 0 && W > 0 && size[0] > 0 && size[1] > 0 && size[2] > 0 && size[0] <= D && size[1] <= H &&
                  size[2] <= W,
-             "gs_patch_affine: patch %d x %d x %d does not fit the %d x %d x %d volume", size[0], size[1], size[2], D, H, W);
+             "%s: patch %d x %d x %d does not fit the %d x %d x %d volume", who, size[0], size[1], size[2], D, H, W);
   GS_REQUIRE(start[0] >= 0 && start[1] >= 0 && start[2] >= 0 && start[0] <= D - size[0] && start[1] <= H - size[1] &&
                  start[2] <= W - size[2],
-             "gs_patch_affine: patch [%d+%d, %d+%d, %d+%d] outside the %d x %d x %d volume", start[0], size[0], start[1],
-             size[1], start[2], size[2], D, H, W);
-  GS_REQUIRE(finite9(M), "gs_patch_affine: the matrix has a non-finite entry");
+             "%s: patch [%d+%d, %d+%d, %d+%d] outside the %d x %d x %d volume", who, start[0], size[0], start[1], size[1],
+             start[2], size[2], D, H, W);
+  GS_REQUIRE(finite9(M), "%s: the matrix has a non-finite entry", who);
   AffK k;
   for (int c = 0; c < PC_MAX; ++c) {
     k.vol[c] = vol;
@@ -681,7 +843,39 @@ extern "C" int gs_patch_affine(const void* vol, int32_t dtype, int32_t D, int32_
   k.point = nullptr;
   k.start[0] = start[0]; k.start[1] = start[1]; k.start[2] = start[2];
   k.C = 1; k.D = D; k.H = H; k.W = W;
-  return launch_affine(k, size, M, out, false, stream);
+  return launch_affine(k, size, M, grid, field, out, false, stream);
+}
+}  // namespace
+
+extern "C" int gs_patch_affine_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
+                                           int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch,
+                                           const double* M, const float* outside, const float* divisor, const float* lo,
+                                           const float* hi, float* out, void* stream) {
+  return gather_clip_minmax("gs_patch_affine_clip_minmax", vols, dtypes, C, mask, D, H, W, point, patch, M, nullptr, nullptr,
+                            outside, divisor, lo, hi, out, stream);
+}
+
+extern "C" int gs_patch_affine(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                               const int32_t* size, const double* M, float fill, float* out, void* stream) {
+  return gather_raw("gs_patch_affine", vol, dtype, D, H, W, start, size, M, nullptr, nullptr, fill, out, stream);
+}
+
+extern "C" int gs_patch_elastic_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
+                                            int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch,
+                                            const double* M, const int32_t* grid, const double* field, const float* outside,
+                                            const float* divisor, const float* lo, const float* hi, float* out, void* stream) {
+  GS_REQUIRE(patch, "gs_patch_elastic_clip_minmax: null argument");
+  if (const int rc = check_lattice("gs_patch_elastic_clip_minmax", patch, grid, field)) return rc;
+  return gather_clip_minmax("gs_patch_elastic_clip_minmax", vols, dtypes, C, mask, D, H, W, point, patch, M, grid, field,
+                            outside, divisor, lo, hi, out, stream);
+}
+
+extern "C" int gs_patch_elastic(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                                const int32_t* size, const double* M, const int32_t* grid, const double* field, float fill,
+                                float* out, void* stream) {
+  GS_REQUIRE(size, "gs_patch_elastic: null argument");
+  if (const int rc = check_lattice("gs_patch_elastic", size, grid, field)) return rc;
+  return gather_raw("gs_patch_elastic", vol, dtype, D, H, W, start, size, M, grid, field, fill, out, stream);
 }
 
 extern "C" int64_t gs_volume_prepare_ws_bytes(void) { return (int64_t)(PC_MAX + VP_MAX_MASKS) * VP_PARTS * 4; }

@@ -3,9 +3,23 @@ iteration only patch coordinates arrive from the loader (data/volume_datasets.py
 scaling run as gs_patch_zscore (csrc/volproc.hip) and write straight into the fp32 [N, 1, d, h, w] batch `set_input`
 takes. Reference path being replaced: projects/brats_mri_sequence_translation/datasets/train_dataset.py:83-92.
 With `augmentation` a sample also carries a 3 x 3 matrix: gs_patch_affine (csrc/volsample.hip) gathers the patch through
-it into a scratch patch, and gs_patch_zscore normalises that as a volume of its own."""
+it into a scratch patch, and gs_patch_zscore normalises that as a volume of its own. A sample that also carries an elastic
+field takes gs_patch_elastic there; the fields of a batch are uploaded in one copy."""
 import numpy as np
 import torch
+
+
+def upload_fields(items, device):
+    """{id(field): float64 device tensor [3, G0, G1, G2]} of every elastic field the raw samples carry: one host array, one
+    copy. A field shared by two samples (a paired one) travels once."""
+    fields = {}
+    for r in items:
+        if getattr(r, "field", None) is not None:
+            fields.setdefault(id(r.field), r.field)
+    if not fields:
+        return {}
+    dev = torch.from_numpy(np.stack([np.asarray(f, dtype=np.float64) for f in fields.values()])).to(device)
+    return {key: dev[n] for n, key in enumerate(fields)}
 
 
 class DeviceVolumePipeline:
@@ -44,6 +58,8 @@ class DeviceVolumePipeline:
     def __call__(self, batch):
         from .volume_datasets import RawPatch
         out = {}
+        fields = upload_fields([r for items in batch.values() if items and isinstance(items[0], RawPatch) for r in items],
+                               self.device)
         for key, items in batch.items():
             if not items or not isinstance(items[0], RawPatch):
                 out[key] = items
@@ -55,8 +71,12 @@ class DeviceVolumePipeline:
                     continue
                 # augmented: the raw gather into a dense patch, which patch_zscore then takes as a volume of its own
                 raw = torch.empty(tuple(self.size), dtype=torch.float32, device=self.device)
-                self.ops.patch_affine(self.volume(r.domain, r.index), r.start, self.size, r.matrix,
-                                      self.dataset.augmentation.fill, raw)
+                if r.field is not None:
+                    self.ops.patch_elastic(self.volume(r.domain, r.index), r.start, self.size, r.matrix, fields[id(r.field)],
+                                           self.dataset.augmentation.fill, raw)
+                else:
+                    self.ops.patch_affine(self.volume(r.domain, r.index), r.start, self.size, r.matrix,
+                                          self.dataset.augmentation.fill, raw)
                 self.ops.patch_zscore(raw, (0, 0, 0), self.size, dst[n, 0], (-1.0, 1.0))
             out[key] = dst.squeeze(2) if self.squeeze else dst
         return out
@@ -69,7 +89,8 @@ class DeviceMultiModalPipeline:
     memory), one in total when paired, and one gs_patch_clip_minmax per domain writing all of its modalities straight into
     the batch (csrc/volsample.hip). Nothing synchronises per iteration; the empty-zone check of a case runs once, when its
     mask is first uploaded. A sample that carries an augmentation matrix takes gs_patch_affine_clip_minmax instead: the
-    same crop as one trilinear gather through the matrix (data/utils/patch_affine.py). Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
+    same crop as one trilinear gather through the matrix (data/utils/patch_affine.py), and one that also carries an elastic
+    field gs_patch_elastic_clip_minmax (the fields of a batch are uploaded in one copy). Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
     train_dataset.py:106-188 with datasets/utils/patch_samplers.py."""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
@@ -119,13 +140,15 @@ class DeviceMultiModalPipeline:
             self.checked.add((domain, index))
         return mask, weight, [self.volume(n, index) for n in ds.modalities[domain]]
 
-    def _patch(self, domain, index, vols, mask, point, dst, matrix=None):
+    def _patch(self, domain, index, vols, mask, point, dst, matrix=None, field=None):
         ds = self.dataset
         names = ds.modalities[domain]
         cols = ([ds.outside_value[n] for n in names], [ds.divisor(n, index) for n in names],
                 [ds.clip_range[n][0] for n in names], [ds.clip_range[n][1] for n in names])
         if matrix is None:
             self.ops.patch_clip_minmax(vols, mask, point, self.size, *cols, dst)
+        elif field is not None:
+            self.ops.patch_elastic_clip_minmax(vols, mask, point, self.size, matrix, field, *cols, dst)
         else:
             self.ops.patch_affine_clip_minmax(vols, mask, point, self.size, matrix, *cols, dst)
 
@@ -138,19 +161,21 @@ class DeviceMultiModalPipeline:
         out = {k: v for k, v in batch.items() if k not in ("A", "B")}
         dst = {k: torch.empty((n, len(ds.modalities[k]), *self.size), dtype=torch.float32, device=self.device) for k in "AB"}
         points = torch.empty((n, 2, 4), dtype=torch.int32, device=self.device)
+        fields = upload_fields(list(items_A) + list(items_B), self.device)
+        field_of = lambda r: None if r.field is None else fields[id(r.field)]
         for i, (a, b) in enumerate(zip(items_A, items_B)):
             mask_A, weight, vols_A = self.case("A", a.index)
             self.ops.voxel_draw(mask_A, weight, self.size, a.u, points[i, 0])
-            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i], a.matrix)
+            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i], a.matrix, field_of(a))
             if ds.paired:                                   # the same point, A's mask and A's case
                 points[i, 1].copy_(points[i, 0])
                 self._patch("B", a.index, [self.volume(m, a.index) for m in ds.modalities["B"]], mask_A, points[i, 0],
-                            dst["B"][i], b.matrix)
+                            dst["B"][i], b.matrix, field_of(b))
             else:
                 mask_B, _, vols_B = self.case("B", b.index)
                 self.ops.voxel_draw(mask_B, None, self.size, b.u, points[i, 1], focal_A=points[i, 0],
                                     dims_A=tuple(mask_A.shape), proportion=ds.focal_region_proportion)
-                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i], b.matrix)
+                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i], b.matrix, field_of(b))
         self.points = points
         out.update(dst)
         return out

@@ -19,7 +19,9 @@ stay resident in HBM and `DeviceMultiModalPipeline` (data/device_volumes.py) dra
 `augmentation` (not in the reference; data/utils/patch_affine.py) turns the crop into one trilinear gather through a random
 3 x 3 matrix — flips, rotation, zoom — round the same patch centre: mask, then interpolate, then the same normalisation.
 Its eight `np.random` uniforms per matrix follow the sample's draws above (one matrix for a paired sample, A's then B's
-otherwise); without the field nothing changes, the random streams included."""
+otherwise); without the field nothing changes, the random streams included. Its `elastic` key adds a free-form
+deformation in front of the matrix — a lattice of control-point displacements, cubic B-splines — inside the same gather;
+each set then takes 1 + 3 G_0 G_1 G_2 further uniforms after its eight, and a paired sample shares one field."""
 import json
 import math
 import random
@@ -33,7 +35,7 @@ from torch.utils.data import Dataset
 
 from .. import configs
 from .utils.normalization import min_max_normalize
-from .utils.patch_affine import draw_params, matrix_tuple, parse_augmentation, sample_patch
+from .utils.patch_affine import check_elastic, draw_set, matrix_tuple, parse_augmentation, sample_patch
 
 PAIRED_SAMPLING_SCHEMES = ("uniform-random-within-body", "fdg-pet-weighted")
 UNPAIRED_SAMPLING_SCHEMES = ("uniform-random-within-body-sf", "fdg-pet-weighted-sf")
@@ -56,7 +58,8 @@ class MultiModalVolumeDatasetConfig(configs.base.BaseDatasetConfig):
     # not in the reference: volumes resident in HBM, draw + crop + normalisation on the GPU (data/device_volumes.py)
     device_transforms: bool = False
     # not in the reference: random flips / rotation / zoom of every patch as one trilinear gather (data/utils/
-    # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W]}
+    # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W],
+    # elastic: {prob, control_points: [D, H, W], max_displacement: [D, H, W] in the units of spacing}}
     augmentation: Optional[Dict[str, Any]] = None
 
 
@@ -118,13 +121,15 @@ def draw_focal_point(mask, weight, patch, u, box=None):
 
 
 class RawCase:
-    """what a worker hands over with device_transforms on: which case, the uniform its focal point is drawn from, and the
-    augmentation matrix of its patch (9 floats, row-major) or None"""
-    __slots__ = ("domain", "index", "u", "matrix")
+    """what a worker hands over with device_transforms on: which case, the uniform its focal point is drawn from, the
+    augmentation matrix of its patch (9 floats, row-major) or None, and next to it the elastic field (float64
+    [3, G0, G1, G2], already in voxels) or None"""
+    __slots__ = ("domain", "index", "u", "matrix", "field")
 
-    def __init__(self, domain, index, u, matrix=None):
+    def __init__(self, domain, index, u, matrix=None, field=None):
         self.domain, self.index, self.u = domain, int(index), (None if u is None else float(u))
         self.matrix = None if matrix is None else matrix_tuple(matrix)
+        self.field = field
 
 
 def collate_raw(samples):
@@ -180,6 +185,7 @@ class MultiModalVolumeDataset(Dataset):
         self.divisors = json.loads(Path(path).read_text()) if path else {}
         self.raw = bool(_field(d, "device_transforms", False))
         self.augmentation = parse_augmentation(_field(d, "augmentation"), fill_allowed=False)
+        check_elastic(self.augmentation, self.patch_size)
 
     def __len__(self):
         return len(self.cases)
@@ -210,12 +216,12 @@ class MultiModalVolumeDataset(Dataset):
         v = v / self.divisor(name, index)
         return min_max_normalize(torch.clamp(v, lo, hi), lo, hi)
 
-    def crop(self, domain, index, mask, focal, matrix=None):
+    def crop(self, domain, index, mask, focal, matrix=None, field=None):
         start = [f - p // 2 for f, p in zip(focal, self.patch_size)]
         if matrix is not None:              # mask, then interpolate (sample_patch), then the same chain
             full = np.ones(self.patch_size, bool)
             return torch.stack([self.normalize(n, index, sample_patch(self.load(n, index), mask, start, self.patch_size,
-                                                                      matrix, self.outside_value[n]), full)
+                                                                      matrix, self.outside_value[n], field), full)
                                 for n in self.modalities[domain]])
         win = tuple(slice(s, s + p) for s, p in zip(start, self.patch_size))
         m = mask[win]
@@ -238,12 +244,12 @@ class MultiModalVolumeDataset(Dataset):
         return (focal_A, focal_B), flag
 
     def draw_matrices(self):
-        """(M_A, M_B) after the sample's other draws: none without `augmentation`, one set of eight uniforms shared by A and
-        B when paired, A's set then B's set when unpaired"""
+        """((M_A, field_A), (M_B, field_B)) after the sample's other draws: none without `augmentation`, one set (eight
+        uniforms, and the field's with `elastic`) shared by A and B when paired, A's set then B's set when unpaired"""
         if self.augmentation is None:
-            return None, None
-        M_A = draw_params(self.augmentation)
-        return M_A, (M_A if self.paired else draw_params(self.augmentation))
+            return (None, None), (None, None)
+        set_A = draw_set(self.augmentation)
+        return set_A, (set_A if self.paired else draw_set(self.augmentation))
 
     def __getitem__(self, index):
         index_A = index % len(self.cases)
@@ -251,13 +257,13 @@ class MultiModalVolumeDataset(Dataset):
         if self.raw:
             u_A = np.random.random_sample()
             u_B = None if self.paired else np.random.random_sample()
-            M_A, M_B = self.draw_matrices()
-            return {"A": RawCase("A", index_A, u_A, M_A), "B": RawCase("B", index_B, u_B, M_B)}
+            set_A, set_B = self.draw_matrices()
+            return {"A": RawCase("A", index_A, u_A, *set_A), "B": RawCase("B", index_B, u_B, *set_B)}
         (focal_A, focal_B), _ = self.sample_points(index_A, index_B)
-        M_A, M_B = self.draw_matrices()
+        set_A, set_B = self.draw_matrices()
         mask_A = self.load(self.body_mask["A"], index_A)
         mask_B = mask_A if self.paired else self.load(self.body_mask["B"], index_B)
-        return {"A": self.crop("A", index_A, mask_A, focal_A, M_A), "B": self.crop("B", index_B, mask_B, focal_B, M_B)}
+        return {"A": self.crop("A", index_A, mask_A, focal_A, *set_A), "B": self.crop("B", index_B, mask_B, focal_B, *set_B)}
 
     # ---- picked up by build_loader / Trainer ----------------------------------------------------------------------
     @property

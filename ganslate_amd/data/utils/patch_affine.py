@@ -13,17 +13,47 @@ For a volume of size (D, H, W), a patch p = (d, h, w) starting at `start` and a 
     lerp(a, b, t) = a + t * (b - a) in float32, along W, then H, then D
 M = I is the plain crop, diag(+-1) the flipped crop, a signed permutation np.rot90 of it (as equal numbers).
 
+Elastic deformation (`elastic`, also stated in include/ganslate_hip.h) is a free-form deformation in front of the matrix:
+a lattice of G = (G_0, G_1, G_2) >= 4 control-point displacements PHI[a][i][j][k] (float64, voxels of axis a), aligned
+with the patch so that [0, p_a - 1] spans its G_a - 3 inner intervals, interpolated by uniform cubic B-splines:
+    num = o_a (G_a - 3), den = p_a - 1, j_a = min(num // den, G_a - 4), f = float(num - j_a den) / float(den)
+    f2 = f f, f3 = f2 f, g = 1 - f
+    B0 = ((g g) g) / 6, B1 = ((3 f3 - 6 f2) + 4) / 6, B2 = (((3 f2 - 3 f3) + 3 f) + 1) / 6, B3 = f3 / 6
+    q[m][n] = ((Bz0 PHI[a][j_0][j_1+m][j_2+n] + Bz1 PHI[a][j_0+1][..]) + Bz2 PHI[a][j_0+2][..]) + Bz3 PHI[a][j_0+3][..]
+    R[n] = ((By0 q[0][n] + By1 q[1][n]) + By2 q[2][n]) + By3 q[3][n]
+    u_a = ((Bx0 R[0] + Bx1 R[1]) + Bx2 R[2]) + Bx3 R[3];    r'_a = r_a + u_a
+and s is computed from r' instead of r; the rest is unchanged, except that t_a = 0 where s_a fails the reach test (no bit
+changes for a finite s_a; a NaN or infinite displacement then gives the outside value instead of NaN).
+
 `augmentation` in a dataset config: {prob: 1.0, flip: [false, false, false], rotate_deg: [0, 0, 0], scale: [1, 1],
-spacing: [1, 1, 1], fill: 0.0 (UnpairedVolumeDataset only)}. Per sample and matrix `draw_params` takes eight np.random
-uniforms — always all eight, after the sample's other draws."""
+spacing: [1, 1, 1], fill: 0.0 (UnpairedVolumeDataset only), elastic: null or {prob: 1.0, control_points: [7, 7, 7],
+max_displacement: [0, 4, 4]} (D, H, W; in the units of `spacing`)}. Per sample and matrix `draw_params` takes eight
+np.random uniforms — always all eight, after the sample's other draws; with `elastic` set `draw_field` takes
+1 + 3 G_0 G_1 G_2 more after them, always all of them."""
 import math
 from dataclasses import dataclass
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
-KEYS = ("prob", "flip", "rotate_deg", "scale", "spacing", "fill")
+KEYS = ("prob", "flip", "rotate_deg", "scale", "spacing", "fill", "elastic")
+ELASTIC_KEYS = ("prob", "control_points", "max_displacement")
 UNIFORMS = 8          # np.random uniforms per drawn matrix
+MAX_CONTROL_POINTS = 1024      # GS_ELASTIC_MAX_POINTS: the lattice travels as 3 * 1024 doubles at the most
+FOLD_BOUND = 0.4      # of the control spacing: Choi and Lee's sufficient bound for a 3-D cubic B-spline map without folds
+
+
+@dataclass(frozen=True)
+class ElasticAugmentation:
+    prob: float = 1.0
+    control_points: Tuple[int, int, int] = (7, 7, 7)
+    max_displacement: Tuple[float, float, float] = (0.0, 0.0, 0.0)      # D, H, W, in the units of `spacing`
+
+    @property
+    def uniforms(self):
+        """np.random uniforms per drawn field: the switch, then one per component and control point"""
+        g = self.control_points
+        return 1 + 3 * g[0] * g[1] * g[2]
 
 
 @dataclass(frozen=True)
@@ -34,6 +64,7 @@ class AffineAugmentation:
     scale: Tuple[float, float] = (1.0, 1.0)
     spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0)
     fill: float = 0.0
+    elastic: Optional[ElasticAugmentation] = None
 
 
 def _numbers(name, value, n):
@@ -70,7 +101,53 @@ def parse_augmentation(node, fill_allowed):
     if "fill" in node and node["fill"] is not None and not fill_allowed:
         raise ValueError("augmentation.fill is UnpairedVolumeDataset's; here a voxel outside the volume or the body mask "
                          "takes the modality's `outside_value`")
-    return AffineAugmentation(prob, tuple(bool(v) for v in flip), rotate, scale, spacing, float(get("fill", 0.0)))
+    return AffineAugmentation(prob, tuple(bool(v) for v in flip), rotate, scale, spacing, float(get("fill", 0.0)),
+                              parse_elastic(get("elastic", None)))
+
+
+def parse_elastic(node):
+    """the `elastic` sub-field -> ElasticAugmentation, or None when it is absent / null"""
+    if node is None:
+        return None
+    unknown = sorted(set(node.keys()) - set(ELASTIC_KEYS))
+    if unknown:
+        raise ValueError(f"augmentation.elastic: unknown keys {unknown}; known: {list(ELASTIC_KEYS)}")
+    get = lambda k, default: default if k not in node or node[k] is None else node[k]
+    prob = float(get("prob", 1.0))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"augmentation.elastic.prob must lie in [0, 1]; got {prob}")
+    raw = list(get("control_points", (7, 7, 7)))
+    if len(raw) != 3 or not all(float(v) == int(v) for v in raw):
+        raise ValueError(f"augmentation.elastic.control_points: expected three integers (D, H, W); got {raw}")
+    grid = tuple(int(v) for v in raw)
+    if min(grid) < 4:
+        raise ValueError(f"augmentation.elastic.control_points: a cubic B-spline lattice needs at least 4 per axis; got "
+                         f"{list(grid)}")
+    if grid[0] * grid[1] * grid[2] > MAX_CONTROL_POINTS:
+        raise ValueError(f"augmentation.elastic.control_points: {list(grid)} are {grid[0] * grid[1] * grid[2]} control points; "
+                         f"at most {MAX_CONTROL_POINTS}")
+    disp = _numbers("elastic.max_displacement", get("max_displacement", (0.0, 0.0, 0.0)), 3)
+    if min(disp) < 0.0:
+        raise ValueError(f"augmentation.elastic.max_displacement must not be negative; got {list(disp)}")
+    return ElasticAugmentation(prob, grid, disp)
+
+
+def check_elastic(cfg, patch):
+    """Where the patch size is known: refuses a patch axis under 2 voxels and any axis a with
+    max_displacement[a] / spacing[a] >= 0.4 (p_a - 1) / (G_a - 3), i.e. control-point displacements of 0.4 control
+    spacings or more. Below that bound a 3-D cubic B-spline map is free of folds (Choi and Lee); it is applied per axis
+    here, which is a guard and not a proof for lattices whose control spacing differs between the axes."""
+    if cfg is None or cfg.elastic is None:
+        return
+    patch = [int(p) for p in patch]
+    if len(patch) != 3 or min(patch) < 2:
+        raise ValueError(f"augmentation.elastic needs a 3-D patch_size of at least 2 voxels per axis; got {patch}")
+    for a in range(3):
+        bound = FOLD_BOUND * (patch[a] - 1) / (cfg.elastic.control_points[a] - 3)        # voxels
+        if cfg.elastic.max_displacement[a] / cfg.spacing[a] >= bound:
+            raise ValueError(f"augmentation.elastic.max_displacement[{a}] = {cfg.elastic.max_displacement[a]} (axis {'DHW'[a]}) "
+                             f"may fold the patch: with {cfg.elastic.control_points[a]} control points over {patch[a]} voxels "
+                             f"of spacing {cfg.spacing[a]} it must stay below {bound * cfg.spacing[a]:.6g}")
 
 
 def _cos_sin(deg):
@@ -125,14 +202,65 @@ def draw_params(cfg):
     return affine_matrix(flips, angles, zoom, cfg.spacing)
 
 
+def draw_field(cfg):
+    """One lattice of control-point displacements from 1 + 3 G_0 G_1 G_2 np.random uniforms, always all of them (one
+    vectorised draw, which consumes the stream as that many single draws would): the first < elastic.prob switches the
+    field on, the others give PHI_mm[a][i][j][k] = (2 u - 1) max_displacement[a], component-major, lattice in C order.
+    Returns float64 [3, G_0, G_1, G_2] in voxels (PHI_mm[a] / spacing[a]), or None when switched off."""
+    e = cfg.elastic
+    u = np.random.random_sample(e.uniforms)
+    if not float(u[0]) < e.prob:
+        return None
+    mm = (2.0 * u[1:].reshape(3, *e.control_points) - 1.0) * np.asarray(e.max_displacement, np.float64).reshape(3, 1, 1, 1)
+    return np.ascontiguousarray(mm / np.asarray(cfg.spacing, np.float64).reshape(3, 1, 1, 1))
+
+
+def draw_set(cfg):
+    """(M, field) of one patch: the matrix's eight uniforms, then — only with `elastic` set — the field's"""
+    M = draw_params(cfg)
+    return M, (None if cfg.elastic is None else draw_field(cfg))
+
+
+def bspline_axis(p, G):
+    """per output index of an axis of p voxels over G control points: (j [p] int64, (B0, B1, B2, B3) float64 [p] each)"""
+    o = np.arange(int(p), dtype=np.int64)
+    num, den = o * (int(G) - 3), int(p) - 1
+    j = np.minimum(num // den, int(G) - 4)
+    f = (num - j * den).astype(np.float64) / np.float64(den)
+    f2 = f * f
+    f3 = f2 * f
+    g = 1.0 - f
+    return j, (((g * g) * g) / 6.0, ((3.0 * f3 - 6.0 * f2) + 4.0) / 6.0, (((3.0 * f2 - 3.0 * f3) + 3.0 * f) + 1.0) / 6.0,
+               f3 / 6.0)
+
+
+def displacement(patch, field):
+    """[u_0, u_1, u_2], float64 [d, h, w] each: the free-form deformation of the definition above, vectorised — D
+    innermost, then H, W outermost, every numpy operation one IEEE operation per element"""
+    field = np.asarray(field, dtype=np.float64)
+    if field.ndim != 4 or field.shape[0] != 3 or min(field.shape[1:]) < 4 or min(int(p) for p in patch) < 2:
+        raise ValueError(f"elastic field {field.shape} on patch {list(patch)}: expected [3, G0, G1, G2] with every G >= 4 and "
+                         f"a patch of at least 2 voxels per axis")
+    (j0, Bz), (j1, By), (j2, Bx) = [bspline_axis(patch[a], field.shape[1 + a]) for a in range(3)]
+    j0, j1, j2 = j0[:, None, None], j1[None, :, None], j2[None, None, :]
+    Bz = [b[:, None, None] for b in Bz]
+    By = [b[None, :, None] for b in By]
+    Bx = [b[None, None, :] for b in Bx]
+    dot = lambda B, v: ((B[0] * v[0] + B[1] * v[1]) + B[2] * v[2]) + B[3] * v[3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return [dot(Bx, [dot(By, [dot(Bz, [field[a][j0 + l, j1 + m, j2 + n] for l in range(4)]) for m in range(4)])
+                         for n in range(4)]) for a in range(3)]
+
+
 def matrix_tuple(M):
     """the 9-tuple of floats (row-major) a worker hands over"""
     return tuple(float(v) for v in np.asarray(M, dtype=np.float64).reshape(9))
 
 
-def sample_patch(volume, mask, start, patch, M, outside):
+def sample_patch(volume, mask, start, patch, M, outside, field=None):
     """float32 [d, h, w]: the definition above, vectorised — every numpy operation is one IEEE operation per element.
-    volume: (D, H, W) array of any real dtype (read as float32); mask: (D, H, W) or None."""
+    volume: (D, H, W) array of any real dtype (read as float32); mask: (D, H, W) or None; field: None or the elastic
+    lattice, float64 [3, G0, G1, G2] in voxels."""
     vol = np.asarray(volume)
     size = vol.shape
     M = np.asarray(M, dtype=np.float64).reshape(3, 3)
@@ -140,13 +268,21 @@ def sample_patch(volume, mask, start, patch, M, outside):
     c = [(int(p) - 1) / 2.0 for p in patch]
     o = np.meshgrid(*[np.arange(int(p), dtype=np.float64) for p in patch], indexing="ij")
     r = [o[a] - c[a] for a in range(3)]
-    s = [((M[a, 0] * r[0] + M[a, 1] * r[1]) + M[a, 2] * r[2]) + (float(int(start[a])) + c[a]) for a in range(3)]
+    if field is not None:
+        u = displacement(patch, field)
+        with np.errstate(invalid="ignore", over="ignore"):
+            r = [r[a] + u[a] for a in range(3)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = [((M[a, 0] * r[0] + M[a, 1] * r[1]) + M[a, 2] * r[2]) + (float(int(start[a])) + c[a]) for a in range(3)]
     fl = [np.floor(x) for x in s]
     with np.errstate(invalid="ignore"):
         t = [(x - y).astype(f32) for x, y in zip(s, fl)]
         reach = np.ones(s[0].shape, bool)
         for a in range(3):
-            reach &= (s[a] >= -1.0) & (s[a] < float(size[a]))
+            inside = (s[a] >= -1.0) & (s[a] < float(size[a]))
+            reach &= inside
+            if field is not None:
+                t[a] = np.where(inside, t[a], f32(0))
     i = [np.where(reach, x, 0.0).astype(np.int64) for x in fl]
     fill = f32(outside)
 

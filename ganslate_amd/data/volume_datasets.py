@@ -13,7 +13,9 @@ normalises on the GPU (csrc/volproc.hip) in front of `set_input`, through the sa
 
 `augmentation` (not in the reference; data/utils/patch_affine.py, 3-D patch sizes only) replaces the crop by one trilinear
 gather through a random 3 x 3 matrix per domain — flips, rotation, zoom, `fill` outside the volume — in front of the same
-z-score; the patch starts still come from `random`, the matrices from `np.random` (A's eight uniforms, then B's)."""
+z-score; the patch starts still come from `random`, the matrices from `np.random` (A's eight uniforms, then B's). With
+its `elastic` key a free-form deformation (control-point lattice, cubic B-splines) precedes the matrix inside the same
+gather, and each set takes 1 + 3 G_0 G_1 G_2 further uniforms after its eight."""
 import random
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -25,7 +27,7 @@ from torch.utils.data import Dataset
 
 from .. import configs
 from .utils.normalization import z_score_normalize
-from .utils.patch_affine import draw_params, matrix_tuple, parse_augmentation, sample_patch
+from .utils.patch_affine import check_elastic, draw_set, matrix_tuple, parse_augmentation, sample_patch
 from .utils.stochastic_focal_patching import StochasticFocalPatchSampler
 
 EXTENSIONS = [".npy"]
@@ -39,18 +41,21 @@ class UnpairedVolumeDatasetConfig(configs.base.BaseDatasetConfig):
     # not in the reference: volumes resident in HBM, crop + normalisation on the GPU (data/device_volumes.py)
     device_transforms: bool = False
     # not in the reference: random flips / rotation / zoom of every patch as one trilinear gather (data/utils/
-    # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W], fill}
+    # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W], fill,
+    # elastic: {prob, control_points: [D, H, W], max_displacement: [D, H, W] in the units of spacing}}
     augmentation: Optional[Dict[str, Any]] = None
 
 
 class RawPatch:
-    """what a worker hands over with device_transforms on: which volume, where the patch starts, and its augmentation
-    matrix (9 floats, row-major) or None"""
-    __slots__ = ("domain", "index", "start", "matrix")
+    """what a worker hands over with device_transforms on: which volume, where the patch starts, its augmentation
+    matrix (9 floats, row-major) or None, and next to it the elastic field (float64 [3, G0, G1, G2], already in voxels)
+    or None"""
+    __slots__ = ("domain", "index", "start", "matrix", "field")
 
-    def __init__(self, domain, index, start, matrix=None):
+    def __init__(self, domain, index, start, matrix=None, field=None):
         self.domain, self.index, self.start = domain, int(index), tuple(int(v) for v in start)
         self.matrix = None if matrix is None else matrix_tuple(matrix)
+        self.field = field
 
 
 def collate_raw(samples):
@@ -77,6 +82,7 @@ class UnpairedVolumeDataset(Dataset):
         self.augmentation = parse_augmentation(node, fill_allowed=True)
         if self.augmentation is not None and self.patch_sampler.dims != 3:
             raise ValueError(f"augmentation needs a 3-D patch_size (D, H, W); got {[int(v) for v in self.patch_size]}")
+        check_elastic(self.augmentation, self.patch_size)
         self._shapes = {}
 
     def load(self, domain, index):
@@ -97,14 +103,15 @@ class UnpairedVolumeDataset(Dataset):
         aug = self.augmentation
         if self.raw:
             start_A, start_B = self.patch_sampler.get_start_pair(self.shape("A", index_A), self.shape("B", index_B))
-            M_A, M_B = (draw_params(aug), draw_params(aug)) if aug else (None, None)       # A's set, then B's set
-            return {"A": RawPatch("A", index_A, start_A, M_A), "B": RawPatch("B", index_B, start_B, M_B)}
+            set_A, set_B = (draw_set(aug), draw_set(aug)) if aug else ((None, None), (None, None))   # A's set, then B's
+            return {"A": RawPatch("A", index_A, start_A, *set_A), "B": RawPatch("B", index_B, start_B, *set_B)}
         A, B = self.load("A", index_A).float(), self.load("B", index_B).float()
         if aug:
             start_A, start_B = self.patch_sampler.get_start_pair(A.shape, B.shape)
             size = [int(v) for v in self.patch_size]
-            A = torch.from_numpy(sample_patch(A.numpy(), None, start_A, size, draw_params(aug), aug.fill))
-            B = torch.from_numpy(sample_patch(B.numpy(), None, start_B, size, draw_params(aug), aug.fill))
+            (M_A, field_A), (M_B, field_B) = draw_set(aug), draw_set(aug)
+            A = torch.from_numpy(sample_patch(A.numpy(), None, start_A, size, M_A, aug.fill, field_A))
+            B = torch.from_numpy(sample_patch(B.numpy(), None, start_B, size, M_B, aug.fill, field_B))
         else:
             A, B = self.patch_sampler.get_patch_pair(A, B)
         A = z_score_normalize(A, scale_to_range=(-1, 1))

@@ -233,6 +233,13 @@ _PROTOS = {
                                               C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "gs_patch_affine": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_float, C.c_void_p, C.c_void_p]),
+    "gs_patch_elastic_clip_minmax": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "gs_patch_elastic": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.c_float,
+                                   C.c_void_p, C.c_void_p]),
     "gs_volume_prepare_ws_bytes": (C.c_int64, []),
     "gs_volume_prepare": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float),

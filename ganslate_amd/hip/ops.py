@@ -1168,6 +1168,51 @@ class HipOps(TwinSplit):
         L.check(self.lib.gs_patch_affine(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
                                          self._matrix(matrix), float(fill), _ptr(out), _stream()), "gs_patch_affine")
 
+    @staticmethod
+    def _lattice(field):
+        """(grid as int32[3], device pointer) of an elastic field: a contiguous float64 device tensor [3, G0, G1, G2]"""
+        if not (isinstance(field, torch.Tensor) and field.is_cuda and field.dtype == torch.float64 and field.dim() == 4
+                and field.shape[0] == 3 and field.is_contiguous()):
+            got = (tuple(field.shape), field.dtype, str(field.device)) if isinstance(field, torch.Tensor) else type(field).__name__
+            raise ValueError(f"field: expected a contiguous float64 device tensor of shape [3, G0, G1, G2]; got {got}")
+        return (C.c_int32 * 3)(*[int(v) for v in field.shape[1:]]), _ptr(field)
+
+    def patch_elastic_clip_minmax(self, volumes, mask, point, patch, matrix, field, outside, divisor, lo, hi, out):
+        """gs_patch_elastic_clip_minmax: patch_affine_clip_minmax with a free-form deformation in front of the matrix.
+        field: float64 device tensor [3, G0, G1, G2], control-point displacements in voxels (include/ganslate_hip.h)."""
+        n = len(volumes)
+        if n < 1:
+            raise ValueError("patch_elastic_clip_minmax: at least one volume")
+        self._case_volume("mask", mask, (torch.uint8,))
+        for i, v in enumerate(volumes):
+            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        self._point("point", point, 3)
+        grid, fptr = self._lattice(field)
+        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
+            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == (n, *[int(v) for v in patch])):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *[int(v) for v in patch])}")
+        fl = lambda vals: (C.c_float * n)(*[float(v) for v in vals])
+        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in volumes])
+        dts = (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes])
+        L.check(self.lib.gs_patch_elastic_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, _ptr(point),
+                                                      (C.c_int32 * 3)(*[int(v) for v in patch]), self._matrix(matrix), grid,
+                                                      fptr, fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
+                "gs_patch_elastic_clip_minmax")
+
+    def patch_elastic(self, volume, start, size, matrix, field, fill, out):
+        """gs_patch_elastic: patch_affine with a free-form deformation in front of the matrix (field as above)"""
+        self._case_volume("volume", volume, tuple(self.VOL_DTYPES))
+        grid, fptr = self._lattice(field)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == tuple(int(v) for v in size)):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {tuple(int(v) for v in size)}")
+        st, sz = (C.c_int32 * 3)(*[int(v) for v in start]), (C.c_int32 * 3)(*[int(v) for v in size])
+        L.check(self.lib.gs_patch_elastic(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
+                                          self._matrix(matrix), grid, fptr, float(fill), _ptr(out), _stream()),
+                "gs_patch_elastic")
+
     def volume_prepare(self, volumes, mask, extra_masks, target, outside, divisor, lo, hi, out=None, masks_out=None):
         """gs_volume_prepare: one whole case for the val / test engines -> (out, [masks]). volumes: C fp32 / int16
         (D, H, W) device tensors; mask: the body mask (uint8, non-zero = inside); extra_masks: up to VM_MAX_LABELS further

@@ -46,6 +46,7 @@ LIBRARY_OPTIONS = {
     "hconv2": "GS_HCONV2",
     "pwise": "GS_PWISE",
     "daxis": "GS_DAXIS",
+    "elastic_rows": None,
 }
 
 # ---- host switches ---------------------------------------------------------------------------------------------------

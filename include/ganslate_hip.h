@@ -117,7 +117,9 @@ const char* gs_last_error(void);
  * gradient / forward kernels), pwise (one-tap layers with <= 8 channels on one side — the V-Net's 32 -> 1 output conv — on
  * register-operand kernels: smallest volume in units of 2048 voxels, 0 = off), daxis (streaming kernel for stride-1 classes
  * whose taps all lie on the row axis with 8..64 channels — the (k,1,1) half of a separable volume conv on its [N, D, H W, C]
- * view, and its data gradient: smallest launch in units of 64 voxels, 0 = off; default 8192). Every setting computes the same function (up to
+ * view, and its data gradient: smallest launch in units of 64 voxels, 0 = off; default 8192), elastic_rows (largest row table,
+ * in bytes of LDS, with which gs_patch_elastic* run their row-shared form; 0 = always per voxel; both give the same bits).
+ * Every setting computes the same function (up to
  * the fp32 summation order and, for hconvw_ring, where the bf16 rounding of the folded gradient happens); none skips work.
  * Unknown name -> non-zero. */
 int gs_set_option(const char* name, int value);
@@ -616,6 +618,50 @@ int gs_patch_affine_clip_minmax(const void* const* vols, const int32_t* dtypes, 
                                 void* stream);
 int gs_patch_affine(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
                     const int32_t* size, const double* M, float fill, float* out, void* stream);
+/* Elastic deformation inside the same gather: a free-form deformation, i.e. a coarse lattice of control-point
+ * displacements interpolated by uniform cubic B-splines and aligned with the patch, added to the patch offset BEFORE the
+ * matrix is applied — the two compose as maps, in one launch, without an intermediate volume.
+ * THE DEFINITION (data/utils/patch_affine.py states it in numpy, tests/patch_elastic_ref.py as a per-voxel loop).
+ *   lattice G = (G_0, G_1, G_2) control points per axis (D, H, W), every G_a >= 4, G_0 G_1 G_2 <= GS_ELASTIC_MAX_POINTS
+ *   field   PHI[a][i][j][k], float64, C order: component a of the displacement at control point (i, j, k), already in
+ *           voxels of axis a (millimetres / spacing[a] on the host)
+ *   patch   p = (d, h, w), every p_a >= 2; the extent [0, p_a - 1] spans the G_a - 3 inner intervals of the lattice
+ * Per output voxel o and axis a, in integers:
+ *   num = o_a (G_a - 3),  den = p_a - 1,  j_a = min(num / den, G_a - 4) (integer division),
+ *   f = (double)(num - j_a den) / (double)den      one correctly rounded float64 division of two exact integers; the last
+ *                                                  voxel of an axis gets j_a = G_a - 4, f = 1
+ * Basis weights in float64, one IEEE operation per step, no fused multiply-add:
+ *   f2 = f f,  f3 = f2 f,  g = 1 - f
+ *   B0 = ((g g) g) / 6,  B1 = ((3 f3 - 6 f2) + 4) / 6,  B2 = (((3 f2 - 3 f3) + 3 f) + 1) / 6,  B3 = f3 / 6
+ * Displacement component a — innermost over D (weights Bz of axis 0), then H (By), outermost over W (Bx), every sum left
+ * to right with separate multiply and add:
+ *   q[m][n] = ((Bz0 PHI[a][j_0][j_1 + m][j_2 + n] + Bz1 PHI[a][j_0 + 1][..]) + Bz2 PHI[a][j_0 + 2][..]) + Bz3 PHI[a][j_0 + 3][..]
+ *   R[n]    = ((By0 q[0][n] + By1 q[1][n]) + By2 q[2][n]) + By3 q[3][n]
+ *   u_a     = ((Bx0 R[0] + Bx1 R[1]) + Bx2 R[2]) + Bx3 R[3]
+ * r'_a = r_a + u_a (one float64 add), and s_a = ((M[a][0] r'_0 + M[a][1] r'_1) + M[a][2] r'_2) + (start_a + c_a) onwards
+ * is the affine definition above, unchanged: floor, t, the reach test, masked corners, the three float32 lerps — with one
+ * addition: t_a = 0 on an axis whose s_a fails the reach test. For a finite s_a that changes no bit (the eight corners are
+ * all the outside value, which every finite t lerps to itself); for a NaN or infinite s_a, where s_a - i_a is no number,
+ * it makes the result that same value. So a NaN or infinite displacement gives a NaN or out-of-range coordinate, by the
+ * reach rule "all eight corners outside": the voxel takes the outside value and nothing is read out of bounds. A zero
+ * field is the affine gather bit for bit.
+ * The order is chosen so that R[n] of a lattice column depends on (o_0, o_1) only: the kernel computes it once per output
+ * row a workgroup covers (into LDS) and every voxel of the row reads it — the same bits as the per-voxel evaluation,
+ * which is what it launches instead when that row table passes 32 KB of LDS (the option elastic_rows): rows of a few
+ * voxels under a wide lattice. The divisions and weights reproduce between hipcc and numpy, so no host-built tables are involved.
+ *
+ * gs_patch_elastic_clip_minmax / gs_patch_elastic: gs_patch_affine_clip_minmax / gs_patch_affine plus grid (host
+ * int32[3] = G) and field (DEVICE double[3 G_0 G_1 G_2], read through L2 or staged to LDS, never modified). They refuse
+ * everything the affine entries refuse and, before any launch, a null grid or field, any G_a < 4, more than
+ * GS_ELASTIC_MAX_POINTS control points, any p_a < 2, and (p_a - 1) (G_a - 3) beyond int32. */
+#define GS_ELASTIC_MAX_POINTS 1024
+int gs_patch_elastic_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask, int32_t D,
+                                 int32_t H, int32_t W, const int32_t* point, const int32_t* patch, const double* M,
+                                 const int32_t* grid, const double* field, const float* outside, const float* divisor,
+                                 const float* lo, const float* hi, float* out, void* stream);
+int gs_patch_elastic(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                     const int32_t* size, const double* M, const int32_t* grid, const double* field, float fill, float* out,
+                     void* stream);
 /* gs_volume_prepare: one whole case for the val / test engines (the reference's val_test_dataset.py:136-161): body
  * masking, centred padding to a target shape and the per-voxel chain of gs_patch_clip_minmax, for all C
  * (1..GS_PATCH_MAX_MODALITIES) volumes and M (1..1 + GS_VM_MAX_LABELS) byte masks of a D x H x W case. masks[0] is the

@@ -1,18 +1,22 @@
-"""Time of the augmented patch launch next to the plain crop it replaces (profiles/patch_affine.txt): gs_patch_affine_clip_minmax
-through a 30 degrees x 1.1 matrix and gs_patch_clip_minmax, both for the HX4 patch (32, 128, 128) with C = 2 int16 volumes of a
-resident (128, 256, 256) case and its body mask. The plain crop is the yardstick; the ratio is reported, nothing is gated.
+"""Time of the augmented patch launches next to the plain crop they replace (profiles/patch_elastic.txt; profiles/patch_affine.txt
+is the run of this tool before the elastic launch existed): gs_patch_clip_minmax, gs_patch_affine_clip_minmax through a
+30 degrees x 1.1 matrix, and gs_patch_elastic_clip_minmax through the same matrix behind a 7 x 7 x 7 lattice of random
+displacements within 0.3 of the control spacing — in its row-shared form (the one launched) and, forced by the library option
+elastic_rows = 0, in its per-voxel form. All for the HX4 patch (32, 128, 128) with C = 2 int16 volumes of a resident
+(128, 256, 256) case and its body mask. The plain crop is the yardstick; the ratios are reported, nothing is gated.
 
 Each measurement is a child process of its own under its own time limit (10 warm-up launches, then 100 launches between HIP
 events: one pair per launch for the median, one pair round a second window of 100 back-to-back launches for the mean), the
-two kernels alternating over the rounds so that a drift of the machine shows as spread between rounds and not as a
+kernels alternating over the rounds so that a drift of the machine shows as spread between rounds and not as a
 difference between kernels. The first child that fails ends the run.
 
-    python tools/bench_patch_affine.py [--rounds 3] [--out profiles/patch_affine.txt]
+    python tools/bench_patch_affine.py [--rounds 3] [--out profiles/patch_elastic.txt]
     python tools/bench_patch_affine.py --step affine        # one measurement, one JSON line
 """
 import argparse
 import json
 import math
+import re
 import statistics
 import subprocess
 import sys
@@ -24,6 +28,9 @@ sys.path.insert(0, str(ROOT))
 SHAPE, PATCH, C_MOD = (128, 256, 256), (32, 128, 128), 2
 WARMUP, LAUNCHES = 10, 100
 STEP_LIMIT_S = 180
+GRID, FRACTION = (7, 7, 7), 0.3
+KINDS = (("plain", "gs_patch_clip_minmax (plain crop)"), ("affine", "gs_patch_affine_clip_minmax (30 deg x 1.1)"),
+         ("elastic", "gs_patch_elastic_clip_minmax, row-shared"), ("elastic_voxel", "gs_patch_elastic_clip_minmax, per voxel"))
 
 
 def matrix():
@@ -49,8 +56,14 @@ def step(kind):
     M = matrix()
     if kind == "plain":
         fn = lambda: ops.patch_clip_minmax(vols, mask, point, PATCH, *cols, out)
-    else:
+    elif kind == "affine":
         fn = lambda: ops.patch_affine_clip_minmax(vols, mask, point, PATCH, M, *cols, out)
+    else:
+        bound = np.array([FRACTION * (PATCH[a] - 1) / (GRID[a] - 3) for a in range(3)]).reshape(3, 1, 1, 1)
+        field = torch.from_numpy((2.0 * rng.random((3, *GRID)) - 1.0) * bound).to(dev)
+        if kind == "elastic_voxel":
+            ops.set_option("elastic_rows", 0)
+        fn = lambda: ops.patch_elastic_clip_minmax(vols, mask, point, PATCH, M, field, *cols, out)
     for _ in range(WARMUP):
         fn()
     torch.cuda.synchronize()
@@ -74,16 +87,16 @@ def step(kind):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["plain", "affine"])
+    ap.add_argument("--step", choices=[k for k, _ in KINDS])
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "patch_affine.txt"))
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "patch_elastic.txt"))
     args = ap.parse_args()
     if args.step:
         step(args.step)
         return
-    rows = {"plain": [], "affine": []}
+    rows = {k: [] for k, _ in KINDS}
     for r in range(args.rounds):
-        for kind in ("plain", "affine"):
+        for kind, _ in KINDS:
             done = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--step", kind], capture_output=True, text=True,
                                   timeout=STEP_LIMIT_S, cwd=str(ROOT))
             if done.returncode != 0:                   # nothing more is started on the device after a failure
@@ -98,23 +111,38 @@ def main():
         f"Resident {SHAPE[0]} x {SHAPE[1]} x {SHAPE[2]} case: {C_MOD} int16 volumes and a uint8 body mask; patch "
         f"({PATCH[0]}, {PATCH[1]}, {PATCH[2]}) around the centre, C = {C_MOD}: {out_bytes / 1e6:.2f} MB of fp32 output per launch.",
         f"Per measurement a process of its own: {WARMUP} warm-up launches, {LAUNCHES} launches with a HIP event pair each (median),",
-        f"then {LAUNCHES} back-to-back launches between one event pair (window mean, launch gaps included). {args.rounds} rounds, the two",
+        f"then {LAUNCHES} back-to-back launches between one event pair (window mean, launch gaps included). {args.rounds} rounds, the",
         "kernels alternating; the figures below are medians over the rounds, the per-round values follow.",
-        "The matrix is a 30 degree rotation about the depth axis times a source step of 1.1.",
+        "The matrix is a 30 degree rotation about the depth axis times a source step of 1.1; the elastic lattice has "
+        f"{GRID[0]} x {GRID[1]} x {GRID[2]}",
+        f"control points with random displacements within {FRACTION} of the control spacing. The per-voxel form of the elastic launch is",
+        "forced with the library option elastic_rows = 0; the row-shared form is what this patch and lattice launch by themselves.",
         "",
     ]
-    for kind, name in (("plain", "gs_patch_clip_minmax (plain crop)"), ("affine", "gs_patch_affine_clip_minmax (30 deg x 1.1)")):
+    for kind, name in KINDS:
         lines.append(f"{name:46s} median {med[kind]:8.1f} us  {out_bytes / med[kind] / 1e3:7.1f} GB/s of output   "
                      f"window mean {win[kind]:8.1f} us  {out_bytes / win[kind] / 1e3:7.1f} GB/s")
-    lines.append(f"ratio affine / plain: {med['affine'] / med['plain']:.2f} (median per launch), "
-                 f"{win['affine'] / win['plain']:.2f} (window mean). Reported, not gated.")
+    for kind in ("affine", "elastic", "elastic_voxel"):
+        lines.append(f"ratio {kind} / plain: {med[kind] / med['plain']:.2f} (median per launch), "
+                     f"{win[kind] / win['plain']:.2f} (window mean). Reported, not gated.")
+    lines.append(f"ratio elastic / affine, this session: {med['elastic'] / med['affine']:.2f} (median per launch), "
+                 f"{win['elastic'] / win['affine']:.2f} (window mean); per voxel / row-shared: "
+                 f"{med['elastic_voxel'] / med['elastic']:.2f}, {win['elastic_voxel'] / win['elastic']:.2f}.")
+    before = re.search(r"^gs_patch_affine_clip_minmax.*?median\s+([\d.]+) us.*?window mean\s+([\d.]+) us",
+                       (ROOT / "profiles" / "patch_affine.txt").read_text(), flags=re.M)
+    if before:
+        b_med, b_win = float(before.group(1)), float(before.group(2))
+        lines.append(f"Against the affine gather before the elastic variant existed (profiles/patch_affine.txt: {b_med} / {b_win} us): "
+                     f"affine now {med['affine'] / b_med:.2f} / {win['affine'] / b_win:.2f}, elastic {med['elastic'] / b_med:.2f} / "
+                     f"{win['elastic'] / b_win:.2f}.")
     lines.append("")
-    for kind in ("plain", "affine"):
+    for kind, _ in KINDS:
         for r, row in enumerate(rows[kind]):
-            lines.append(f"round {r} {kind:6s} median {row['median_us']:8.1f} us  min {row['min_us']:8.1f} us  "
+            lines.append(f"round {r} {kind:13s} median {row['median_us']:8.1f} us  min {row['min_us']:8.1f} us  "
                          f"window mean {row['window_mean_us']:8.1f} us")
-    lines.append("Not measured: kernel times from a profiler trace, achieved HBM read bandwidth, and a blockIdx.y = modality mapping "
-                 "of the gather (not built).")
+    lines.append("Not measured: kernel times from a profiler trace, achieved HBM read bandwidth, LDS bank conflicts of the row table, "
+                 "other patch sizes and lattices (short rows, wide lattices), the upload of the fields, and the effect on a training "
+                 "step (a 3-D step is about 50 ms; these launches are tens of microseconds per sample).")
     text = "\n".join(lines) + "\n"
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(text)
