@@ -36,6 +36,10 @@
 // per-voxel chain (one device function, clip_minmax), with centred padding up to a target shape in between; the pad value is
 // the minimum of the masked volume over the case, NaN-propagating like np.min, each mask padded with its own minimum. Two
 // launches: 256 partial minima per volume / mask, then the apply pass, whose workgroups fold the partials in one fixed tree.
+//
+// ModTable — the per-modality columns (volume pointer, dtype, outside, divisor, lo, hi) that every kernel argument struct
+// of these entries begins with. One host function, fill_table, checks the caller's arrays and fills it; check_patch_fits and
+// patch_start (the start clamp, device side) are the other rules the entries share.
 #include <limits>
 #include "common.hpp"
 
@@ -270,10 +274,45 @@ long long range_len(int D, int H, int W, const int32_t* p) {
 
 constexpr int PC_MAX = GS_PATCH_MAX_MODALITIES;
 
-struct ClipK {
+// the per-modality columns, the leading base of ClipK, AffK and PrepK: the kernels read k.vol[c], k.lo[c], ...
+struct ModTable {
   const void* vol[PC_MAX];
   int dtype[PC_MAX];
   float outside[PC_MAX], divisor[PC_MAX], lo[PC_MAX], hi[PC_MAX];
+};
+
+// checks the C caller-side entries and fills all PC_MAX slots, the unused ones from slot 0 (no kernel reads them)
+int fill_table(const char* who, ModTable& t, const void* const* vols, const int32_t* dtypes, const float* outside,
+               const float* divisor, const float* lo, const float* hi, int C) {
+  for (int c = 0; c < PC_MAX; ++c) {
+    const int s = c < C ? c : 0;
+    GS_REQUIRE(vols[s], "%s: null volume %d", who, s);
+    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16, "%s: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", who,
+               dtypes[s], s);
+    GS_REQUIRE(hi[s] > lo[s], "%s: clip range [%g, %g] of volume %d is empty", who, lo[s], hi[s], s);
+    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "%s: divisor %g of volume %d", who, divisor[s], s);
+    t.vol[c] = vols[s];
+    t.dtype[c] = dtypes[s];
+    t.outside[c] = outside[s]; t.divisor[c] = divisor[s]; t.lo[c] = lo[s]; t.hi[c] = hi[s];
+  }
+  return 0;
+}
+
+int check_patch_fits(const char* who, int D, int H, int W, const int32_t* p) {
+  GS_REQUIRE(D > 0 && H > 0 && W > 0 && p[0] > 0 && p[1] > 0 && p[2] > 0 && p[0] <= D && p[1] <= H && p[2] <= W,
+             "%s: patch %d x %d x %d does not fit the %d x %d x %d volume", who, p[0], p[1], p[2], D, H, W);
+  return 0;
+}
+
+// the patch start on one axis: point - patch / 2, clamped to [0, size - patch], so that no point reads outside the volume
+__device__ __forceinline__ int patch_start(int point, int patch, int size) {
+  int v = point - patch / 2;
+  const int top = size - patch;
+  v = v > top ? top : v;
+  return v < 0 ? 0 : v;
+}
+
+struct ClipK : ModTable {
   const uint8_t* mask;
   const int32_t* point;
   int D, H, W, pd, ph, pw;
@@ -299,12 +338,7 @@ __global__ __launch_bounds__(256) void patch_clip_minmax_kernel(const ClipK k, f
   const int size[3] = {k.D, k.H, k.W}, patch[3] = {k.pd, k.ph, k.pw};
   int s[3];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    int v = k.point[a] - patch[a] / 2;
-    const int top = size[a] - patch[a];
-    v = v > top ? top : v;
-    s[a] = v < 0 ? 0 : v;
-  }
+  for (int a = 0; a < 3; ++a) s[a] = patch_start(k.point[a], patch[a], size[a]);
   const void* vol = k.vol[c];
   const int dtype = k.dtype[c];
   const float outside = k.outside[c], divisor = k.divisor[c], lo = k.lo[c], hi = k.hi[c];
@@ -326,10 +360,7 @@ __global__ __launch_bounds__(256) void patch_clip_minmax_kernel(const ClipK k, f
 // the in-bounds tests and the mask bytes are per voxel; the modalities are looped inside the thread, each plane's store
 // coalesced. hipcc contracts a * b + c to an fma by default, through __fmul_rn / __fadd_rn too (slidewin.hip), so the
 // coordinate and lerp bodies switch contraction off.
-struct AffK {
-  const void* vol[PC_MAX];
-  int dtype[PC_MAX];
-  float outside[PC_MAX], divisor[PC_MAX], lo[PC_MAX], hi[PC_MAX];
+struct AffK : ModTable {
   const uint8_t* mask;             // nullptr: no mask (gs_patch_affine)
   const int32_t* point;            // device focal point; nullptr: start[] is the patch start
   int start[3];
@@ -488,12 +519,7 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const K k, float* out
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     int s = k.start[a];
-    if (k.point) {
-      s = k.point[a] - patch[a] / 2;
-      const int top = size[a] - patch[a];
-      s = s > top ? top : s;
-      s = s < 0 ? 0 : s;
-    }
+    if (k.point) s = patch_start(k.point[a], patch[a], size[a]);
     const double c = (double)(patch[a] - 1) * 0.5;       // exact
     r[a] = (double)o[a] - c;                             // exact
     base[a] = (double)s + c;                             // exact
@@ -565,6 +591,13 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const K k, float* out
   }
 }
 
+// the one launch line of the gather: E and K come with the caller's form, `clip` picks CLIP
+template <int E, typename K>
+void launch_gather(const K& k, bool clip, dim3 g, size_t lds, hipStream_t st, float* out) {
+  void (*kernel)(const K, float*) = clip ? patch_affine_kernel<true, E, K> : patch_affine_kernel<false, E, K>;
+  hipLaunchKernelGGL(kernel, g, dim3(256), lds, st, k, out);
+}
+
 // grid (nullptr: no elastic part) and field: the lattice of gs_patch_elastic*, checked by the caller
 int launch_affine(AffK& k, const int32_t* patch, const double* M, const int32_t* grid, const double* field, float* out,
                   bool clip, void* stream) {
@@ -574,10 +607,9 @@ int launch_affine(AffK& k, const int32_t* patch, const double* M, const int32_t*
   const long long blocks = (k.n + 255) / 256;            // one voxel per thread
   GS_REQUIRE(blocks <= 0x7fffffffLL, "gs_patch_affine: %lld voxels do not fit one grid", k.n);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 g((unsigned)blocks), b(256);
+  const dim3 g((unsigned)blocks);
   if (!grid) {
-    if (clip) hipLaunchKernelGGL((patch_affine_kernel<true, ELA_NONE, AffK>), g, b, 0, st, k, out);
-    else hipLaunchKernelGGL((patch_affine_kernel<false, ELA_NONE, AffK>), g, b, 0, st, k, out);
+    launch_gather<ELA_NONE>(k, clip, g, 0, st, out);
   } else {
     ElaK e;
     static_cast<AffK&>(e) = k;
@@ -587,14 +619,8 @@ int launch_affine(AffK& k, const int32_t* patch, const double* M, const int32_t*
     const size_t table = (size_t)(rows_all < rows_wg ? rows_all : rows_wg) * 3 * grid[2] * sizeof(double);
     int fits = gs_opt(GS_OPT_ELASTIC_ROWS);
     fits = fits < 0 ? 0 : (fits > 65536 ? 65536 : fits);
-    if (table <= (size_t)fits) {
-      if (clip) hipLaunchKernelGGL((patch_affine_kernel<true, ELA_ROWS, ElaK>), g, b, table, st, e, out);
-      else hipLaunchKernelGGL((patch_affine_kernel<false, ELA_ROWS, ElaK>), g, b, table, st, e, out);
-    } else {
-      const size_t lattice = (size_t)3 * grid[0] * grid[1] * grid[2] * sizeof(double);
-      if (clip) hipLaunchKernelGGL((patch_affine_kernel<true, ELA_VOXEL, ElaK>), g, b, lattice, st, e, out);
-      else hipLaunchKernelGGL((patch_affine_kernel<false, ELA_VOXEL, ElaK>), g, b, lattice, st, e, out);
-    }
+    if (table <= (size_t)fits) launch_gather<ELA_ROWS>(e, clip, g, table, st, out);
+    else launch_gather<ELA_VOXEL>(e, clip, g, (size_t)3 * grid[0] * grid[1] * grid[2] * sizeof(double), st, out);
   }
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -625,10 +651,7 @@ inline bool finite9(const double* M) {
 constexpr int VP_MAX_MASKS = 1 + GS_VM_MAX_LABELS;
 constexpr int VP_PARTS = 256;              // workgroups of the minimum pass per volume / mask
 
-struct PrepK {
-  const void* vol[PC_MAX];
-  int dtype[PC_MAX];
-  float outside[PC_MAX], divisor[PC_MAX], lo[PC_MAX], hi[PC_MAX];
+struct PrepK : ModTable {
   const uint8_t* mask[VP_MAX_MASKS];
   uint8_t* mask_out[VP_MAX_MASKS];
   int C, M;
@@ -719,9 +742,7 @@ extern "C" int gs_voxel_draw(const uint8_t* mask, const void* weight, int32_t wd
   GS_REQUIRE(mask && patch && out && ws, "gs_voxel_draw: null argument");
   GS_REQUIRE(!weight || wdtype == GS_VOL_F32 || wdtype == GS_VOL_I16,
              "gs_voxel_draw: weight dtype %d (GS_VOL_F32 / GS_VOL_I16)", wdtype);
-  GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
-                 patch[2] <= W,
-             "gs_voxel_draw: patch %d x %d x %d does not fit the %d x %d x %d volume", patch[0], patch[1], patch[2], D, H, W);
+  if (const int rc = check_patch_fits("gs_voxel_draw", D, H, W, patch)) return rc;
   GS_REQUIRE(u >= 0.0 && u < 1.0, "gs_voxel_draw: u = %.17g is not in [0, 1)", u);
   GS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "gs_voxel_draw: the workspace must be 8-byte aligned");
   GS_REQUIRE(!focal_a || (dims_a && proportion), "gs_voxel_draw: a focal point needs A's dims and the proportions");
@@ -761,22 +782,9 @@ extern "C" int gs_patch_clip_minmax(const void* const* vols, const int32_t* dtyp
   GS_REQUIRE(vols && dtypes && mask && patch && point && outside && divisor && lo && hi && out,
              "gs_patch_clip_minmax: null argument");
   GS_REQUIRE(C >= 1 && C <= PC_MAX, "gs_patch_clip_minmax: between 1 and %d modalities per call; got %d", PC_MAX, C);
-  GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
-                 patch[2] <= W,
-             "gs_patch_clip_minmax: patch %d x %d x %d does not fit the %d x %d x %d volume", patch[0], patch[1], patch[2],
-             D, H, W);
+  if (const int rc = check_patch_fits("gs_patch_clip_minmax", D, H, W, patch)) return rc;
   ClipK k;
-  for (int c = 0; c < PC_MAX; ++c) {
-    const int s = c < C ? c : 0;
-    GS_REQUIRE(vols[s], "gs_patch_clip_minmax: null volume %d", s);
-    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16,
-               "gs_patch_clip_minmax: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", dtypes[s], s);
-    GS_REQUIRE(hi[s] > lo[s], "gs_patch_clip_minmax: clip range [%g, %g] of volume %d is empty", lo[s], hi[s], s);
-    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "gs_patch_clip_minmax: divisor %g of volume %d", divisor[s], s);
-    k.vol[c] = vols[s];
-    k.dtype[c] = dtypes[s];
-    k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
-  }
+  if (const int rc = fill_table("gs_patch_clip_minmax", k, vols, dtypes, outside, divisor, lo, hi, C)) return rc;
   k.mask = mask;
   k.point = point;
   k.D = D; k.H = H; k.W = W;
@@ -797,22 +805,10 @@ int gather_clip_minmax(const char* who, const void* const* vols, const int32_t* 
                        const float* hi, float* out, void* stream) {
   GS_REQUIRE(vols && dtypes && mask && point && patch && M && outside && divisor && lo && hi && out, "%s: null argument", who);
   GS_REQUIRE(C >= 1 && C <= PC_MAX, "%s: between 1 and %d modalities per call; got %d", who, PC_MAX, C);
-  GS_REQUIRE(D > 0 && H > 0 && W > 0 && patch[0] > 0 && patch[1] > 0 && patch[2] > 0 && patch[0] <= D && patch[1] <= H &&
-                 patch[2] <= W,
-             "%s: patch %d x %d x %d does not fit the %d x %d x %d volume", who, patch[0], patch[1], patch[2], D, H, W);
+  if (const int rc = check_patch_fits(who, D, H, W, patch)) return rc;
   GS_REQUIRE(finite9(M), "%s: the matrix has a non-finite entry", who);
   AffK k;
-  for (int c = 0; c < PC_MAX; ++c) {
-    const int s = c < C ? c : 0;
-    GS_REQUIRE(vols[s], "%s: null volume %d", who, s);
-    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16, "%s: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", who,
-               dtypes[s], s);
-    GS_REQUIRE(hi[s] > lo[s], "%s: clip range [%g, %g] of volume %d is empty", who, lo[s], hi[s], s);
-    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "%s: divisor %g of volume %d", who, divisor[s], s);
-    k.vol[c] = vols[s];
-    k.dtype[c] = dtypes[s];
-    k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
-  }
+  if (const int rc = fill_table(who, k, vols, dtypes, outside, divisor, lo, hi, C)) return rc;
   k.mask = mask;
   k.point = point;
   k.start[0] = k.start[1] = k.start[2] = 0;
@@ -825,9 +821,7 @@ int gather_raw(const char* who, const void* vol, int32_t dtype, int32_t D, int32
                void* stream) {
   GS_REQUIRE(vol && start && size && M && out, "%s: null argument", who);
   GS_REQUIRE(dtype == GS_VOL_F32 || dtype == GS_VOL_I16, "%s: dtype %d (GS_VOL_F32 / GS_VOL_I16)", who, dtype);
-  GS_REQUIRE(D > 0 && H > 0 && W > 0 && size[0] > 0 && size[1] > 0 && size[2] > 0 && size[0] <= D && size[1] <= H &&
-                 size[2] <= W,
-             "%s: patch %d x %d x %d does not fit the %d x %d x %d volume", who, size[0], size[1], size[2], D, H, W);
+  if (const int rc = check_patch_fits(who, D, H, W, size)) return rc;
   GS_REQUIRE(start[0] >= 0 && start[1] >= 0 && start[2] >= 0 && start[0] <= D - size[0] && start[1] <= H - size[1] &&
                  start[2] <= W - size[2],
              "%s: patch [%d+%d, %d+%d, %d+%d] outside the %d x %d x %d volume", who, start[0], size[0], start[1], size[1],
@@ -893,17 +887,7 @@ extern "C" int gs_volume_prepare(const void* const* vols, const int32_t* dtypes,
              "gs_volume_prepare: volume %d x %d x %d, target %d x %d x %d", D, H, W, target[0], target[1], target[2]);
   GS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3) == 0, "gs_volume_prepare: the workspace must be 4-byte aligned");
   PrepK k;
-  for (int c = 0; c < PC_MAX; ++c) {
-    const int s = c < C ? c : 0;
-    GS_REQUIRE(vols[s], "gs_volume_prepare: null volume %d", s);
-    GS_REQUIRE(dtypes[s] == GS_VOL_F32 || dtypes[s] == GS_VOL_I16,
-               "gs_volume_prepare: dtype %d of volume %d (GS_VOL_F32 / GS_VOL_I16)", dtypes[s], s);
-    GS_REQUIRE(hi[s] > lo[s], "gs_volume_prepare: clip range [%g, %g] of volume %d is empty", lo[s], hi[s], s);
-    GS_REQUIRE(divisor[s] != 0.f && divisor[s] == divisor[s], "gs_volume_prepare: divisor %g of volume %d", divisor[s], s);
-    k.vol[c] = vols[s];
-    k.dtype[c] = dtypes[s];
-    k.outside[c] = outside[s]; k.divisor[c] = divisor[s]; k.lo[c] = lo[s]; k.hi[c] = hi[s];
-  }
+  if (const int rc = fill_table("gs_volume_prepare", k, vols, dtypes, outside, divisor, lo, hi, C)) return rc;
   for (int m = 0; m < VP_MAX_MASKS; ++m) {
     const int s = m < M ? m : 0;
     GS_REQUIRE(masks[s] && masks_out[s], "gs_volume_prepare: null mask %d", s);

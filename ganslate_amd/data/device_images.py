@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .multimodal_images import RawImageSample, TapTable, bicubic_taps
+from .resident_cache import ResidentCache
 
 
 class StackItem(NamedTuple):
@@ -27,7 +28,7 @@ class StackItem(NamedTuple):
     hwc: bool = True                 # False: src is (c, in_h, in_w), planes apart; the datasets store (H, W[, C])
 
 
-class DeviceMultiModalImagePipeline:
+class DeviceMultiModalImagePipeline(ResidentCache):
     """callable(raw batch) -> {"A": fp32 [N, C_A, H, W] on the device, "B": fp32 [N, front + C_B + back, H, W],
     "metadata": as it came} for MultiModalImageDataset and MultiModalImageValTestDataset. Images are uploaded on first use
     and stay resident under `max_resident_bytes` (beyond it: uploaded per use); the tap tables of every (stored size,
@@ -35,32 +36,18 @@ class DeviceMultiModalImagePipeline:
     tensor per batch; nothing synchronises."""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
+        super().__init__(device, ops, max_resident_bytes)
         self.dataset = dataset
-        self.device = torch.device(device)
-        self._ops = ops
         self.size = tuple(int(v) for v in dataset.size)               # (H, W)
-        self.resident, self.tables = {}, {}
-        self.resident_bytes, self.max_resident_bytes = 0, max_resident_bytes
+        self.tables = {}
         self.uploads = 0
 
-    @property
-    def ops(self):
-        if self._ops is None:
-            from ..nn.native.backend import get_ops
-            self._ops = get_ops()
-        return self._ops
-
     def image(self, name, index):
-        key = (name, index)
-        v = self.resident.get(key)
-        if v is None:
-            v = torch.from_numpy(np.array(self.dataset.load(name, index))).to(self.device)
+        def upload():
             self.uploads += 1
-            nbytes = v.numel() * v.element_size()
-            if self.resident_bytes + nbytes <= self.max_resident_bytes:      # beyond the budget: upload per use
-                self.resident[key] = v
-                self.resident_bytes += nbytes
-        return v
+            return torch.from_numpy(np.array(self.dataset.load(name, index))).to(self.device)
+
+        return self._get((name, index), upload)
 
     def taps(self, n_in, n_out):
         key = (int(n_in), int(n_out))

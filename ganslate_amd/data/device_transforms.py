@@ -25,6 +25,7 @@ from typing import Any, NamedTuple
 
 import numpy as np
 import torch
+from torch.utils.data.dataloader import default_collate
 
 PRECISION_BITS = 32 - 8 - 2
 
@@ -114,8 +115,12 @@ def draw_params():
 
 
 def collate_raw(samples):
-    """DataLoader collate_fn: images of a batch may have different sizes, so they stay a list per key"""
-    return {k: [s[k] for s in samples] for k in samples[0]}
+    """DataLoader collate_fn of every raw dataset: images or cases of a batch may have different sizes, so they stay a list
+    per key; only "metadata", where a sample carries it, is collated the default way"""
+    out = {k: [s[k] for s in samples] for k in samples[0] if k != "metadata"}
+    if "metadata" in samples[0]:
+        out["metadata"] = default_collate([s["metadata"] for s in samples])
+    return out
 
 
 class DeviceImagePipeline:

@@ -8,6 +8,31 @@ field takes gs_patch_elastic there; the fields of a batch are uploaded in one co
 import numpy as np
 import torch
 
+from .resident_cache import ResidentCache
+
+
+class ResidentVolumes(ResidentCache):
+    """the resident volumes and masks of one dataset, as the kernels take them: a mask as uint8 0 / 1, a volume as fp32 or
+    int16"""
+
+    def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
+        super().__init__(device, ops, max_resident_bytes)
+        self.dataset = dataset
+
+    def _host(self, name, index):
+        return torch.from_numpy(np.array(self.dataset.load(name, index)))           # a copy out of the memory map
+
+    def volume(self, name, index, mask=False):
+        def upload():
+            host = self._host(name, index)
+            if mask:
+                host = (host != 0).to(torch.uint8)
+            elif host.dtype not in (torch.float32, torch.int16):
+                host = host.float()
+            return host.to(self.device)
+
+        return self._get((name, index), upload)
+
 
 def upload_fields(items, device):
     """{id(field): float64 device tensor [3, G0, G1, G2]} of every elastic field the raw samples carry: one host array, one
@@ -22,38 +47,16 @@ def upload_fields(items, device):
     return {key: dev[n] for n, key in enumerate(fields)}
 
 
-class DeviceVolumePipeline:
+class DeviceVolumePipeline(ResidentVolumes):
     """callable(raw batch) -> {"A": fp32 [N, 1, *patch] on the device, "B": ...}"""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
-        self.dataset = dataset
-        self.device = torch.device(device)
-        self._ops = ops
+        super().__init__(dataset, device, ops, max_resident_bytes)
         self.size = [int(v) for v in dataset.patch_sampler.patch_size]       # (d, h, w); d = 1 for 2-D patch sizes
         self.squeeze = dataset.patch_sampler.dims == 2
-        self.resident = {}
-        self.resident_bytes, self.max_resident_bytes = 0, max_resident_bytes
 
-    @property
-    def ops(self):
-        if self._ops is None:
-            from ..nn.native.backend import get_ops
-            self._ops = get_ops()
-        return self._ops
-
-    def volume(self, domain, index):
-        key = (domain, index)
-        v = self.resident.get(key)
-        if v is None:
-            host = self.dataset.load(domain, index)
-            if host.dtype not in (torch.float32, torch.int16):
-                host = host.float()
-            v = host.to(self.device)
-            nbytes = v.numel() * v.element_size()
-            if self.resident_bytes + nbytes <= self.max_resident_bytes:      # beyond the budget: upload per use
-                self.resident[key] = v
-                self.resident_bytes += nbytes
-        return v
+    def _host(self, domain, index):
+        return self.dataset.load(domain, index)              # torch tensors, keyed by domain
 
     def __call__(self, batch):
         from .volume_datasets import RawPatch
@@ -82,7 +85,7 @@ class DeviceVolumePipeline:
         return out
 
 
-class DeviceMultiModalPipeline:
+class DeviceMultiModalPipeline(ResidentVolumes):
     """callable(raw batch) -> {"A": fp32 [N, C_A, *patch] on the device, "B": fp32 [N, C_B, *patch]} for
     MultiModalVolumeDataset (data/multimodal_volumes.py): volumes and body masks resident in HBM, per iteration only case
     indices and uniforms arrive. Per sample: one gs_voxel_draw per domain when unpaired (B's reads A's point from device
@@ -94,37 +97,10 @@ class DeviceMultiModalPipeline:
     train_dataset.py:106-188 with datasets/utils/patch_samplers.py."""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
-        self.dataset = dataset
-        self.device = torch.device(device)
-        self._ops = ops
+        super().__init__(dataset, device, ops, max_resident_bytes)
         self.size = [int(v) for v in dataset.patch_size]
-        self.resident = {}
-        self.resident_bytes, self.max_resident_bytes = 0, max_resident_bytes
         self.checked = set()
         self.points = None          # int32 [N, 2, 4] of the last batch: (z, y, x, fallback_used) per sample and domain
-
-    @property
-    def ops(self):
-        if self._ops is None:
-            from ..nn.native.backend import get_ops
-            self._ops = get_ops()
-        return self._ops
-
-    def volume(self, name, index, mask=False):
-        key = (name, index)
-        v = self.resident.get(key)
-        if v is None:
-            host = torch.from_numpy(np.array(self.dataset.load(name, index)))       # a copy out of the memory map
-            if mask:
-                host = (host != 0).to(torch.uint8)
-            elif host.dtype not in (torch.float32, torch.int16):
-                host = host.float()
-            v = host.to(self.device)
-            nbytes = v.numel() * v.element_size()
-            if self.resident_bytes + nbytes <= self.max_resident_bytes:      # beyond the budget: upload per use
-                self.resident[key] = v
-                self.resident_bytes += nbytes
-        return v
 
     def case(self, domain, index):
         """(mask, weight or None, [volumes]) of one case of a domain; on first use the count of the kernel's own draw tells
@@ -181,7 +157,7 @@ class DeviceMultiModalPipeline:
         return out
 
 
-class DeviceWholeVolumePipeline:
+class DeviceWholeVolumePipeline(ResidentVolumes):
     """callable(raw batch) -> {"A": fp32 [N, C_A, Do, Ho, Wo] on the device, "B": fp32 [N, before + C_B + after, ...],
     "masks": {label: uint8 [N, 1, Do, Ho, Wo] on the device}, "metadata": as it came} for MultiModalVolumeValTestDataset
     (data/multimodal_valtest.py): raw volumes and masks resident in HBM under the same `max_resident_bytes` rule as the
@@ -193,50 +169,20 @@ class DeviceWholeVolumePipeline:
     val_test_dataset.py:86-187 with ganslate/data/utils/body_mask.py."""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
-        self.dataset = dataset
-        self.device = torch.device(device)
-        self._ops = ops
-        self.resident = {}
-        self.resident_bytes, self.max_resident_bytes = 0, max_resident_bytes
-
-    @property
-    def ops(self):
-        if self._ops is None:
-            from ..nn.native.backend import get_ops
-            self._ops = get_ops()
-        return self._ops
-
-    def _keep(self, key, v):
-        nbytes = v.numel() * v.element_size()
-        if self.resident_bytes + nbytes <= self.max_resident_bytes:          # beyond the budget: upload / generate per use
-            self.resident[key] = v
-            self.resident_bytes += nbytes
-        return v
-
-    def volume(self, name, index, mask=False):
-        key = (name, index)
-        v = self.resident.get(key)
-        if v is None:
-            host = torch.from_numpy(np.array(self.dataset.load(name, index)))       # a copy out of the memory map
-            if mask:
-                host = (host != 0).to(torch.uint8)
-            elif host.dtype not in (torch.float32, torch.int16):
-                host = host.float()
-            v = self._keep(key, host.to(self.device))
-        return v
+        super().__init__(dataset, device, ops, max_resident_bytes)
 
     def body(self, index):
         ds = self.dataset
         if not ds.generates(index):
             return self.volume(ds.body_mask, index, mask=True)
-        key = (None, index)                                  # no file has this name
-        v = self.resident.get(key)
-        if v is None:
+
+        def generate():
             v, info = self.ops.body_mask(self.volume(ds.body_mask_from, index), ds.body_mask_threshold)
             if int(info[0].item()) == 0:
                 raise ds.empty_body_error(index)
-            self._keep(key, v)
-        return v
+            return v
+
+        return self._get((None, index), generate)            # no file has this name
 
     def __call__(self, batch):
         from .multimodal_valtest import RawWholeCase

@@ -39,9 +39,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 from torch.utils.data import Dataset
-from torch.utils.data.dataloader import default_collate
 
 from .. import configs
+from .device_transforms import collate_raw
 from .multimodal_volumes import _field
 from .utils.normalization import min_max_denormalize, min_max_normalize
 
@@ -137,13 +137,6 @@ class RawImageSample:
 
     def __init__(self, domain, index, keys=None):
         self.domain, self.index, self.keys = domain, int(index), dict(keys or {})
-
-
-def collate_raw(samples):
-    out = {k: [s[k] for s in samples] for k in samples[0] if k != "metadata"}
-    if "metadata" in samples[0]:
-        out["metadata"] = default_collate([s["metadata"] for s in samples])
-    return out
 
 
 class _MultiModalImages(Dataset):

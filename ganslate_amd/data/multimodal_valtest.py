@@ -31,9 +31,9 @@ from typing import Any, Dict, Optional, Tuple
 import numpy as np
 import torch
 from torch.utils.data import Dataset
-from torch.utils.data.dataloader import default_collate
 
 from .. import configs
+from .device_transforms import collate_raw
 from .multimodal_volumes import _field
 from .utils.body_mask import get_body_mask
 from .utils.normalization import min_max_denormalize, min_max_normalize
@@ -66,12 +66,6 @@ class RawWholeCase:
 
     def __init__(self, index):
         self.index = int(index)
-
-
-def collate_raw(samples):
-    out = {k: [s[k] for s in samples] for k in samples[0] if k != "metadata"}
-    out["metadata"] = default_collate([s["metadata"] for s in samples])
-    return out
 
 
 class MultiModalVolumeValTestDataset(Dataset):

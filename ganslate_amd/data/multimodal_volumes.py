@@ -34,6 +34,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .. import configs
+from .device_transforms import collate_raw
 from .utils.normalization import min_max_normalize
 from .utils.patch_affine import check_elastic, draw_set, matrix_tuple, parse_augmentation, sample_patch
 
@@ -130,10 +131,6 @@ class RawCase:
         self.domain, self.index, self.u = domain, int(index), (None if u is None else float(u))
         self.matrix = None if matrix is None else matrix_tuple(matrix)
         self.field = field
-
-
-def collate_raw(samples):
-    return {k: [s[k] for s in samples] for k in samples[0]}
 
 
 def _field(node, name, default=None):

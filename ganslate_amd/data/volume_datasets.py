@@ -26,6 +26,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .. import configs
+from .device_transforms import collate_raw
 from .utils.normalization import z_score_normalize
 from .utils.patch_affine import check_elastic, draw_set, matrix_tuple, parse_augmentation, sample_patch
 from .utils.stochastic_focal_patching import StochasticFocalPatchSampler
@@ -56,10 +57,6 @@ class RawPatch:
         self.domain, self.index, self.start = domain, int(index), tuple(int(v) for v in start)
         self.matrix = None if matrix is None else matrix_tuple(matrix)
         self.field = field
-
-
-def collate_raw(samples):
-    return {k: [s[k] for s in samples] for k in samples[0]}
 
 
 class UnpairedVolumeDataset(Dataset):

@@ -1104,28 +1104,37 @@ class HipOps(TwinSplit):
                                        *mask.shape, (C.c_int32 * 3)(*[int(v) for v in patch]), float(u), _ptr(focal_A), da,
                                        pr, _ptr(out), _ptr(ws), _stream()), "gs_voxel_draw")
 
+    def _mod_table(self, who, volumes, mask, outside, divisor, lo, hi):
+        """the per-modality columns of one case as gs_* arguments (csrc/volsample.hip ModTable): checks the mask, every
+        volume against it and one outside / divisor / lo / hi entry per volume -> (n, pointers, dtypes, the four columns)"""
+        n = len(volumes)
+        if n < 1:
+            raise ValueError(f"{who}: at least one volume")
+        self._case_volume("mask", mask, (torch.uint8,))
+        for i, v in enumerate(volumes):
+            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
+            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
+        cols = [(C.c_float * n)(*[float(v) for v in vals]) for vals in (outside, divisor, lo, hi)]
+        return (n, (C.c_void_p * n)(*[v.data_ptr() for v in volumes]),
+                (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes]), cols)
+
+    @staticmethod
+    def _out_f32(out, shape):
+        shape = tuple(int(v) for v in shape)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == shape):
+            raise ValueError(f"out: expected a dense fp32 device tensor of shape {shape}")
+
     def patch_clip_minmax(self, volumes, mask, point, patch, outside, divisor, lo, hi, out):
         """gs_patch_clip_minmax: out [C, d, h, w] fp32 = the patch around `point` (device int32[3]) of every volume of one
         case: where(mask, v, outside) / divisor, clamped to [lo, hi], min-max normalised to [-1, 1]. volumes: C fp32 / int16
         (D, H, W) device tensors; outside / divisor / lo / hi: C host numbers each."""
-        n = len(volumes)
-        if n < 1:
-            raise ValueError("patch_clip_minmax: at least one volume")
-        self._case_volume("mask", mask, (torch.uint8,))
-        for i, v in enumerate(volumes):
-            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        n, ptrs, dts, cols = self._mod_table("patch_clip_minmax", volumes, mask, outside, divisor, lo, hi)
         self._point("point", point, 3)
-        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
-            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == (n, *[int(v) for v in patch])):
-            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *[int(v) for v in patch])}")
-        fl = lambda vals: (C.c_float * max(n, 1))(*[float(v) for v in vals])
-        ptrs = (C.c_void_p * max(n, 1))(*[v.data_ptr() for v in volumes])
-        dts = (C.c_int32 * max(n, 1))(*[self.VOL_DTYPES[v.dtype] for v in volumes])
+        self._out_f32(out, (n, *patch))
         L.check(self.lib.gs_patch_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, (C.c_int32 * 3)(*[int(v) for v in patch]),
-                                              _ptr(point), fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
-                "gs_patch_clip_minmax")
+                                              _ptr(point), *cols, _ptr(out), _stream()), "gs_patch_clip_minmax")
 
     @staticmethod
     def _matrix(matrix):
@@ -1133,40 +1142,6 @@ class HipOps(TwinSplit):
         if len(m) != 9:
             raise ValueError(f"matrix: expected 9 numbers (3 x 3, row-major); got {len(m)}")
         return (C.c_double * 9)(*m)
-
-    def patch_affine_clip_minmax(self, volumes, mask, point, patch, matrix, outside, divisor, lo, hi, out):
-        """gs_patch_affine_clip_minmax: patch_clip_minmax through a 3 x 3 matrix — the trilinear gather of
-        data/utils/patch_affine.py (mask, then interpolate), then the same chain. matrix: 9 numbers, row-major, or 3 x 3."""
-        n = len(volumes)
-        if n < 1:
-            raise ValueError("patch_affine_clip_minmax: at least one volume")
-        self._case_volume("mask", mask, (torch.uint8,))
-        for i, v in enumerate(volumes):
-            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
-        self._point("point", point, 3)
-        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
-            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == (n, *[int(v) for v in patch])):
-            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *[int(v) for v in patch])}")
-        fl = lambda vals: (C.c_float * n)(*[float(v) for v in vals])
-        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in volumes])
-        dts = (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes])
-        L.check(self.lib.gs_patch_affine_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, _ptr(point),
-                                                     (C.c_int32 * 3)(*[int(v) for v in patch]), self._matrix(matrix),
-                                                     fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
-                "gs_patch_affine_clip_minmax")
-
-    def patch_affine(self, volume, start, size, matrix, fill, out):
-        """gs_patch_affine: out (d, h, w) fp32 = the raw trilinear gather of the window [start, start + size) of a dense
-        (D, H, W) fp32 / int16 device volume through `matrix`, `fill` outside the volume; no mask, no normalisation"""
-        self._case_volume("volume", volume, tuple(self.VOL_DTYPES))
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == tuple(int(v) for v in size)):
-            raise ValueError(f"out: expected a dense fp32 device tensor of shape {tuple(int(v) for v in size)}")
-        st, sz = (C.c_int32 * 3)(*[int(v) for v in start]), (C.c_int32 * 3)(*[int(v) for v in size])
-        L.check(self.lib.gs_patch_affine(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
-                                         self._matrix(matrix), float(fill), _ptr(out), _stream()), "gs_patch_affine")
 
     @staticmethod
     def _lattice(field):
@@ -1177,41 +1152,43 @@ class HipOps(TwinSplit):
             raise ValueError(f"field: expected a contiguous float64 device tensor of shape [3, G0, G1, G2]; got {got}")
         return (C.c_int32 * 3)(*[int(v) for v in field.shape[1:]]), _ptr(field)
 
+    def _gather_clip_minmax(self, sym, volumes, mask, point, patch, matrix, lattice, outside, divisor, lo, hi, out):
+        """gs_patch_affine_clip_minmax (lattice = ()) or gs_patch_elastic_clip_minmax (lattice = (grid, field pointer))"""
+        n, ptrs, dts, cols = self._mod_table(sym[3:], volumes, mask, outside, divisor, lo, hi)
+        self._point("point", point, 3)
+        self._out_f32(out, (n, *patch))
+        L.check(getattr(self.lib, sym)(ptrs, dts, n, _ptr(mask), *mask.shape, _ptr(point),
+                                       (C.c_int32 * 3)(*[int(v) for v in patch]), self._matrix(matrix), *lattice, *cols,
+                                       _ptr(out), _stream()), sym)
+
+    def _gather_raw(self, sym, volume, start, size, matrix, lattice, fill, out):
+        """gs_patch_affine (lattice = ()) or gs_patch_elastic (lattice = (grid, field pointer))"""
+        self._case_volume("volume", volume, tuple(self.VOL_DTYPES))
+        self._out_f32(out, size)
+        st, sz = (C.c_int32 * 3)(*[int(v) for v in start]), (C.c_int32 * 3)(*[int(v) for v in size])
+        L.check(getattr(self.lib, sym)(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
+                                       self._matrix(matrix), *lattice, float(fill), _ptr(out), _stream()), sym)
+
+    def patch_affine_clip_minmax(self, volumes, mask, point, patch, matrix, outside, divisor, lo, hi, out):
+        """gs_patch_affine_clip_minmax: patch_clip_minmax through a 3 x 3 matrix — the trilinear gather of
+        data/utils/patch_affine.py (mask, then interpolate), then the same chain. matrix: 9 numbers, row-major, or 3 x 3."""
+        self._gather_clip_minmax("gs_patch_affine_clip_minmax", volumes, mask, point, patch, matrix, (), outside, divisor, lo,
+                                 hi, out)
+
+    def patch_affine(self, volume, start, size, matrix, fill, out):
+        """gs_patch_affine: out (d, h, w) fp32 = the raw trilinear gather of the window [start, start + size) of a dense
+        (D, H, W) fp32 / int16 device volume through `matrix`, `fill` outside the volume; no mask, no normalisation"""
+        self._gather_raw("gs_patch_affine", volume, start, size, matrix, (), fill, out)
+
     def patch_elastic_clip_minmax(self, volumes, mask, point, patch, matrix, field, outside, divisor, lo, hi, out):
         """gs_patch_elastic_clip_minmax: patch_affine_clip_minmax with a free-form deformation in front of the matrix.
         field: float64 device tensor [3, G0, G1, G2], control-point displacements in voxels (include/ganslate_hip.h)."""
-        n = len(volumes)
-        if n < 1:
-            raise ValueError("patch_elastic_clip_minmax: at least one volume")
-        self._case_volume("mask", mask, (torch.uint8,))
-        for i, v in enumerate(volumes):
-            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
-        self._point("point", point, 3)
-        grid, fptr = self._lattice(field)
-        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
-            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == (n, *[int(v) for v in patch])):
-            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *[int(v) for v in patch])}")
-        fl = lambda vals: (C.c_float * n)(*[float(v) for v in vals])
-        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in volumes])
-        dts = (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes])
-        L.check(self.lib.gs_patch_elastic_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, _ptr(point),
-                                                      (C.c_int32 * 3)(*[int(v) for v in patch]), self._matrix(matrix), grid,
-                                                      fptr, fl(outside), fl(divisor), fl(lo), fl(hi), _ptr(out), _stream()),
-                "gs_patch_elastic_clip_minmax")
+        self._gather_clip_minmax("gs_patch_elastic_clip_minmax", volumes, mask, point, patch, matrix, self._lattice(field),
+                                 outside, divisor, lo, hi, out)
 
     def patch_elastic(self, volume, start, size, matrix, field, fill, out):
         """gs_patch_elastic: patch_affine with a free-form deformation in front of the matrix (field as above)"""
-        self._case_volume("volume", volume, tuple(self.VOL_DTYPES))
-        grid, fptr = self._lattice(field)
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == tuple(int(v) for v in size)):
-            raise ValueError(f"out: expected a dense fp32 device tensor of shape {tuple(int(v) for v in size)}")
-        st, sz = (C.c_int32 * 3)(*[int(v) for v in start]), (C.c_int32 * 3)(*[int(v) for v in size])
-        L.check(self.lib.gs_patch_elastic(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
-                                          self._matrix(matrix), grid, fptr, float(fill), _ptr(out), _stream()),
-                "gs_patch_elastic")
+        self._gather_raw("gs_patch_elastic", volume, start, size, matrix, self._lattice(field), fill, out)
 
     def volume_prepare(self, volumes, mask, extra_masks, target, outside, divisor, lo, hi, out=None, masks_out=None):
         """gs_volume_prepare: one whole case for the val / test engines -> (out, [masks]). volumes: C fp32 / int16
@@ -1220,19 +1197,14 @@ class HipOps(TwinSplit):
         where(mask, v, outside) (each mask with its own minimum); then / divisor, clamp to [lo, hi], min-max to [-1, 1].
         out: fp32 [C, Do, Ho, Wo]; masks: uint8 [Do, Ho, Wo] each, the body mask first. Enqueued on the current stream;
         nothing syncs."""
-        n = len(volumes)
-        if not 1 <= n <= L.PATCH_MAX_MODALITIES:
-            raise ValueError(f"volume_prepare: between 1 and {L.PATCH_MAX_MODALITIES} volumes; got {n}")
+        if not 1 <= len(volumes) <= L.PATCH_MAX_MODALITIES:
+            raise ValueError(f"volume_prepare: between 1 and {L.PATCH_MAX_MODALITIES} volumes; got {len(volumes)}")
         extra_masks = list(extra_masks or [])
         if len(extra_masks) > L.VM_MAX_LABELS:
             raise ValueError(f"volume_prepare: at most {L.VM_MAX_LABELS} extra masks; got {len(extra_masks)}")
-        self._case_volume("mask", mask, (torch.uint8,))
-        for i, v in enumerate(volumes):
-            self._case_volume(f"volume {i}", v, tuple(self.VOL_DTYPES), mask.shape)
+        n, ptrs, dts, cols = self._mod_table("volume_prepare", volumes, mask, outside, divisor, lo, hi)
         for i, m in enumerate(extra_masks):
             self._case_volume(f"extra mask {i}", m, (torch.uint8,), mask.shape)
-        if not all(len(t) == n for t in (outside, divisor, lo, hi)):
-            raise ValueError(f"outside / divisor / lo / hi need one entry per volume ({n})")
         target = [int(v) for v in target]
         if len(target) != 3 or min(target) < 1:
             raise ValueError(f"target must be three positive sizes (D, H, W); got {target}")
@@ -1242,9 +1214,7 @@ class HipOps(TwinSplit):
             out = torch.empty((n, *shape), dtype=torch.float32, device=mask.device)
         if masks_out is None:
             masks_out = [torch.empty(shape, dtype=torch.uint8, device=mask.device) for _ in masks_in]
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == (n, *shape)):
-            raise ValueError(f"out: expected a dense fp32 device tensor of shape {(n, *shape)}")
+        self._out_f32(out, (n, *shape))
         if len(masks_out) != len(masks_in):
             raise ValueError(f"masks_out: one tensor per mask ({len(masks_in)})")
         for i, m in enumerate(masks_out):
@@ -1252,14 +1222,10 @@ class HipOps(TwinSplit):
         nws = getattr(self, "_prepare_ws", None) or int(self.lib.gs_volume_prepare_ws_bytes())
         self._prepare_ws = nws
         ws = torch.empty(nws // 4, dtype=torch.float32, device=mask.device)     # per launch: private to it
-        fl = lambda vals: (C.c_float * n)(*[float(v) for v in vals])
-        ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in volumes])
-        dts = (C.c_int32 * n)(*[self.VOL_DTYPES[v.dtype] for v in volumes])
         mi = (C.c_void_p * len(masks_in))(*[m.data_ptr() for m in masks_in])
         mo = (C.c_void_p * len(masks_in))(*[m.data_ptr() for m in masks_out])
-        L.check(self.lib.gs_volume_prepare(ptrs, dts, n, mi, len(masks_in), *mask.shape, (C.c_int32 * 3)(*target), fl(outside),
-                                           fl(divisor), fl(lo), fl(hi), _ptr(out), mo, _ptr(ws), _stream()),
-                "gs_volume_prepare")
+        L.check(self.lib.gs_volume_prepare(ptrs, dts, n, mi, len(masks_in), *mask.shape, (C.c_int32 * 3)(*target), *cols,
+                                           _ptr(out), mo, _ptr(ws), _stream()), "gs_volume_prepare")
         return out, list(masks_out)
 
     def body_mask(self, volume, threshold, out=None, return_rounds=False):

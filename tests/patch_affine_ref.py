@@ -19,8 +19,11 @@ def start_of(point, patch, size):
     return [min(max(int(point[a]) - patch[a] // 2, 0), size[a] - patch[a]) for a in range(3)]
 
 
-def coords(size, patch, start, M):
-    """per output voxel in C order: (reach, (i_0, i_1, i_2), (t_0, t_1, t_2)) — independent of the volume's values"""
+def coords(size, patch, start, M, u=None):
+    """per output voxel in C order: (reach, (i_0, i_1, i_2), (t_0, t_1, t_2)) — independent of the volume's values.
+    u: the elastic definition (tests/patch_elastic_ref.py), a displacement (u_0, u_1, u_2) per voxel in C order: r' = r + u,
+    and t_a = 0 where s_a fails the reach test (s - floor(s) is no number for a NaN or infinite s). The affine definition
+    keeps s - floor(s) there, NaN for an infinite s."""
     M = [[float(M[a][b]) for b in range(3)] for a in range(3)]
     c = [(patch[a] - 1) / 2.0 for a in range(3)]
     base = [float(start[a]) + c[a] for a in range(3)]
@@ -29,6 +32,8 @@ def coords(size, patch, start, M):
         for oy in range(patch[1]):
             for ox in range(patch[2]):
                 r = (oz - c[0], oy - c[1], ox - c[2])
+                if u is not None:
+                    r = tuple(r[a] + u[len(rows)][a] for a in range(3))         # o - c is exact: one rounded add
                 reach, idx, t = True, [], []
                 for a in range(3):
                     p0 = M[a][0] * r[0]
@@ -38,7 +43,10 @@ def coords(size, patch, start, M):
                     if not (s >= -1.0 and s < float(size[a])):         # NaN included
                         reach = False
                         idx.append(0)
-                        t.append(F(s - math.floor(s)) if math.isfinite(s) else F(np.nan))
+                        if u is not None:
+                            t.append(F(0.0))
+                        else:
+                            t.append(F(s - math.floor(s)) if math.isfinite(s) else F(np.nan))
                         continue
                     fl = math.floor(s)
                     idx.append(int(fl))
@@ -53,12 +61,12 @@ def lerp(a, b, t):
     return F(a + p)
 
 
-def gather(volumes, mask, start, patch, M, outside):
-    """[C, d, h, w] float32: mask, then interpolate; the coordinates once per voxel, the modalities inside"""
+def gather(volumes, mask, start, patch, M, outside, u=None):
+    """[C, d, h, w] float32: mask, then interpolate; the coordinates once per voxel, the modalities inside. u: as in coords"""
     size = volumes[0].shape
     out = np.empty((len(volumes), patch[0] * patch[1] * patch[2]), np.float32)
     with np.errstate(invalid="ignore", over="ignore"):
-        for n, (reach, (z, y, x), t) in enumerate(coords(size, patch, start, M)):
+        for n, (reach, (z, y, x), t) in enumerate(coords(size, patch, start, M, u)):
             ok = []
             for dz in (0, 1):
                 for dy in (0, 1):

@@ -2,21 +2,18 @@
 ganslate_amd/data/utils/patch_affine.py), restated from the definition in include/ganslate_hip.h as a plain per-voxel loop:
 Python ints for the lattice interval, Python floats (IEEE doubles, one rounding per operation, no fused multiply-add) for
 the B-spline weights, the displacement and r' = r + u. Everything after r' — the matrix, floor, t, the reach test, the
-masked corners, the float32 lerps, the clip / min-max chain — is the loop of tests/patch_affine_ref.py, called with its
-per-voxel coordinates replaced by the displaced ones. Nothing here calls the package's sampling code or the kernels.
+masked corners, the float32 lerps, the clip / min-max chain — is the loop of tests/patch_affine_ref.py, called with the
+per-voxel displacements (its `coords` adds them to r and carries the elastic definition's t = 0 outside the reach test).
+Nothing here calls the package's sampling code or the kernels.
 
 The displacement is a function of (patch, field) alone, about 500 float operations per voxel: `displacements` keeps the last
 few, so the tests of one case pay for it once. `RefElasticOps` carries HipOps' signatures for the pipelines' control flow."""
 import functools
-import math
-from unittest import mock
 
 import numpy as np
 import torch
 
 from tests import patch_affine_ref as A
-
-F = np.float32
 
 
 def axis_weights(o, p, G):
@@ -66,42 +63,10 @@ def displacements(patch, field):
     return _displacements(tuple(int(p) for p in patch), tuple(field.shape[1:]), field.tobytes())
 
 
-def coords(size, patch, start, M, u):
-    """tests/patch_affine_ref.py coords with r' = r + u, and t_a = 0 where s_a fails the reach test (s - floor(s) is no
-    number for a NaN or infinite s): (reach, (i_0, i_1, i_2), (t_0, t_1, t_2)) per voxel"""
-    M = [[float(M[a][b]) for b in range(3)] for a in range(3)]
-    c = [(patch[a] - 1) / 2.0 for a in range(3)]
-    base = [float(start[a]) + c[a] for a in range(3)]
-    rows, n = [], 0
-    for oz in range(patch[0]):
-        for oy in range(patch[1]):
-            for ox in range(patch[2]):
-                r = (oz - c[0] + u[n][0], oy - c[1] + u[n][1], ox - c[2] + u[n][2])     # o - c is exact: one rounded add
-                n += 1
-                reach, idx, t = True, [], []
-                for a in range(3):
-                    p0 = M[a][0] * r[0]
-                    p1 = M[a][1] * r[1]
-                    p2 = M[a][2] * r[2]
-                    s = ((p0 + p1) + p2) + base[a]
-                    if not (s >= -1.0 and s < float(size[a])):         # NaN included
-                        reach = False
-                        idx.append(0)
-                        t.append(F(0.0))                                   # the elastic definition's addition
-                        continue
-                    fl = math.floor(s)
-                    idx.append(int(fl))
-                    t.append(F(s - fl))
-                rows.append((reach, idx, t))
-    return rows
-
-
 def gather(volumes, mask, start, patch, M, field, outside):
     """[C, d, h, w] float32: the affine reference's gather loop on the displaced coordinates"""
     patch = [int(p) for p in patch]
-    u = displacements(patch, field)
-    with mock.patch.object(A, "coords", lambda size, p, s, m: coords(size, p, s, m, u)):
-        return A.gather(volumes, mask, start, patch, M, outside)
+    return A.gather(volumes, mask, start, patch, M, outside, displacements(patch, field))
 
 
 def patch_elastic_clip_minmax(volumes, mask, point, patch, M, field, outside, divisor, lo, hi):
