@@ -1456,30 +1456,7 @@ class HipOps(TwinSplit):
         (columns not asked for hold NaN). target / pred: [N, C, H, W] (the C channels are the SSIM planes) or
         [N, C, D, H, W] (all C*D depth slices are). With return_counts, also the raw bin counts (t [N, 100], p [N, 100],
         joint [N, 100, 100] indexed [t bin, p bin]) as int64 tensors. Enqueued on the current stream; nothing syncs."""
-        if target.shape != pred.shape:
-            raise ValueError(f"target {tuple(target.shape)} and prediction {tuple(pred.shape)} differ in shape")
-        if target.dim() not in (4, 5):
-            raise NotImplementedError(f"image metrics for {target.dim() - 1}-D samples are not implemented")
-        N, H, W = target.shape[0], target.shape[-2], target.shape[-1]
-        P = target[0].numel() // (H * W)
-        if ssim and (H < 7 or W < 7):
-            raise ValueError(f"SSIM needs planes of at least 7 x 7 (the window size); got {H} x {W}")
-        if P * H * W >= 2 ** 31:
-            raise ValueError("a sample must hold fewer than 2^31 elements")
-        hist = hist or return_counts
-        t = target.detach().contiguous().float()
-        p = pred.detach().contiguous().float()
-        table = torch.empty(N, 7, dtype=torch.float64, device=t.device)
-        counts = torch.empty(N, 2 * L.VM_BINS + L.VM_BINS ** 2, dtype=torch.int32, device=t.device) if hist else None
-        scratch = torch.empty(self.lib.gs_valmetric_scratch_bytes(N, P, H, W), dtype=torch.uint8, device=t.device)
-        flags = (L.VM_FLAGS["ssim"] if ssim else 0) | (L.VM_FLAGS["hist"] if hist else 0)
-        L.check(self.lib.gs_valmetrics(_ptr(t), _ptr(p), N, P, H, W, flags, _ptr(table), _ptr(counts), _ptr(scratch),
-                                       _stream()), "gs_valmetrics")
-        if not return_counts:
-            return table
-        B = L.VM_BINS
-        c = counts.long()
-        return table, (c[:, :B], c[:, B:2 * B], c[:, 2 * B:].reshape(N, B, B))
+        return self._valmetrics(target, pred, None, ssim, hist, return_counts)
 
     def valmetrics_masked(self, target, pred, masks, ssim=True, hist=True, return_counts=False):
         """`valmetrics` inside region masks (validator_tester.py:78-98; what the reference's masked arrays make of each
@@ -1488,17 +1465,21 @@ class HipOps(TwinSplit):
         batch's shape. A (sample, mask) pair with no element inside holds NaN in every column. With return_counts, also
         the raw bin counts of t*m and p*m ([N, L, 100], [N, L, 100], [N, L, 100, 100]). t*m and p*m are not built: the
         kernels apply the masks on load. Enqueued on the current stream; nothing syncs."""
+        return self._valmetrics(target, pred, list(masks), ssim, hist, return_counts)
+
+    def _valmetrics(self, target, pred, masks, ssim, hist, return_counts):
+        """the body of valmetrics (masks is None: rows are [N]) and valmetrics_masked (a list: rows are [N, L])"""
         if target.shape != pred.shape:
             raise ValueError(f"target {tuple(target.shape)} and prediction {tuple(pred.shape)} differ in shape")
         if target.dim() not in (4, 5):
             raise NotImplementedError(f"image metrics for {target.dim() - 1}-D samples are not implemented")
-        masks = list(masks)
-        if not 1 <= len(masks) <= L.VM_MAX_LABELS:
-            raise ValueError(f"between 1 and {L.VM_MAX_LABELS} masks per call; got {len(masks)}")
-        for i, m in enumerate(masks):
-            if m.shape != target.shape:
-                raise ValueError(f"mask {i} has shape {tuple(m.shape)}; the batch has {tuple(target.shape)} "
-                                 "(masks are not broadcast)")
+        if masks is not None:
+            if not 1 <= len(masks) <= L.VM_MAX_LABELS:
+                raise ValueError(f"between 1 and {L.VM_MAX_LABELS} masks per call; got {len(masks)}")
+            for i, m in enumerate(masks):
+                if m.shape != target.shape:
+                    raise ValueError(f"mask {i} has shape {tuple(m.shape)}; the batch has {tuple(target.shape)} "
+                                     "(masks are not broadcast)")
         N, H, W = target.shape[0], target.shape[-2], target.shape[-1]
         P = target[0].numel() // (H * W)
         if ssim and (H < 7 or W < 7):
@@ -1508,23 +1489,29 @@ class HipOps(TwinSplit):
         hist = hist or return_counts
         t = target.detach().contiguous().float()
         p = pred.detach().contiguous().float()
-        # one byte per element: bool and uint8 masks go as they are, every other dtype through `!= 0`
-        held = [(m if m.dtype in (torch.bool, torch.uint8) else m != 0).detach().to(t.device).contiguous()
-                .view(torch.uint8) for m in masks]
-        nl = len(held)
-        ptrs = (C.c_void_p * nl)(*[m.data_ptr() for m in held])
-        table = torch.empty(N, nl, 7, dtype=torch.float64, device=t.device)
-        counts = torch.empty(N, nl, 2 * L.VM_BINS + L.VM_BINS ** 2, dtype=torch.int32, device=t.device) if hist else None
-        scratch = torch.empty(self.lib.gs_valmetric_masked_scratch_bytes(N, nl, P, H, W), dtype=torch.uint8,
-                              device=t.device)
+        rows = (N,) if masks is None else (N, len(masks))
+        table = torch.empty(*rows, 7, dtype=torch.float64, device=t.device)
+        counts = torch.empty(*rows, 2 * L.VM_BINS + L.VM_BINS ** 2, dtype=torch.int32, device=t.device) if hist else None
         flags = (L.VM_FLAGS["ssim"] if ssim else 0) | (L.VM_FLAGS["hist"] if hist else 0)
-        L.check(self.lib.gs_valmetrics_masked(_ptr(t), _ptr(p), ptrs, nl, N, P, H, W, flags, _ptr(table), _ptr(counts),
-                                              _ptr(scratch), _stream()), "gs_valmetrics_masked")
+        tail = (N, P, H, W, flags, _ptr(table), _ptr(counts))
+        if masks is None:
+            scratch = torch.empty(self.lib.gs_valmetric_scratch_bytes(N, P, H, W), dtype=torch.uint8, device=t.device)
+            L.check(self.lib.gs_valmetrics(_ptr(t), _ptr(p), *tail, _ptr(scratch), _stream()), "gs_valmetrics")
+        else:
+            # one byte per element: bool and uint8 masks go as they are, every other dtype through `!= 0`
+            held = [(m if m.dtype in (torch.bool, torch.uint8) else m != 0).detach().to(t.device).contiguous()
+                    .view(torch.uint8) for m in masks]
+            nl = len(held)
+            ptrs = (C.c_void_p * nl)(*[m.data_ptr() for m in held])
+            scratch = torch.empty(self.lib.gs_valmetric_masked_scratch_bytes(N, nl, P, H, W), dtype=torch.uint8,
+                                  device=t.device)
+            L.check(self.lib.gs_valmetrics_masked(_ptr(t), _ptr(p), ptrs, nl, *tail, _ptr(scratch), _stream()),
+                    "gs_valmetrics_masked")
         if not return_counts:
             return table
         B = L.VM_BINS
         c = counts.long()
-        return table, (c[..., :B], c[..., B:2 * B], c[..., 2 * B:].reshape(N, nl, B, B))
+        return table, (c[..., :B], c[..., B:2 * B], c[..., 2 * B:].reshape(*rows, B, B))
 
     # ---- sliding-window inference (slidewin.hip) -------------------------------------------------------------
     # The stitching of utils/sliding_window_inferer.py around a predictor. Tensors are dense fp32 [N, C, D, H, W] on the

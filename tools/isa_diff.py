@@ -7,10 +7,12 @@
 One line per kernel: VGPRs, LDS bytes and scratch bytes of both builds, and whether the instruction streams are identical after
 symbol names and local label numbers are normalised and the two factors of an integer multiply (v_mul_lo_u32, v_mad_u64_u32) are
 put in a fixed order: say so next to a table made with this. --rename matches a kernel of the parent with a differently named
-kernel of the new build (demangled names, a substring is replaced). Exit status 1 when a kernel of the new build has scratch, more VGPRs
+kernel of the new build (demangled names, a substring is replaced). --diff appends the unified diff of the normalised instruction
+streams of every kernel that is not identical. Exit status 1 when a kernel of the new build has scratch, more VGPRs
 or another LDS size than its parent, or has no parent.
 """
 import argparse
+import difflib
 import re
 import subprocess
 import sys
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("new")
     ap.add_argument("--rename", action="append", default=[], help="OLD=NEW substring of a demangled kernel name")
+    ap.add_argument("--diff", action="store_true", help="append the instruction diff of every kernel that is not identical")
     args = ap.parse_args()
     bad = 0
     print("%-78s %9s %13s %9s %s" % ("kernel", "VGPRs p/n", "LDS p/n", "scratch", "identical"))
@@ -78,6 +81,11 @@ def main():
         bad += kb["scratch"] != 0 or kb["vgpr"] > ka["vgpr"] or kb["lds"] != ka["lds"]
     for name in sorted(set(a) - set(b)):
         print("%-78s only in the parent" % name)
+    if args.diff:
+        for name in sorted(b):
+            if name in a and a[name]["body"] != b[name]["body"]:
+                print("\n## %s" % name)
+                print("\n".join(difflib.unified_diff(a[name]["body"], b[name]["body"], "parent", "new", n=1, lineterm="")))
     return 1 if bad else 0
 
 
