@@ -11,6 +11,7 @@
 // and the apply pass, which evaluates the reference's expression operation for operation in fp32. HBM-bound, 4 B in +
 // 4 B out per voxel twice over an 8 MB patch: not a kernel worth more than coalesced rows.
 #include "common.hpp"
+#include "intensity.hpp"
 
 namespace {
 constexpr int NB = 256;      // partial-sum blocks
@@ -104,17 +105,85 @@ __global__ __launch_bounds__(256) void patch_apply_kernel(const PatchK k, const 
   }
 }
 
+// gs_patch_zscore_intensity's apply pass: t as above, n = (t - tmin) / (tmax - tmin), the intensity chain (intensity.hpp),
+// span * n + lo — one IEEE operation per step. The bias lattice (at most 8 KB) is staged to LDS per workgroup and evaluated
+// per voxel; the voxel index i of the grid-stride loop is the index of the definition (noise counter, lattice position).
+struct ZIntK {
+  GsPatchIntensity it;
+  const double* beta;              // DEVICE double[BG0][BG1][BG2], or nullptr
+  int BG[3];
+};
+
 template <typename T>
-int launch(const PatchK& k, float lo, float hi, int rescale, float* out, float* scratch, hipStream_t st) {
+__global__ __launch_bounds__(256) void patch_apply_intensity_kernel(const PatchK k, const ZIntK q, const float* stats, float lo,
+                                                                    float hi, float* out) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double beta_lds[];
+  if (q.beta) {
+    const int GN = q.BG[0] * q.BG[1] * q.BG[2];
+    for (int e = threadIdx.x; e < GN; e += 256) beta_lds[e] = q.beta[e];
+    __syncthreads();
+  }
+  const float m = stats[0], sd = stats[1], tmin = stats[2], tmax = stats[3];
+  const float span = hi - lo, delta = tmax - tmin;
+  const int patch[3] = {k.pd, k.ph, k.pw};
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < k.n; i += (long long)gridDim.x * 256) {
+    const float d = voxel<T>(k, i) - m;
+    const float t = d / sd;
+    const float u = t - tmin;
+    float n = u / delta;
+    double beta = 0.0;
+    if (q.beta) {
+      int o[3];
+      o[2] = (int)(i % k.pw);
+      const long long row = i / k.pw;
+      o[1] = (int)(row % k.ph);
+      o[0] = (int)(row / k.ph);
+      beta = lattice_at(beta_lds, q.BG, o, patch);
+    }
+    n = intensity_chain(n, q.it, beta, i, 0);
+    const float s = span * n;
+    out[i] = s + lo;
+  }
+}
+
+template <typename T>
+int launch(const PatchK& k, float lo, float hi, int rescale, float* out, float* scratch, hipStream_t st,
+           const ZIntK* q = nullptr) {
   double* partial = reinterpret_cast<double*>(scratch);
   float* stats = scratch + NB * 4 * 2;
   hipLaunchKernelGGL((patch_stats_kernel<T>), dim3(NB), dim3(256), 0, st, k, partial);
   hipLaunchKernelGGL(patch_finalize_kernel, dim3(1), dim3(256), 0, st, partial, k.n, stats);
   const long long blocks = (k.n + 256 * 4 - 1) / (256 * 4);
-  hipLaunchKernelGGL((patch_apply_kernel<T>), dim3((unsigned)(blocks < 1 ? 1 : (blocks > 65535 ? 65535 : blocks))), dim3(256),
-                     0, st, k, stats, lo, hi, rescale, out);
+  const dim3 g((unsigned)(blocks < 1 ? 1 : (blocks > 65535 ? 65535 : blocks)));
+  if (q) {
+    const size_t lds = q->beta ? (size_t)q->BG[0] * q->BG[1] * q->BG[2] * sizeof(double) : 0;
+    hipLaunchKernelGGL((patch_apply_intensity_kernel<T>), g, dim3(256), lds, st, k, *q, stats, lo, hi, out);
+  } else {
+    hipLaunchKernelGGL((patch_apply_kernel<T>), g, dim3(256), 0, st, k, stats, lo, hi, rescale, out);
+  }
   GS_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+int zscore(const char* who, const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+           const int32_t* size, int32_t rescale, float lo, float hi, float* out, float* scratch, void* stream, const ZIntK* q) {
+  GS_REQUIRE(vol && start && size && out && scratch, "%s: null argument", who);
+  GS_REQUIRE(dtype == GS_VOL_F32 || dtype == GS_VOL_I16, "%s: dtype %d (GS_VOL_F32 / GS_VOL_I16)", who, dtype);
+  GS_REQUIRE(size[0] > 0 && size[1] > 0 && size[2] > 0 && start[0] >= 0 && start[1] >= 0 && start[2] >= 0 &&
+                 start[0] + size[0] <= D && start[1] + size[1] <= H && start[2] + size[2] <= W,
+             "%s: patch [%d+%d, %d+%d, %d+%d] outside the %d x %d x %d volume", who, start[0], size[0], start[1],
+             size[1], start[2], size[2], D, H, W);
+  GS_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "%s: scratch must be 8-byte aligned", who);
+  PatchK k;
+  k.vol = vol;
+  k.sz = (long long)H * W; k.sy = W;
+  k.z0 = start[0]; k.y0 = start[1]; k.x0 = start[2];
+  k.pd = size[0]; k.ph = size[1]; k.pw = size[2];
+  k.n = (long long)size[0] * size[1] * size[2];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return dtype == GS_VOL_F32 ? launch<float>(k, lo, hi, rescale, out, scratch, st, q)
+                             : launch<short>(k, lo, hi, rescale, out, scratch, st, q);
 }
 }  // namespace
 
@@ -123,20 +192,20 @@ extern "C" int64_t gs_patch_zscore_ws_floats(void) { return NB * 4 * 2 + 8; }
 extern "C" int gs_patch_zscore(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
                                const int32_t* size, int32_t rescale, float lo, float hi, float* out, float* scratch,
                                void* stream) {
-  GS_REQUIRE(vol && start && size && out && scratch, "gs_patch_zscore: null argument");
-  GS_REQUIRE(dtype == GS_VOL_F32 || dtype == GS_VOL_I16, "gs_patch_zscore: dtype %d (GS_VOL_F32 / GS_VOL_I16)", dtype);
-  GS_REQUIRE(size[0] > 0 && size[1] > 0 && size[2] > 0 && start[0] >= 0 && start[1] >= 0 && start[2] >= 0 &&
-                 start[0] + size[0] <= D && start[1] + size[1] <= H && start[2] + size[2] <= W,
-             "gs_patch_zscore: patch [%d+%d, %d+%d, %d+%d] outside the %d x %d x %d volume", start[0], size[0], start[1],
-             size[1], start[2], size[2], D, H, W);
-  GS_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, "gs_patch_zscore: scratch must be 8-byte aligned");
-  PatchK k;
-  k.vol = vol;
-  k.sz = (long long)H * W; k.sy = W;
-  k.z0 = start[0]; k.y0 = start[1]; k.x0 = start[2];
-  k.pd = size[0]; k.ph = size[1]; k.pw = size[2];
-  k.n = (long long)size[0] * size[1] * size[2];
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == GS_VOL_F32 ? launch<float>(k, lo, hi, rescale, out, scratch, st)
-                             : launch<short>(k, lo, hi, rescale, out, scratch, st);
+  return zscore("gs_patch_zscore", vol, dtype, D, H, W, start, size, rescale, lo, hi, out, scratch, stream, nullptr);
+}
+
+extern "C" int gs_patch_zscore_intensity(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                                         const int32_t* size, float lo, float hi, const GsPatchIntensity* intensity,
+                                         const int32_t* bias_grid, const double* bias_field, float* out, float* scratch,
+                                         void* stream) {
+  const char* who = "gs_patch_zscore_intensity";
+  GS_REQUIRE(size, "%s: null argument", who);
+  bool lattice;
+  if (const int rc = check_intensity(who, intensity, 1, size, bias_grid, bias_field, &lattice)) return rc;
+  ZIntK q;
+  q.it = intensity[0];
+  q.beta = bias_field;
+  for (int a = 0; a < 3; ++a) q.BG[a] = bias_grid ? bias_grid[a] : 4;
+  return zscore(who, vol, dtype, D, H, W, start, size, 1, lo, hi, out, scratch, stream, &q);
 }

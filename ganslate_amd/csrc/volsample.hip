@@ -31,6 +31,8 @@
 // feeds gs_patch_zscore). One thread per voxel, the modalities looped inside it; no contraction anywhere in the definition.
 // gs_patch_elastic_clip_minmax / gs_patch_elastic — the same kernel with a free-form deformation (a lattice of control-point
 // displacements, cubic B-splines) added to the patch offset in front of the matrix: a compile-time variant of that kernel.
+// gs_patch_augment_clip_minmax — either of the two with the intensity chain of intensity.hpp (bias field, contrast,
+// brightness, gamma, noise) between the min-max step and 2 n - 1: one more compile-time variant.
 //
 // gs_volume_prepare — a whole case for the val / test engines (data/multimodal_valtest.py): the same mask step and the same
 // per-voxel chain (one device function, clip_minmax), with centred padding up to a target shape in between; the pad value is
@@ -42,6 +44,7 @@
 // patch_start (the start clamp, device side) are the other rules the entries share.
 #include <limits>
 #include "common.hpp"
+#include "intensity.hpp"
 
 namespace {
 constexpr int NR = 256;      // ranges = workgroups of pass 1
@@ -404,50 +407,6 @@ struct ElaK : AffK {
 
 enum { ELA_NONE = 0, ELA_VOXEL = 1, ELA_ROWS = 2 };
 
-// the interval j and the four uniform cubic B-spline weights of output index o on an axis of p voxels over G control
-// points: f = (o (G - 3) - j (p - 1)) / (p - 1), one correctly rounded division of two exact integers
-__device__ __forceinline__ int bspline_axis(int o, int p, int G, double B[4]) {
-#pragma clang fp contract(off)
-  const int num = o * (G - 3), den = p - 1;              // the host refused (p - 1) (G - 3) > INT_MAX
-  int j = num / den;
-  j = j > G - 4 ? G - 4 : j;
-  const double f = __ddiv_rn((double)(num - j * den), (double)den);
-  const double f2 = f * f;
-  const double f3 = f2 * f;
-  const double g = 1.0 - f;
-  const double gg = g * g;
-  const double t1 = 3.0 * f3;
-  const double t2 = 6.0 * f2;
-  const double t3 = 3.0 * f2;
-  const double t4 = 3.0 * f;
-  B[0] = __ddiv_rn(gg * g, 6.0);
-  B[1] = __ddiv_rn((t1 - t2) + 4.0, 6.0);
-  B[2] = __ddiv_rn(((t3 - t1) + t4) + 1.0, 6.0);
-  B[3] = __ddiv_rn(f3, 6.0);
-  return j;
-}
-
-__device__ __forceinline__ double dot4(const double B[4], double a0, double a1, double a2, double a3) {
-#pragma clang fp contract(off)
-  const double p0 = B[0] * a0;
-  const double p1 = B[1] * a1;
-  const double p2 = B[2] * a2;
-  const double p3 = B[3] * a3;
-  const double s1 = p0 + p1;
-  const double s2 = s1 + p2;
-  return s2 + p3;
-}
-
-// R of one lattice column: D innermost (Bz), then H (By). F: one component of the lattice at (j0, j1, column), in LDS or
-// in global memory
-__device__ __forceinline__ double lattice_R(const double* F, int G1, int G2, const double Bz[4], const double By[4]) {
-  double q[4];
-  const int sz = G1 * G2;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) q[m] = dot4(Bz, F[m * G2], F[sz + m * G2], F[2 * sz + m * G2], F[3 * sz + m * G2]);
-  return dot4(By, q[0], q[1], q[2], q[3]);
-}
-
 // cooperative part, every thread of the workgroup: fills the LDS of its form and synchronises
 template <int E>
 __device__ __forceinline__ void elastic_stage(const ElaK& k, double* lds) {
@@ -503,11 +462,72 @@ __device__ __forceinline__ void elastic_displace(const ElaK& k, const double* ld
   for (int a = 0; a < 3; ++a) r[a] = r[a] + u[a];
 }
 
-template <bool CLIP, int E, typename K>
+// ---- the intensity variant (gs_patch_augment_clip_minmax) ----------------------------------------------------------------
+// The chain of intensity.hpp in the CLIP epilogue, between (v - lo) / span and 2 n - 1 (ganslate_hip.h states the
+// definition). IntK wraps the argument of the geometric form it rides on. The bias lattice BETA (one scalar lattice, up to
+// 8 KB of float64, a grid of its own) is evaluated once per voxel in front of the modality loop, in the forms of the elastic
+// part and behind its LDS: `bform` ELA_ROWS adds BG[2] doubles per row to the row table, ELA_VOXEL stages the lattice;
+// ELA_NONE is a launch without a lattice. The host picks one form for both lattices, by the size of the combined table.
+template <typename B>
+struct IntK : B {
+  GsPatchIntensity it[PC_MAX];
+  const double* beta;              // DEVICE double[BG0][BG1][BG2], or nullptr
+  int BG[3];
+  int bform, boff;                 // boff: doubles of LDS in front of the bias part
+};
+
+template <typename K>
+__device__ __forceinline__ void bias_stage(const K& k, double* lds) {
+  if (k.bform == ELA_NONE) return;                         // uniform over the launch
+  if (k.bform == ELA_VOXEL) {
+    const int GN = k.BG[0] * k.BG[1] * k.BG[2];
+    for (int e = threadIdx.x; e < GN; e += 256) lds[e] = k.beta[e];
+  } else {
+    const long long first = (long long)blockIdx.x * 256;
+    long long last = first + 255;
+    last = last < k.n ? last : k.n - 1;
+    const long long row0 = first / k.pw;
+    const int rows = (int)(last / k.pw - row0) + 1;        // as in elastic_stage
+    const int per = k.BG[2];
+    for (int e = threadIdx.x; e < rows * per; e += 256) {
+      const long long row = row0 + e / per;
+      double Bz[4], By[4];
+      const int j0 = bspline_axis((int)(row / k.ph), k.pd, k.BG[0], Bz);
+      const int j1 = bspline_axis((int)(row % k.ph), k.ph, k.BG[1], By);
+      lds[e] = lattice_R(k.beta + (j0 * k.BG[1] + j1) * k.BG[2] + e % per, k.BG[1], k.BG[2], Bz, By);
+    }
+  }
+  __syncthreads();
+}
+
+template <typename K>
+__device__ __forceinline__ double bias_at(const K& k, const double* lds, const int o[3], long long i) {
+  if (k.bform == ELA_NONE) return 0.0;
+  if (k.bform == ELA_VOXEL) {
+    const int patch[3] = {k.pd, k.ph, k.pw};
+    return lattice_at(lds, k.BG, o, patch);
+  }
+  double Bx[4];
+  const int j2 = bspline_axis(o[2], k.pw, k.BG[2], Bx);
+  const int rl = (int)(i / k.pw - ((long long)blockIdx.x * 256) / k.pw);
+  const double* R = lds + rl * k.BG[2] + j2;
+  return dot4(Bx, R[0], R[1], R[2], R[3]);
+}
+
+// clip_minmax up to the normalised value n, and its last step
+__device__ __forceinline__ float clip_unit(float v, float divisor, float lo, float hi, float span) {
+  v = __fdiv_rn(v, divisor);
+  v = v < lo ? lo : v;
+  v = v > hi ? hi : v;
+  return __fdiv_rn(__fsub_rn(v, lo), span);
+}
+
+template <bool CLIP, int E, typename K, bool INT = false>
 __global__ __launch_bounds__(256) void patch_affine_kernel(const K k, float* out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   extern __shared__ __attribute__((aligned(16))) double ela_lds[];
   if constexpr (E != ELA_NONE) elastic_stage<E>(k, ela_lds);
+  if constexpr (INT) bias_stage(k, ela_lds + k.boff);
   if (i >= k.n) return;
   const int size[3] = {k.D, k.H, k.W}, patch[3] = {k.pd, k.ph, k.pw};
   int o[3];
@@ -524,6 +544,8 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const K k, float* out
     r[a] = (double)o[a] - c;                             // exact
     base[a] = (double)s + c;                             // exact
   }
+  double beta = 0.0;
+  if constexpr (INT) beta = bias_at(k, ela_lds + k.boff, o, i);
   if constexpr (E != ELA_NONE) elastic_displace<E>(k, ela_lds, o, i, r);
   int ix[3];
   float t[3];
@@ -586,21 +608,47 @@ __global__ __launch_bounds__(256) void patch_affine_kernel(const K k, float* out
     const float c00 = lerp_rn(v[0], v[1], t[2]), c01 = lerp_rn(v[2], v[3], t[2]);
     const float c10 = lerp_rn(v[4], v[5], t[2]), c11 = lerp_rn(v[6], v[7], t[2]);
     float g = lerp_rn(lerp_rn(c00, c01, t[1]), lerp_rn(c10, c11, t[1]), t[0]);
-    if constexpr (CLIP) g = clip_minmax(g, k.divisor[c], k.lo[c], k.hi[c], __fsub_rn(k.hi[c], k.lo[c]));
+    if constexpr (INT) {
+      float n = clip_unit(g, k.divisor[c], k.lo[c], k.hi[c], __fsub_rn(k.hi[c], k.lo[c]));
+      n = intensity_chain(n, k.it[c], beta, i, c);
+      g = __fsub_rn(__fmul_rn(2.f, n), 1.f);
+    } else if constexpr (CLIP) {
+      g = clip_minmax(g, k.divisor[c], k.lo[c], k.hi[c], __fsub_rn(k.hi[c], k.lo[c]));
+    }
     out[(long long)c * k.n + i] = g;
   }
 }
 
-// the one launch line of the gather: E and K come with the caller's form, `clip` picks CLIP
+// the intensity arguments of gs_patch_augment_clip_minmax, checked by the caller (check_intensity)
+struct IntArgs {
+  const GsPatchIntensity* it;      // host, k.C entries
+  const int32_t* grid;             // nullptr: no bias lattice
+  const double* field;
+};
+
+// the one launch line of the gather: E and K come with the caller's form, `clip` picks CLIP; with `ia` the intensity
+// variant of that form, its bias part in LDS behind the lds bytes of the elastic part
 template <int E, typename K>
-void launch_gather(const K& k, bool clip, dim3 g, size_t lds, hipStream_t st, float* out) {
+void launch_gather(const K& k, bool clip, dim3 g, size_t lds, hipStream_t st, float* out, const IntArgs* ia = nullptr,
+                   int bform = ELA_NONE, size_t lds_bias = 0) {
+  if (ia) {
+    IntK<K> q;
+    static_cast<K&>(q) = k;
+    for (int c = 0; c < PC_MAX; ++c) q.it[c] = ia->it[c < k.C ? c : 0];
+    q.beta = ia->field;
+    for (int a = 0; a < 3; ++a) q.BG[a] = ia->grid ? ia->grid[a] : 4;
+    q.bform = bform;
+    q.boff = (int)(lds / sizeof(double));
+    hipLaunchKernelGGL((patch_affine_kernel<true, E, IntK<K>, true>), g, dim3(256), lds + lds_bias, st, q, out);
+    return;
+  }
   void (*kernel)(const K, float*) = clip ? patch_affine_kernel<true, E, K> : patch_affine_kernel<false, E, K>;
   hipLaunchKernelGGL(kernel, g, dim3(256), lds, st, k, out);
 }
 
 // grid (nullptr: no elastic part) and field: the lattice of gs_patch_elastic*, checked by the caller
 int launch_affine(AffK& k, const int32_t* patch, const double* M, const int32_t* grid, const double* field, float* out,
-                  bool clip, void* stream) {
+                  bool clip, void* stream, const IntArgs* ia = nullptr) {
   for (int j = 0; j < 9; ++j) k.M[j] = M[j];
   k.pd = patch[0]; k.ph = patch[1]; k.pw = patch[2];
   k.n = (long long)patch[0] * patch[1] * patch[2];
@@ -608,19 +656,27 @@ int launch_affine(AffK& k, const int32_t* patch, const double* M, const int32_t*
   GS_REQUIRE(blocks <= 0x7fffffffLL, "gs_patch_affine: %lld voxels do not fit one grid", k.n);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 g((unsigned)blocks);
+  // one form for both lattices: the row tables when together they fit the option, else both staged whole
+  const int32_t* bg = ia ? ia->grid : nullptr;
+  const long long rows_all = (long long)patch[0] * patch[1], rows_wg = 255 / patch[2] + 2;
+  const size_t rows = (size_t)(rows_all < rows_wg ? rows_all : rows_wg);
+  const size_t table = grid ? rows * 3 * grid[2] * sizeof(double) : 0;
+  const size_t table_bias = bg ? rows * bg[2] * sizeof(double) : 0;
+  int fits = gs_opt(GS_OPT_ELASTIC_ROWS);
+  fits = fits < 0 ? 0 : (fits > 65536 ? 65536 : fits);
+  const bool by_rows = table + table_bias <= (size_t)fits;
+  const int bform = !bg ? ELA_NONE : (by_rows ? ELA_ROWS : ELA_VOXEL);
+  const size_t lds_bias = !bg ? 0 : (by_rows ? table_bias : (size_t)bg[0] * bg[1] * bg[2] * sizeof(double));
   if (!grid) {
-    launch_gather<ELA_NONE>(k, clip, g, 0, st, out);
+    launch_gather<ELA_NONE>(k, clip, g, 0, st, out, ia, bform, lds_bias);
   } else {
     ElaK e;
     static_cast<AffK&>(e) = k;
     e.field = field;
     e.G[0] = grid[0]; e.G[1] = grid[1]; e.G[2] = grid[2];
-    const long long rows_all = (long long)patch[0] * patch[1], rows_wg = 255 / patch[2] + 2;
-    const size_t table = (size_t)(rows_all < rows_wg ? rows_all : rows_wg) * 3 * grid[2] * sizeof(double);
-    int fits = gs_opt(GS_OPT_ELASTIC_ROWS);
-    fits = fits < 0 ? 0 : (fits > 65536 ? 65536 : fits);
-    if (table <= (size_t)fits) launch_gather<ELA_ROWS>(e, clip, g, table, st, out);
-    else launch_gather<ELA_VOXEL>(e, clip, g, (size_t)3 * grid[0] * grid[1] * grid[2] * sizeof(double), st, out);
+    if (by_rows) launch_gather<ELA_ROWS>(e, clip, g, table, st, out, ia, bform, lds_bias);
+    else launch_gather<ELA_VOXEL>(e, clip, g, (size_t)3 * grid[0] * grid[1] * grid[2] * sizeof(double), st, out, ia, bform,
+                                  lds_bias);
   }
   GS_CHECK_HIP(hipGetLastError());
   return 0;
@@ -802,7 +858,7 @@ namespace {
 int gather_clip_minmax(const char* who, const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
                        int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch, const double* M,
                        const int32_t* grid, const double* field, const float* outside, const float* divisor, const float* lo,
-                       const float* hi, float* out, void* stream) {
+                       const float* hi, float* out, void* stream, const IntArgs* ia = nullptr) {
   GS_REQUIRE(vols && dtypes && mask && point && patch && M && outside && divisor && lo && hi && out, "%s: null argument", who);
   GS_REQUIRE(C >= 1 && C <= PC_MAX, "%s: between 1 and %d modalities per call; got %d", who, PC_MAX, C);
   if (const int rc = check_patch_fits(who, D, H, W, patch)) return rc;
@@ -813,7 +869,7 @@ int gather_clip_minmax(const char* who, const void* const* vols, const int32_t* 
   k.point = point;
   k.start[0] = k.start[1] = k.start[2] = 0;
   k.C = C; k.D = D; k.H = H; k.W = W;
-  return launch_affine(k, patch, M, grid, field, out, true, stream);
+  return launch_affine(k, patch, M, grid, field, out, true, stream, ia);
 }
 
 int gather_raw(const char* who, const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
@@ -870,6 +926,25 @@ extern "C" int gs_patch_elastic(const void* vol, int32_t dtype, int32_t D, int32
   GS_REQUIRE(size, "gs_patch_elastic: null argument");
   if (const int rc = check_lattice("gs_patch_elastic", size, grid, field)) return rc;
   return gather_raw("gs_patch_elastic", vol, dtype, D, H, W, start, size, M, grid, field, fill, out, stream);
+}
+
+extern "C" int gs_patch_augment_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask,
+                                            int32_t D, int32_t H, int32_t W, const int32_t* point, const int32_t* patch,
+                                            const double* M, const int32_t* grid, const double* field,
+                                            const GsPatchIntensity* intensity, const int32_t* bias_grid,
+                                            const double* bias_field, const float* outside, const float* divisor,
+                                            const float* lo, const float* hi, float* out, void* stream) {
+  const char* who = "gs_patch_augment_clip_minmax";
+  GS_REQUIRE(patch, "%s: null argument", who);
+  GS_REQUIRE(C >= 1 && C <= PC_MAX, "%s: between 1 and %d modalities per call; got %d", who, PC_MAX, C);
+  GS_REQUIRE((grid != nullptr) == (field != nullptr), "%s: grid and field come together", who);
+  if (grid)
+    if (const int rc = check_lattice(who, patch, grid, field)) return rc;
+  bool lattice;
+  if (const int rc = check_intensity(who, intensity, C, patch, bias_grid, bias_field, &lattice)) return rc;
+  const IntArgs ia = {intensity, bias_grid, bias_field};
+  return gather_clip_minmax(who, vols, dtypes, C, mask, D, H, W, point, patch, M, grid, field, outside, divisor, lo, hi, out,
+                            stream, &ia);
 }
 
 extern "C" int64_t gs_volume_prepare_ws_bytes(void) { return (int64_t)(PC_MAX + VP_MAX_MASKS) * VP_PARTS * 4; }

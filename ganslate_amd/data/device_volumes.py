@@ -4,11 +4,14 @@ scaling run as gs_patch_zscore (csrc/volproc.hip) and write straight into the fp
 takes. Reference path being replaced: projects/brats_mri_sequence_translation/datasets/train_dataset.py:83-92.
 With `augmentation` a sample also carries a 3 x 3 matrix: gs_patch_affine (csrc/volsample.hip) gathers the patch through
 it into a scratch patch, and gs_patch_zscore normalises that as a volume of its own. A sample that also carries an elastic
-field takes gs_patch_elastic there; the fields of a batch are uploaded in one copy."""
+field takes gs_patch_elastic there; the fields of a batch are uploaded in one copy. A sample whose intensity row is not
+neutral (data/utils/patch_intensity.py) takes gs_patch_zscore_intensity in place of gs_patch_zscore; the bias lattices of a
+batch are one more copy."""
 import numpy as np
 import torch
 
 from .resident_cache import ResidentCache
+from .utils.patch_intensity import active
 
 
 class ResidentVolumes(ResidentCache):
@@ -47,6 +50,20 @@ def upload_fields(items, device):
     return {key: dev[n] for n, key in enumerate(fields)}
 
 
+def upload_bias(items, device):
+    """{id(lattice): float64 device tensor [G0, G1, G2]} of the bias lattices of the samples whose intensity block is
+    active (data/utils/patch_intensity.py): like the elastic fields, one host array and one copy per batch"""
+    lattices = {}
+    for r in items:
+        block = active(getattr(r, "intensity", None))
+        if block is not None and block[1] is not None:
+            lattices.setdefault(id(block[1]), block[1])
+    if not lattices:
+        return {}
+    dev = torch.from_numpy(np.stack([np.asarray(b, dtype=np.float64) for b in lattices.values()])).to(device)
+    return {key: dev[n] for n, key in enumerate(lattices)}
+
+
 class DeviceVolumePipeline(ResidentVolumes):
     """callable(raw batch) -> {"A": fp32 [N, 1, *patch] on the device, "B": ...}"""
 
@@ -61,8 +78,8 @@ class DeviceVolumePipeline(ResidentVolumes):
     def __call__(self, batch):
         from .volume_datasets import RawPatch
         out = {}
-        fields = upload_fields([r for items in batch.values() if items and isinstance(items[0], RawPatch) for r in items],
-                               self.device)
+        raws = [r for items in batch.values() if items and isinstance(items[0], RawPatch) for r in items]
+        fields, lattices = upload_fields(raws, self.device), upload_bias(raws, self.device)
         for key, items in batch.items():
             if not items or not isinstance(items[0], RawPatch):
                 out[key] = items
@@ -80,7 +97,12 @@ class DeviceVolumePipeline(ResidentVolumes):
                 else:
                     self.ops.patch_affine(self.volume(r.domain, r.index), r.start, self.size, r.matrix,
                                           self.dataset.augmentation.fill, raw)
-                self.ops.patch_zscore(raw, (0, 0, 0), self.size, dst[n, 0], (-1.0, 1.0))
+                block = active(r.intensity)
+                if block is None:           # none, or its one row came out neutral: the plain z-score
+                    self.ops.patch_zscore(raw, (0, 0, 0), self.size, dst[n, 0], (-1.0, 1.0))
+                else:
+                    self.ops.patch_zscore_intensity(raw, (0, 0, 0), self.size, dst[n, 0], block[0][0],
+                                                    None if block[1] is None else lattices[id(block[1])], (-1.0, 1.0))
             out[key] = dst.squeeze(2) if self.squeeze else dst
         return out
 
@@ -93,7 +115,8 @@ class DeviceMultiModalPipeline(ResidentVolumes):
     the batch (csrc/volsample.hip). Nothing synchronises per iteration; the empty-zone check of a case runs once, when its
     mask is first uploaded. A sample that carries an augmentation matrix takes gs_patch_affine_clip_minmax instead: the
     same crop as one trilinear gather through the matrix (data/utils/patch_affine.py), and one that also carries an elastic
-    field gs_patch_elastic_clip_minmax (the fields of a batch are uploaded in one copy). Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
+    field gs_patch_elastic_clip_minmax (the fields of a batch are uploaded in one copy); a domain whose intensity block is
+    not neutral takes gs_patch_augment_clip_minmax, the same gather with the intensity chain inside. Reference path being replaced: projects/maastro_hx4_pet_translation/datasets/
     train_dataset.py:106-188 with datasets/utils/patch_samplers.py."""
 
     def __init__(self, dataset, device, ops=None, max_resident_bytes=200 << 30):
@@ -116,12 +139,14 @@ class DeviceMultiModalPipeline(ResidentVolumes):
             self.checked.add((domain, index))
         return mask, weight, [self.volume(n, index) for n in ds.modalities[domain]]
 
-    def _patch(self, domain, index, vols, mask, point, dst, matrix=None, field=None):
+    def _patch(self, domain, index, vols, mask, point, dst, matrix=None, field=None, intensity=None, lattice=None):
         ds = self.dataset
         names = ds.modalities[domain]
         cols = ([ds.outside_value[n] for n in names], [ds.divisor(n, index) for n in names],
                 [ds.clip_range[n][0] for n in names], [ds.clip_range[n][1] for n in names])
-        if matrix is None:
+        if intensity is not None:           # (rows, _) of an active block; lattice: its bias lattice on the device
+            self.ops.patch_augment_clip_minmax(vols, mask, point, self.size, matrix, field, intensity[0], lattice, *cols, dst)
+        elif matrix is None:
             self.ops.patch_clip_minmax(vols, mask, point, self.size, *cols, dst)
         elif field is not None:
             self.ops.patch_elastic_clip_minmax(vols, mask, point, self.size, matrix, field, *cols, dst)
@@ -138,20 +163,26 @@ class DeviceMultiModalPipeline(ResidentVolumes):
         dst = {k: torch.empty((n, len(ds.modalities[k]), *self.size), dtype=torch.float32, device=self.device) for k in "AB"}
         points = torch.empty((n, 2, 4), dtype=torch.int32, device=self.device)
         fields = upload_fields(list(items_A) + list(items_B), self.device)
+        lattices = upload_bias(list(items_A) + list(items_B), self.device)
         field_of = lambda r: None if r.field is None else fields[id(r.field)]
+
+        def aug_of(r):
+            block = active(r.intensity)
+            lattice = None if block is None or block[1] is None else lattices[id(block[1])]
+            return r.matrix, field_of(r), block, lattice
         for i, (a, b) in enumerate(zip(items_A, items_B)):
             mask_A, weight, vols_A = self.case("A", a.index)
             self.ops.voxel_draw(mask_A, weight, self.size, a.u, points[i, 0])
-            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i], a.matrix, field_of(a))
+            self._patch("A", a.index, vols_A, mask_A, points[i, 0], dst["A"][i], *aug_of(a))
             if ds.paired:                                   # the same point, A's mask and A's case
                 points[i, 1].copy_(points[i, 0])
                 self._patch("B", a.index, [self.volume(m, a.index) for m in ds.modalities["B"]], mask_A, points[i, 0],
-                            dst["B"][i], b.matrix, field_of(b))
+                            dst["B"][i], *aug_of(b))
             else:
                 mask_B, _, vols_B = self.case("B", b.index)
                 self.ops.voxel_draw(mask_B, None, self.size, b.u, points[i, 1], focal_A=points[i, 0],
                                     dims_A=tuple(mask_A.shape), proportion=ds.focal_region_proportion)
-                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i], b.matrix, field_of(b))
+                self._patch("B", b.index, vols_B, mask_B, points[i, 1], dst["B"][i], *aug_of(b))
         self.points = points
         out.update(dst)
         return out

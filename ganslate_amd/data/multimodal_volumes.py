@@ -37,6 +37,7 @@ from .. import configs
 from .device_transforms import collate_raw
 from .utils.normalization import min_max_normalize
 from .utils.patch_affine import check_elastic, draw_set, matrix_tuple, parse_augmentation, sample_patch
+from .utils.patch_intensity import active, apply, bias_field, check_intensity, draw_block, is_neutral
 
 PAIRED_SAMPLING_SCHEMES = ("uniform-random-within-body", "fdg-pet-weighted")
 UNPAIRED_SAMPLING_SCHEMES = ("uniform-random-within-body-sf", "fdg-pet-weighted-sf")
@@ -60,7 +61,9 @@ class MultiModalVolumeDatasetConfig(configs.base.BaseDatasetConfig):
     device_transforms: bool = False
     # not in the reference: random flips / rotation / zoom of every patch as one trilinear gather (data/utils/
     # patch_affine.py): {prob, flip: [D, H, W], rotate_deg: [D, H, W], scale: [lo, hi], spacing: [D, H, W],
-    # elastic: {prob, control_points: [D, H, W], max_displacement: [D, H, W] in the units of spacing}}
+    # elastic: {prob, control_points: [D, H, W], max_displacement: [D, H, W] in the units of spacing},
+    # intensity: {prob, modalities, gamma, contrast, brightness, noise_std: [lo, hi] each, bias_field: {prob,
+    # control_points, max}} (data/utils/patch_intensity.py)}
     augmentation: Optional[Dict[str, Any]] = None
 
 
@@ -124,13 +127,15 @@ def draw_focal_point(mask, weight, patch, u, box=None):
 class RawCase:
     """what a worker hands over with device_transforms on: which case, the uniform its focal point is drawn from, the
     augmentation matrix of its patch (9 floats, row-major) or None, and next to it the elastic field (float64
-    [3, G0, G1, G2], already in voxels) or None"""
-    __slots__ = ("domain", "index", "u", "matrix", "field")
+    [3, G0, G1, G2], already in voxels) or None, and last the intensity block of its domain — (rows, bias lattice): one
+    (gamma, contrast, brightness, noise_std, bias, key0, key1) per modality and float64 [G0, G1, G2] or None — or None"""
+    __slots__ = ("domain", "index", "u", "matrix", "field", "intensity")
 
-    def __init__(self, domain, index, u, matrix=None, field=None):
+    def __init__(self, domain, index, u, matrix=None, field=None, intensity=None):
         self.domain, self.index, self.u = domain, int(index), (None if u is None else float(u))
         self.matrix = None if matrix is None else matrix_tuple(matrix)
         self.field = field
+        self.intensity = intensity
 
 
 def _field(node, name, default=None):
@@ -183,6 +188,7 @@ class MultiModalVolumeDataset(Dataset):
         self.raw = bool(_field(d, "device_transforms", False))
         self.augmentation = parse_augmentation(_field(d, "augmentation"), fill_allowed=False)
         check_elastic(self.augmentation, self.patch_size)
+        check_intensity(self.augmentation and self.augmentation.intensity, self.patch_size, names)
 
     def __len__(self):
         return len(self.cases)
@@ -204,25 +210,38 @@ class MultiModalVolumeDataset(Dataset):
                           f"lies in the valid zone of patch size {self.patch_size}")
 
     # ---- host path --------------------------------------------------------------------------------------------------
-    def normalize(self, name, index, patch, mask):
-        """where(mask, v, outside) -> / divisor -> clamp -> min_max_normalize (basic.py:17-41, train_dataset.py:164-172)"""
+    def normalize(self, name, index, patch, mask, intensity=None):
+        """where(mask, v, outside) -> / divisor -> clamp -> min_max_normalize (basic.py:17-41, train_dataset.py:164-172).
+        intensity: None or (row, beta, channel) — the chain of data/utils/patch_intensity.py on the min-max value, in front
+        of its 2 n - 1"""
         lo, hi = self.clip_range[name]
         v = torch.from_numpy(np.array(patch)).float()
         m = torch.from_numpy(np.array(mask) != 0)
         v = torch.where(m, v, torch.tensor(self.outside_value[name], dtype=torch.float32))
         v = v / self.divisor(name, index)
-        return min_max_normalize(torch.clamp(v, lo, hi), lo, hi)
+        if intensity is None or is_neutral(intensity[0]):
+            return min_max_normalize(torch.clamp(v, lo, hi), lo, hi)
+        unit = (torch.clamp(v, lo, hi) - lo) / (hi - lo)                       # min_max_normalize's first half
+        unit = torch.from_numpy(apply(unit.numpy(), *intensity))
+        return 2 * unit - 1
 
-    def crop(self, domain, index, mask, focal, matrix=None, field=None):
+    def crop(self, domain, index, mask, focal, matrix=None, field=None, intensity=None):
         start = [f - p // 2 for f, p in zip(focal, self.patch_size)]
+        names = self.modalities[domain]
+        intensity = active(intensity)
+        chains = [None] * len(names)
+        if intensity is not None:
+            rows, lattice = intensity
+            beta = None if lattice is None else bias_field(self.patch_size, lattice)
+            chains = [(rows[c], beta, c) for c in range(len(names))]
         if matrix is not None:              # mask, then interpolate (sample_patch), then the same chain
             full = np.ones(self.patch_size, bool)
             return torch.stack([self.normalize(n, index, sample_patch(self.load(n, index), mask, start, self.patch_size,
-                                                                      matrix, self.outside_value[n], field), full)
-                                for n in self.modalities[domain]])
+                                                                      matrix, self.outside_value[n], field), full, chains[c])
+                                for c, n in enumerate(names)])
         win = tuple(slice(s, s + p) for s, p in zip(start, self.patch_size))
         m = mask[win]
-        return torch.stack([self.normalize(n, index, self.load(n, index)[win], m) for n in self.modalities[domain]])
+        return torch.stack([self.normalize(n, index, self.load(n, index)[win], m, chains[c]) for c, n in enumerate(names)])
 
     def sample_points(self, index_A, index_B):
         """((focal_A, focal_B), fallback_used) with the reference's consumption of np.random: one uniform per draw"""
@@ -241,12 +260,19 @@ class MultiModalVolumeDataset(Dataset):
         return (focal_A, focal_B), flag
 
     def draw_matrices(self):
-        """((M_A, field_A), (M_B, field_B)) after the sample's other draws: none without `augmentation`, one set (eight
-        uniforms, and the field's with `elastic`) shared by A and B when paired, A's set then B's set when unpaired"""
-        if self.augmentation is None:
-            return (None, None), (None, None)
-        set_A = draw_set(self.augmentation)
-        return set_A, (set_A if self.paired else draw_set(self.augmentation))
+        """((M_A, field_A, intensity_A), (M_B, field_B, intensity_B)) after the sample's other draws: none without
+        `augmentation`, one geometric set (eight uniforms, and the field's with `elastic`) shared by A and B when paired,
+        A's set then B's set when unpaired. With `intensity` every domain's block (patch_intensity.draw_block) follows its
+        geometric set: shared set, A's block, B's block when paired — intensity is never shared — and A's set, A's block,
+        B's set, B's block when unpaired."""
+        aug = self.augmentation
+        if aug is None:
+            return (None, None, None), (None, None, None)
+        block = lambda k: None if aug.intensity is None else draw_block(aug.intensity, self.modalities[k])
+        set_A = draw_set(aug)
+        int_A = block("A")
+        set_B = set_A if self.paired else draw_set(aug)
+        return (*set_A, int_A), (*set_B, block("B"))
 
     def __getitem__(self, index):
         index_A = index % len(self.cases)

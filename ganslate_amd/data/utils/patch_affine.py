@@ -29,14 +29,16 @@ changes for a finite s_a; a NaN or infinite displacement then gives the outside 
 spacing: [1, 1, 1], fill: 0.0 (UnpairedVolumeDataset only), elastic: null or {prob: 1.0, control_points: [7, 7, 7],
 max_displacement: [0, 4, 4]} (D, H, W; in the units of `spacing`)}. Per sample and matrix `draw_params` takes eight
 np.random uniforms — always all eight, after the sample's other draws; with `elastic` set `draw_field` takes
-1 + 3 G_0 G_1 G_2 more after them, always all of them."""
+1 + 3 G_0 G_1 G_2 more after them, always all of them. The `intensity` key (data/utils/patch_intensity.py: bias field,
+contrast, brightness, gamma, noise on the normalised value) needs nothing else here: with everything else neutral the
+matrix drawn is the identity."""
 import math
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Any, Optional, Tuple
 
 import numpy as np
 
-KEYS = ("prob", "flip", "rotate_deg", "scale", "spacing", "fill", "elastic")
+KEYS = ("prob", "flip", "rotate_deg", "scale", "spacing", "fill", "elastic", "intensity")
 ELASTIC_KEYS = ("prob", "control_points", "max_displacement")
 UNIFORMS = 8          # np.random uniforms per drawn matrix
 MAX_CONTROL_POINTS = 1024      # GS_ELASTIC_MAX_POINTS: the lattice travels as 3 * 1024 doubles at the most
@@ -65,6 +67,7 @@ class AffineAugmentation:
     spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0)
     fill: float = 0.0
     elastic: Optional[ElasticAugmentation] = None
+    intensity: Optional[Any] = None          # patch_intensity.IntensityAugmentation
 
 
 def _numbers(name, value, n):
@@ -79,6 +82,7 @@ def _numbers(name, value, n):
 
 def parse_augmentation(node, fill_allowed):
     """the `augmentation` field of a dataset config -> AffineAugmentation, or None when the field is absent / null"""
+    from .patch_intensity import parse_intensity          # that module builds on this one
     if node is None:
         return None
     unknown = sorted(set(node.keys()) - set(KEYS))
@@ -102,7 +106,7 @@ def parse_augmentation(node, fill_allowed):
         raise ValueError("augmentation.fill is UnpairedVolumeDataset's; here a voxel outside the volume or the body mask "
                          "takes the modality's `outside_value`")
     return AffineAugmentation(prob, tuple(bool(v) for v in flip), rotate, scale, spacing, float(get("fill", 0.0)),
-                              parse_elastic(get("elastic", None)))
+                              parse_elastic(get("elastic", None)), parse_intensity(get("intensity", None)))
 
 
 def parse_elastic(node):

@@ -104,6 +104,12 @@ class ImgStackItem(C.Structure):
         (n, C.c_float) for n in ("lo", "hi", "noise_std")] + [("key0", C.c_uint32), ("key1", C.c_uint32), ("pad_", C.c_int32)]
 
 
+class PatchIntensity(C.Structure):
+    """Mirror of GsPatchIntensity."""
+    _fields_ = [(n, C.c_float) for n in ("gamma", "contrast", "brightness", "noise_std", "bias")] + [
+        ("key0", C.c_uint32), ("key1", C.c_uint32), ("pad_", C.c_int32)]
+
+
 _PROTOS = {
     "gs_init": (C.c_int, [C.c_int]),
     "gs_shutdown": (None, []),
@@ -240,6 +246,14 @@ _PROTOS = {
     "gs_patch_elastic": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.c_float,
                                    C.c_void_p, C.c_void_p]),
+    "gs_patch_augment_clip_minmax": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_int32), C.c_void_p, C.POINTER(PatchIntensity),
+                                               C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "gs_patch_zscore_intensity": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.c_float, C.c_float, C.POINTER(PatchIntensity),
+                                            C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_volume_prepare_ws_bytes": (C.c_int64, []),
     "gs_volume_prepare": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float),

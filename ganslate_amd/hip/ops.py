@@ -1190,6 +1190,59 @@ class HipOps(TwinSplit):
         """gs_patch_elastic: patch_affine with a free-form deformation in front of the matrix (field as above)"""
         self._gather_raw("gs_patch_elastic", volume, start, size, matrix, self._lattice(field), fill, out)
 
+    @staticmethod
+    def _intensity(rows, n, bias_lattice):
+        """(GsPatchIntensity[n], bias_grid as int32[3] or None, device pointer or None): rows of (gamma, contrast,
+        brightness, noise_std, bias, key0, key1), one per modality (None: the neutral row); bias_lattice: None or a
+        contiguous float64 device tensor [G0, G1, G2]"""
+        if rows is None or len(rows) != n:
+            raise ValueError(f"intensity: expected one row per modality ({n}); got {None if rows is None else len(rows)}")
+        table = (L.PatchIntensity * n)()
+        for c, r in enumerate(rows):
+            r = (1.0, 1.0, 0.0, 0.0, 0.0, 0, 0) if r is None else r
+            if len(r) != 7:
+                raise ValueError(f"intensity row {c}: expected (gamma, contrast, brightness, noise_std, bias, key0, key1)")
+            t = table[c]
+            t.gamma, t.contrast, t.brightness, t.noise_std, t.bias = [float(v) for v in r[:5]]
+            t.key0, t.key1 = int(r[5]) & 0xffffffff, int(r[6]) & 0xffffffff
+        if bias_lattice is None:
+            return table, None, None
+        b = bias_lattice
+        if not (isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.float64 and b.dim() == 3 and b.is_contiguous()):
+            got = (tuple(b.shape), b.dtype, str(b.device)) if isinstance(b, torch.Tensor) else type(b).__name__
+            raise ValueError(f"bias_lattice: expected a contiguous float64 device tensor of shape [G0, G1, G2]; got {got}")
+        return table, (C.c_int32 * 3)(*[int(v) for v in b.shape]), _ptr(b)
+
+    def patch_augment_clip_minmax(self, volumes, mask, point, patch, matrix, field, intensity, bias_lattice, outside, divisor,
+                                  lo, hi, out):
+        """gs_patch_augment_clip_minmax: patch_elastic_clip_minmax (field None: patch_affine_clip_minmax) with the intensity
+        chain of data/utils/patch_intensity.py between the min-max step and 2 n - 1. intensity: one row (gamma, contrast,
+        brightness, noise_std, bias, key0, key1) per volume; bias_lattice: None or a float64 device tensor [G0, G1, G2]
+        in [-1, 1], shared by the volumes (include/ganslate_hip.h)."""
+        sym = "gs_patch_augment_clip_minmax"
+        n, ptrs, dts, cols = self._mod_table(sym[3:], volumes, mask, outside, divisor, lo, hi)
+        self._point("point", point, 3)
+        self._out_f32(out, (n, *patch))
+        lattice = (None, None) if field is None else self._lattice(field)
+        L.check(self.lib.gs_patch_augment_clip_minmax(ptrs, dts, n, _ptr(mask), *mask.shape, _ptr(point),
+                                                      (C.c_int32 * 3)(*[int(v) for v in patch]), self._matrix(matrix),
+                                                      *lattice, *self._intensity(intensity, n, bias_lattice), *cols,
+                                                      _ptr(out), _stream()), sym)
+
+    def patch_zscore_intensity(self, volume, start, size, out, intensity, bias_lattice=None, scale_to_range=(-1.0, 1.0)):
+        """gs_patch_zscore_intensity: patch_zscore with rescale and the intensity chain on n = (t - min t) / (max t - min t);
+        intensity: one row (gamma, contrast, brightness, noise_std, bias, key0, key1); bias_lattice as above"""
+        assert volume.dim() == 3 and volume.is_contiguous() and volume.dtype in self.VOL_DTYPES, (volume.shape, volume.dtype)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == size[0] * size[1] * size[2]
+        nws = getattr(self, "_patch_ws", None) or int(self.lib.gs_patch_zscore_ws_floats())
+        self._patch_ws = nws
+        ws = torch.empty(nws, dtype=torch.float32, device=self.device)        # per launch: stream-safe through the allocator
+        st, sz = (C.c_int32 * 3)(*[int(v) for v in start]), (C.c_int32 * 3)(*[int(v) for v in size])
+        lo, hi = scale_to_range
+        L.check(self.lib.gs_patch_zscore_intensity(_ptr(volume), self.VOL_DTYPES[volume.dtype], *volume.shape, st, sz,
+                                                   float(lo), float(hi), *self._intensity([intensity], 1, bias_lattice),
+                                                   _ptr(out), _ptr(ws), _stream()), "gs_patch_zscore_intensity")
+
     def volume_prepare(self, volumes, mask, extra_masks, target, outside, divisor, lo, hi, out=None, masks_out=None):
         """gs_volume_prepare: one whole case for the val / test engines -> (out, [masks]). volumes: C fp32 / int16
         (D, H, W) device tensors; mask: the body mask (uint8, non-zero = inside); extra_masks: up to VM_MAX_LABELS further

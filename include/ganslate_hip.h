@@ -662,6 +662,57 @@ int gs_patch_elastic_clip_minmax(const void* const* vols, const int32_t* dtypes,
 int gs_patch_elastic(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
                      const int32_t* size, const double* M, const int32_t* grid, const double* field, float fill, float* out,
                      void* stream);
+/* Intensity augmentation in the same launches: a smooth multiplicative bias field, contrast and brightness, gamma and
+ * additive Gaussian noise, applied to the value the patch kernels hold in a register just before they store it.
+ * THE DEFINITION (data/utils/patch_intensity.py states it in numpy, tests/patch_intensity_ref.py as a per-voxel loop).
+ * The chain acts on the normalised value n that both normalisations form:
+ *   clip / min-max chain:  n = (v - lo) / (hi - lo), between that step and 2 n - 1
+ *   z-score with rescale:  t = (v - mean) / std, n = (t - min t) / (max t - min t); the last step is then
+ *                          (hi - lo) * n + lo, one multiply and one add
+ * Per modality one GsPatchIntensity. All arithmetic is fp32, one IEEE operation per step, no fused multiply-add; voxel
+ * i is the linear index of the output voxel in its [d, h, w] patch, c its channel (0 for the z-score entry).
+ *   1. bias != 0:  beta = the cubic B-spline interpolation at the voxel of ONE scalar lattice BETA[i][j][k] (float64, C
+ *      order, G = bias_grid, aligned with the patch), exactly as one component of the elastic field above: the same num /
+ *      den / j / f, the same weights, D innermost, then H, W outermost, every sum left to right.
+ *      m = (float)(1.0 + (double)bias * beta), one float64 multiply and one float64 add;  n = n * m
+ *   2. contrast != 1 or brightness != 0:  n = (((n - 0.5) * contrast) + 0.5) + brightness
+ *   3. n = n < 0 ? 0 : n;  n = n > 1 ? 1 : n          (NaN stays NaN)
+ *   4. gamma != 1:  n = powf(n, gamma) — the one step whose bits the host restatement and the device need not share
+ *   5. noise_std > 0:  n = n + noise_std * z, z = sqrt(-2 ln u1) * cos(2 pi u2) as in gs_img_stack, u1 and u2 from the
+ *      first two words of Philox4x32-10 on the counter (i & 0xffffffff, i >> 32, c, 0) and the key (key0, key1)
+ *   6. step 3 again
+ * A step whose parameters are neutral is skipped, not evaluated ((n - 0.5) + 0.5 is not n for a small n), and the clamps
+ * change no bit of a value in [0, 1]: a neutral descriptor gives the bits of gs_patch_elastic_clip_minmax /
+ * gs_patch_affine_clip_minmax. (gs_patch_zscore rounds (hi - lo) * (t - min t) / (max t - min t) in another order than
+ * (hi - lo) * n; a neutral sample takes gs_patch_zscore.) The lattice is shared by the modalities of a launch, each
+ * scales it by its own bias. A NaN lattice entry gives NaN inside its 4 x 4 x 4 support and nothing outside; a constant
+ * z-score patch gives NaN as in gs_patch_zscore.
+ *
+ * gs_patch_augment_clip_minmax: gs_patch_elastic_clip_minmax with grid / field nullable together (null: the affine
+ * gather) plus intensity (HOST array of C descriptors, copied into the kernel argument), bias_grid (host int32[3],
+ * nullable) and bias_field (DEVICE double[G_0 G_1 G_2], nullable, never modified). beta is evaluated once per voxel in
+ * front of the modality loop in the two forms of the elastic part, by the size of the combined row table against the
+ * option elastic_rows; the forms give the same bits. The elastic and the bias lattice may have different grids.
+ * gs_patch_zscore_intensity: gs_patch_zscore with rescale plus the same three arguments (one descriptor): the stats
+ * and finalize launches unchanged, then an apply pass that stages the lattice in LDS per workgroup.
+ * Both refuse, before any launch, what their base entries refuse and: a null intensity; a gamma that is not positive and
+ * finite; a contrast or noise_std that is negative or not finite; a brightness that is not finite; |bias| >= 1 or NaN;
+ * a non-zero bias without bias_grid / bias_field (and one of the two without the other); for bias_grid what the elastic
+ * entries refuse for grid. No atomics, no further workspace, no host synchronisation; every output element is written
+ * exactly once. */
+typedef struct {
+  float gamma, contrast, brightness, noise_std, bias;
+  uint32_t key0, key1;
+  int32_t pad_;
+} GsPatchIntensity;
+int gs_patch_augment_clip_minmax(const void* const* vols, const int32_t* dtypes, int32_t C, const uint8_t* mask, int32_t D,
+                                 int32_t H, int32_t W, const int32_t* point, const int32_t* patch, const double* M,
+                                 const int32_t* grid, const double* field, const GsPatchIntensity* intensity,
+                                 const int32_t* bias_grid, const double* bias_field, const float* outside,
+                                 const float* divisor, const float* lo, const float* hi, float* out, void* stream);
+int gs_patch_zscore_intensity(const void* vol, int32_t dtype, int32_t D, int32_t H, int32_t W, const int32_t* start,
+                              const int32_t* size, float lo, float hi, const GsPatchIntensity* intensity,
+                              const int32_t* bias_grid, const double* bias_field, float* out, float* scratch, void* stream);
 /* gs_volume_prepare: one whole case for the val / test engines (the reference's val_test_dataset.py:136-161): body
  * masking, centred padding to a target shape and the per-voxel chain of gs_patch_clip_minmax, for all C
  * (1..GS_PATCH_MAX_MODALITIES) volumes and M (1..1 + GS_VM_MAX_LABELS) byte masks of a D x H x W case. masks[0] is the

@@ -2,7 +2,8 @@
 is the run of this tool before the elastic launch existed): gs_patch_clip_minmax, gs_patch_affine_clip_minmax through a
 30 degrees x 1.1 matrix, and gs_patch_elastic_clip_minmax through the same matrix behind a 7 x 7 x 7 lattice of random
 displacements within 0.3 of the control spacing — in its row-shared form (the one launched) and, forced by the library option
-elastic_rows = 0, in its per-voxel form. All for the HX4 patch (32, 128, 128) with C = 2 int16 volumes of a resident
+elastic_rows = 0, in its per-voxel form — and gs_patch_augment_clip_minmax, the same elastic gather with the intensity chain
+(bias field on a 4 x 4 x 4 lattice, contrast, brightness, gamma, noise) on both modalities, in both forms. All for the HX4 patch (32, 128, 128) with C = 2 int16 volumes of a resident
 (128, 256, 256) case and its body mask. The plain crop is the yardstick; the ratios are reported, nothing is gated.
 
 Each measurement is a child process of its own under its own time limit (10 warm-up launches, then 100 launches between HIP
@@ -30,7 +31,10 @@ WARMUP, LAUNCHES = 10, 100
 STEP_LIMIT_S = 180
 GRID, FRACTION = (7, 7, 7), 0.3
 KINDS = (("plain", "gs_patch_clip_minmax (plain crop)"), ("affine", "gs_patch_affine_clip_minmax (30 deg x 1.1)"),
-         ("elastic", "gs_patch_elastic_clip_minmax, row-shared"), ("elastic_voxel", "gs_patch_elastic_clip_minmax, per voxel"))
+         ("elastic", "gs_patch_elastic_clip_minmax, row-shared"), ("elastic_voxel", "gs_patch_elastic_clip_minmax, per voxel"),
+         ("augment", "gs_patch_augment_clip_minmax, row-shared"), ("augment_voxel", "gs_patch_augment_clip_minmax, per voxel"))
+BIAS_GRID = (4, 4, 4)
+INTENSITY = [(0.8, 1.2, -0.05, 0.03, 0.3, 5, 6), (1.3, 0.9, 0.05, 0.02, 0.3, 7, 8)]       # every step of the chain on
 
 
 def matrix():
@@ -61,9 +65,13 @@ def step(kind):
     else:
         bound = np.array([FRACTION * (PATCH[a] - 1) / (GRID[a] - 3) for a in range(3)]).reshape(3, 1, 1, 1)
         field = torch.from_numpy((2.0 * rng.random((3, *GRID)) - 1.0) * bound).to(dev)
-        if kind == "elastic_voxel":
+        if kind.endswith("_voxel"):
             ops.set_option("elastic_rows", 0)
-        fn = lambda: ops.patch_elastic_clip_minmax(vols, mask, point, PATCH, M, field, *cols, out)
+        if kind.startswith("augment"):                  # the same field, plus bias field, contrast, gamma and noise
+            beta = torch.from_numpy(2.0 * rng.random(BIAS_GRID) - 1.0).to(dev)
+            fn = lambda: ops.patch_augment_clip_minmax(vols, mask, point, PATCH, M, field, INTENSITY, beta, *cols, out)
+        else:
+            fn = lambda: ops.patch_elastic_clip_minmax(vols, mask, point, PATCH, M, field, *cols, out)
     for _ in range(WARMUP):
         fn()
     torch.cuda.synchronize()
@@ -128,6 +136,9 @@ def main():
     lines.append(f"ratio elastic / affine, this session: {med['elastic'] / med['affine']:.2f} (median per launch), "
                  f"{win['elastic'] / win['affine']:.2f} (window mean); per voxel / row-shared: "
                  f"{med['elastic_voxel'] / med['elastic']:.2f}, {win['elastic_voxel'] / win['elastic']:.2f}.")
+    lines.append(f"ratio augment / elastic (the intensity chain on both modalities, a {BIAS_GRID[0]} x {BIAS_GRID[1]} x {BIAS_GRID[2]} bias "
+                 f"lattice): {med['augment'] / med['elastic']:.2f} (median per launch), {win['augment'] / win['elastic']:.2f} (window mean); "
+                 f"per voxel: {med['augment_voxel'] / med['elastic_voxel']:.2f}, {win['augment_voxel'] / win['elastic_voxel']:.2f}.")
     before = re.search(r"^gs_patch_affine_clip_minmax.*?median\s+([\d.]+) us.*?window mean\s+([\d.]+) us",
                        (ROOT / "profiles" / "patch_affine.txt").read_text(), flags=re.M)
     if before:
