@@ -39,6 +39,16 @@ __device__ __forceinline__ uint4 pack_bf8(const float* f) {
   o.x = pack_bf2(f[0], f[1]); o.y = pack_bf2(f[2], f[3]); o.z = pack_bf2(f[4], f[5]); o.w = pack_bf2(f[6], f[7]);
   return o;
 }
+// the Cp (a multiple of 8) bf16 lanes of one pixel at px (16-byte aligned) from value(c), eight lanes per 16-byte store
+template <class F>
+__device__ __forceinline__ void store_bf_lanes(unsigned short* px, int Cp, F&& value) {
+  for (int c0 = 0; c0 < Cp; c0 += 8) {
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = value(c0 + k);
+    *reinterpret_cast<uint4*>(px + c0) = pack_bf8(f);
+  }
+}
 
 // 16-byte LDS-DMA: LDS destination = wave-uniform base + lane*16; global source is per lane.
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
@@ -132,6 +142,23 @@ __device__ __forceinline__ int border_index(int x, int n, int mode, bool& ok) {
   xc = xc >= n ? n - 1 : xc;
   ok = ok & (inb | (mode != GS_BORDER_ZERO));
   return mode == GS_BORDER_REFLECT ? xr : (mode == GS_BORDER_REPLICATE ? xc : x);
+}
+
+// the adjoint of that padding along one axis: the positions, in coordinates padded by p, that the padding maps onto x
+// (x + p itself first; reflect: <= 3 in all, replicate: a border cell and its p pad cells, p <= 3) -> their count
+__device__ __forceinline__ int fold_sources(int* idx, int x, int n, int p, int mode) {
+  int cnt = 1;
+  idx[0] = x + p;
+  if (p > 0) {
+    if (mode == GS_BORDER_REFLECT) {
+      if (x >= 1 && x <= p) idx[cnt++] = p - x;
+      if (x >= n - 1 - p && x <= n - 2) idx[cnt++] = p + 2 * (n - 1) - x;
+    } else if (mode == GS_BORDER_REPLICATE) {
+      if (x == 0) for (int k = 0; k < p; ++k) idx[cnt++] = k;
+      if (x == n - 1) for (int k = 1; k <= p; ++k) idx[cnt++] = n - 1 + p + k;
+    }
+  }
+  return cnt;
 }
 
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {

@@ -8,14 +8,8 @@ __global__ __launch_bounds__(256) void image_to_act_kernel(const float* img, uns
   const int n = blockIdx.y;
   const float* in = img + (size_t)n * C * hw;
   unsigned short* out = act + (size_t)n * hw * Cp;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
-    for (int c0 = 0; c0 < Cp; c0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) f[k] = (c0 + k < C) ? in[(size_t)(c0 + k) * hw + p] : 0.f;
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
-    }
-  }
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x)
+    store_bf_lanes(out + (size_t)p * Cp, Cp, [&](int c) { return c < C ? in[(size_t)c * hw + p] : 0.f; });
 }
 
 __global__ __launch_bounds__(256) void act_to_image_kernel(const unsigned short* act, float* img, int C, long long hw,
@@ -34,38 +28,15 @@ __global__ __launch_bounds__(256) void act_to_image_bwd_kernel(const float* g_im
   const float* gi = g_img + (size_t)n * C * hw;
   const float* oi = out_img ? out_img + (size_t)n * C * hw : nullptr;
   unsigned short* out = g_act + (size_t)n * hw * Cp;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
-    for (int c0 = 0; c0 < Cp; c0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int c = c0 + k;
-        float v = 0.f;
-        if (c < C) {
-          v = gi[(size_t)c * hw + p];
-          if (oi) v *= act_grad_from_out(oi[(size_t)c * hw + p], act_kind, 0.f);
-        }
-        f[k] = v;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x)
+    store_bf_lanes(out + (size_t)p * Cp, Cp, [&](int c) {
+      float v = 0.f;
+      if (c < C) {
+        v = gi[(size_t)c * hw + p];
+        if (oi) v *= act_grad_from_out(oi[(size_t)c * hw + p], act_kind, 0.f);
       }
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
-    }
-  }
-}
-
-// sources of the pad adjoint along one axis (reflect: <= 3, replicate: border cell + its p pad cells, p <= 3)
-__device__ __forceinline__ int img_fold_sources(int* idx, int x, int n, int p, int mode) {
-  int cnt = 1;
-  idx[0] = x + p;
-  if (p > 0) {
-    if (mode == GS_BORDER_REFLECT) {
-      if (x >= 1 && x <= p) idx[cnt++] = p - x;
-      if (x >= n - 1 - p && x <= n - 2) idx[cnt++] = p + 2 * (n - 1) - x;
-    } else {
-      if (x == 0) for (int k = 0; k < p; ++k) idx[cnt++] = k;
-      if (x == n - 1) for (int k = 1; k <= p; ++k) idx[cnt++] = n - 1 + p + k;
-    }
-  }
-  return cnt;
+      return v;
+    });
 }
 
 __global__ __launch_bounds__(256) void image_to_act_bwd_kernel(const unsigned short* g_pad, float* g_img, int C, int D,
@@ -82,9 +53,9 @@ __global__ __launch_bounds__(256) void image_to_act_bwd_kernel(const unsigned sh
     const int iw = (int)(p - zi * W);
     const int iz = (int)(zi / H), ih = (int)(zi - (long long)iz * H);
     int ds[8], hs[8], ws[8];
-    const int nd = img_fold_sources(ds, iz, D, fd, mode);
-    const int nh = img_fold_sources(hs, ih, H, fold, mode);
-    const int nw = img_fold_sources(ws, iw, W, fold, mode);
+    const int nd = fold_sources(ds, iz, D, fd, mode);
+    const int nh = fold_sources(hs, ih, H, fold, mode);
+    const int nw = fold_sources(ws, iw, W, fold, mode);
     for (int c = 0; c < C; ++c) {
       float s = 0.f;
       for (int e = 0; e < nd; ++e)
@@ -107,60 +78,6 @@ extern "C" int gs_image_to_act(const float* img, void* act, int32_t N, int32_t C
   const long long hw = (long long)H * W;
   hipLaunchKernelGGL(image_to_act_kernel, img_grid(hw, N), dim3(256), 0, static_cast<hipStream_t>(stream), img,
                      static_cast<unsigned short*>(act), C, hw, Cp);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// Two images side by side along the channel axis (the conditional discriminator's input torch.cat([real_A, fake_B], dim=1),
-// ganslate/nn/gans/paired/pix2pix.py:70,80) converted in one pass: channel c < Ca comes from a, the others from b.
-__global__ __launch_bounds__(256) void image_pair_to_act_kernel(const float* a, int Ca, const float* b, int Cb,
-                                                                unsigned short* act, long long hw, int Cp) {
-  const int n = blockIdx.y;
-  const float* ia = a + (size_t)n * Ca * hw;
-  const float* ib = b + (size_t)n * Cb * hw;
-  unsigned short* out = act + (size_t)n * hw * Cp;
-  const int C = Ca + Cb;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
-    for (int c0 = 0; c0 < Cp; c0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int c = c0 + k;
-        f[k] = c < Ca ? ia[(size_t)c * hw + p] : (c < C ? ib[(size_t)(c - Ca) * hw + p] : 0.f);
-      }
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
-    }
-  }
-}
-// its gradient: channels [0, Ca) of g to ga, [Ca, Ca + Cb) to gb (either may be null: that part needs no gradient)
-__global__ __launch_bounds__(256) void image_pair_to_act_bwd_kernel(const unsigned short* g, float* ga, int Ca, float* gb,
-                                                                    int Cb, long long hw, int Cp) {
-  const int n = blockIdx.y;
-  const unsigned short* gp = g + (size_t)n * hw * Cp;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
-    if (ga)
-      for (int c = 0; c < Ca; ++c) ga[((size_t)n * Ca + c) * hw + p] = bf2f(gp[(size_t)p * Cp + c]);
-    if (gb)
-      for (int c = 0; c < Cb; ++c) gb[((size_t)n * Cb + c) * hw + p] = bf2f(gp[(size_t)p * Cp + Ca + c]);
-  }
-}
-
-extern "C" int gs_image_pair_to_act(const float* a, int32_t Ca, const float* b, int32_t Cb, void* act, int32_t N, int32_t H,
-                                    int32_t W, int32_t Cp, void* stream) {
-  GS_REQUIRE(a && b && act && N > 0 && Ca > 0 && Cb > 0 && Cp >= Ca + Cb && (Cp & 7) == 0, "gs_image_pair_to_act: bad argument");
-  const long long hw = (long long)H * W;
-  hipLaunchKernelGGL(image_pair_to_act_kernel, img_grid(hw, N), dim3(256), 0, static_cast<hipStream_t>(stream), a, Ca, b, Cb,
-                     static_cast<unsigned short*>(act), hw, Cp);
-  GS_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-extern "C" int gs_image_pair_to_act_backward(const void* g, float* ga, int32_t Ca, float* gb, int32_t Cb, int32_t N, int32_t H,
-                                             int32_t W, int32_t Cp, void* stream) {
-  GS_REQUIRE(g && (ga || gb) && N > 0 && Ca > 0 && Cb > 0 && Cp >= Ca + Cb, "gs_image_pair_to_act_backward: bad argument");
-  const long long hw = (long long)H * W;
-  hipLaunchKernelGGL(image_pair_to_act_bwd_kernel, img_grid(hw, N), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const unsigned short*>(g), ga, Ca, gb, Cb, hw, Cp);
   GS_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -205,8 +122,9 @@ extern "C" int gs_image_to_act_backward(const void* g_pad, float* g_img, int32_t
 // ---- channel sources ------------------------------------------------------------------------------------------------------
 // Up to GS_CAT_MAX_SRCS image tensors side by side along the channel axis, each a channel window of a dense [N, C, S] fp32
 // tensor: N blocks of channels * S contiguous floats, `stride` floats from one sample to the next, `ptr` at the window's first
-// element (c0 * S floats into the tensor). torch.cat([fake_Bt, real_A[:, guide]], dim=1) and real_B[:, tB] -> bf16 activation
-// in one pass, no concatenated or sliced tensor in memory. A window base is in general not 16-byte aligned (odd S): every
+// element (c0 * S floats into the tensor). torch.cat([fake_Bt, real_A[:, guide]], dim=1), real_B[:, tB] and the conditional
+// discriminator's torch.cat([real_A, fake_B], dim=1) (two whole tensors, pix2pix.py:70,80) -> bf16 activation in one pass, no
+// concatenated or sliced tensor in memory. A window base is in general not 16-byte aligned (odd S): every
 // source read is a scalar fp32 load, coalesced along the pixels; rounding and the zeroed pad lanes are image_to_act_kernel's.
 struct ChanSrcs {
   const float* ptr[GS_CAT_MAX_SRCS];
@@ -218,25 +136,18 @@ struct ChanSrcs {
 __global__ __launch_bounds__(256) void image_cat_to_act_kernel(const ChanSrcs s, unsigned short* act, long long hw, int Cp) {
   const int n = blockIdx.y;
   unsigned short* out = act + (size_t)n * hw * Cp;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x) {
-    for (int c0 = 0; c0 < Cp; c0 += 8) {
-      float f[8];
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (long long)gridDim.x * blockDim.x)
+    store_bf_lanes(out + (size_t)p * Cp, Cp, [&](int b) {      // b: channel within source j once 0 <= b < ch[j]
+      float v = 0.f;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        int b = c0 + k;           // channel within source j once 0 <= b < ch[j]
-        float v = 0.f;
-#pragma unroll
-        for (int j = 0; j < GS_CAT_MAX_SRCS; ++j) {
-          if (j < s.n) {
-            if (b >= 0 && b < s.ch[j]) v = s.ptr[j][(size_t)n * s.stride[j] + (size_t)b * hw + p];
-            b -= s.ch[j];
-          }
+      for (int j = 0; j < GS_CAT_MAX_SRCS; ++j) {
+        if (j < s.n) {
+          if (b >= 0 && b < s.ch[j]) v = s.ptr[j][(size_t)n * s.stride[j] + (size_t)b * hw + p];
+          b -= s.ch[j];
         }
-        f[k] = v;
       }
-      *reinterpret_cast<uint4*>(out + (size_t)p * Cp + c0) = pack_bf8(f);
-    }
-  }
+      return v;
+    });
 }
 
 // its gradient: the channels of source j, as a dense [N, ch[j], S] fp32 tensor at grad[j]; a null grad[j] is left alone

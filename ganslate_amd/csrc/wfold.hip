@@ -10,22 +10,6 @@
 // gs_gconv_forward / gs_wgrad launches on the transformed layer. HBM-bound, one thread per pixel.
 #include "common.hpp"
 
-// source positions (padded coordinates) that the padding maps onto x: reflect <= 3, replicate <= p+1 (p <= 3)
-__device__ __forceinline__ int wf_sources(int* idx, int x, int n, int p, int mode) {
-  int cnt = 1;
-  idx[0] = x + p;
-  if (p > 0) {
-    if (mode == GS_BORDER_REFLECT) {
-      if (x >= 1 && x <= p) idx[cnt++] = p - x;
-      if (x >= n - 1 - p && x <= n - 2) idx[cnt++] = p + 2 * (n - 1) - x;
-    } else if (mode == GS_BORDER_REPLICATE) {
-      if (x == 0) for (int k = 0; k < p; ++k) idx[cnt++] = k;
-      if (x == n - 1) for (int k = 1; k <= p; ++k) idx[cnt++] = n - 1 + p + k;
-    }
-  }
-  return cnt;
-}
-
 __global__ __launch_bounds__(256) void image_unfold_kernel(const float* img, unsigned short* act, int C, long long rows,
                                                            int W, int Qp, int k, int p, int mode) {
   const int n = blockIdx.y;
@@ -35,22 +19,16 @@ __global__ __launch_bounds__(256) void image_unfold_kernel(const float* img, uns
   for (long long px = (long long)blockIdx.x * 256 + threadIdx.x; px < hw; px += (long long)gridDim.x * 256) {
     const long long r = px / W;
     const int j = (int)(px - r * W);
-    for (int q0 = 0; q0 < Qp; q0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int q = q0 + e;
-        float v = 0.f;
-        if (q < k * C) {
-          const int dw = q / C, c = q - dw * C;
-          bool ok = true;
-          const int jj = border_index(j + dw - p, W, mode, ok);
-          if (ok) v = in[(size_t)c * hw + r * W + jj];
-        }
-        f[e] = v;
+    store_bf_lanes(out + (size_t)px * Qp, Qp, [&](int q) {
+      float v = 0.f;
+      if (q < k * C) {
+        const int dw = q / C, c = q - dw * C;
+        bool ok = true;
+        const int jj = border_index(j + dw - p, W, mode, ok);
+        if (ok) v = in[(size_t)c * hw + r * W + jj];
       }
-      *reinterpret_cast<uint4*>(out + (size_t)px * Qp + q0) = pack_bf8(f);
-    }
+      return v;
+    });
   }
 }
 
@@ -70,9 +48,9 @@ __global__ __launch_bounds__(256) void image_unfold_bwd_kernel(const unsigned sh
     const int j = (int)(px - zi * W);
     const int iz = (int)(zi / H), ih = (int)(zi - (long long)iz * H);
     int ds[8], hs[8], ws[8];
-    const int nd = wf_sources(ds, iz, D, fd, mode);
-    const int nh = wf_sources(hs, ih, H, fold, mode);
-    const int nw = wf_sources(ws, j, W, p, mode);       // W positions in coordinates padded by p
+    const int nd = fold_sources(ds, iz, D, fd, mode);
+    const int nh = fold_sources(hs, ih, H, fold, mode);
+    const int nw = fold_sources(ws, j, W, p, mode);       // W positions in coordinates padded by p
     for (int c = 0; c < C; ++c) {
       float s = 0.f;
       for (int a = 0; a < nd; ++a)
@@ -120,25 +98,19 @@ __global__ __launch_bounds__(256) void shiftadd_bwd_kernel(const float* g_img, c
   for (long long px = (long long)blockIdx.x * 256 + threadIdx.x; px < hwx; px += (long long)gridDim.x * 256) {
     const long long r = px / Wx;
     const int jp = (int)(px - r * Wx);
-    for (int q0 = 0; q0 < Pp; q0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int q = q0 + e;
-        float v = 0.f;
-        if (q < k * Co) {
-          const int dw = q / Co, co = q - dw * Co;
-          const int j = jp - dw;
-          if (j >= 0 && j < W) {
-            const size_t o = (size_t)co * hw + r * W + j;
-            v = gi[o];
-            if (oi) v *= act_grad_from_out(oi[o], act_kind, 0.f);
-          }
+    store_bf_lanes(out + (size_t)px * Pp, Pp, [&](int q) {
+      float v = 0.f;
+      if (q < k * Co) {
+        const int dw = q / Co, co = q - dw * Co;
+        const int j = jp - dw;
+        if (j >= 0 && j < W) {
+          const size_t o = (size_t)co * hw + r * W + j;
+          v = gi[o];
+          if (oi) v *= act_grad_from_out(oi[o], act_kind, 0.f);
         }
-        f[e] = v;
       }
-      *reinterpret_cast<uint4*>(out + (size_t)px * Pp + q0) = pack_bf8(f);
-    }
+      return v;
+    });
   }
 }
 
@@ -210,20 +182,14 @@ __global__ __launch_bounds__(256) void shiftadd_bwd_row_kernel(const float* g_im
   const int t = threadIdx.x;
   if (t < nvx) {
     unsigned short* out = gz + (((size_t)n * rows + r) * Wx + jp0 + t) * Pp;
-    for (int q0 = 0; q0 < Pp; q0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int q = q0 + e;
-        float v = 0.f;
-        if (q < k * Co) {
-          const int dw = q / Co, co = q - dw * Co;
-          v = lds[co * L + t + (k - 1) - dw];               // image pixel jp - dw (zero outside the image)
-        }
-        f[e] = v;
+    store_bf_lanes(out, Pp, [&](int q) {
+      float v = 0.f;
+      if (q < k * Co) {
+        const int dw = q / Co, co = q - dw * Co;
+        v = lds[co * L + t + (k - 1) - dw];                 // image pixel jp - dw (zero outside the image)
       }
-      *reinterpret_cast<uint4*>(out + q0) = pack_bf8(f);
-    }
+      return v;
+    });
   }
 }
 
@@ -248,20 +214,14 @@ __global__ __launch_bounds__(256) void image_unfold_row_kernel(const float* img,
   const int j = threadIdx.x;
   if (j < npx) {
     unsigned short* out = act + (((size_t)n * rows + r) * W + j0 + j) * Qp;
-    for (int q0 = 0; q0 < Qp; q0 += 8) {
-      float f[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int q = q0 + e;
-        float v = 0.f;
-        if (q < k * C) {
-          const int dw = q / C, c = q - dw * C;
-          v = lds[c * L + j + dw];
-        }
-        f[e] = v;
+    store_bf_lanes(out, Qp, [&](int q) {
+      float v = 0.f;
+      if (q < k * C) {
+        const int dw = q / C, c = q - dw * C;
+        v = lds[c * L + j + dw];
       }
-      *reinterpret_cast<uint4*>(out + q0) = pack_bf8(f);
-    }
+      return v;
+    });
   }
 }
 
@@ -279,8 +239,8 @@ __global__ __launch_bounds__(256) void image_unfold_bwd_row_kernel(const unsigne
   const int iz = blockIdx.x / H, ih = blockIdx.x - iz * H;
   float* out = g_img + (size_t)n * C * hw + ((size_t)iz * H + ih) * W;
   int ds[8], hs[8];
-  const int nd = wf_sources(ds, iz, D, fd, mode);
-  const int nh = wf_sources(hs, ih, H, fold, mode);
+  const int nd = fold_sources(ds, iz, D, fd, mode);
+  const int nh = fold_sources(hs, ih, H, fold, mode);
   constexpr int MAXJ = 4, MAXC = 4;                      // pixels per thread (W <= 1024), channels
   float acc[MAXJ][MAXC];
 #pragma unroll
@@ -299,7 +259,7 @@ __global__ __launch_bounds__(256) void image_unfold_bwd_row_kernel(const unsigne
         const int j = threadIdx.x + u * 256;
         if (j < W) {
           int ws[8];
-          const int nw = wf_sources(ws, j, W, p, mode);
+          const int nw = fold_sources(ws, j, W, p, mode);
           for (int c = 0; c < C; ++c) {
             float s = 0.f;
             for (int e = 0; e < nw; ++e)

@@ -183,10 +183,6 @@ _PROTOS = {
                                      C.c_int64, C.c_void_p]),
     "gs_image_to_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p]),
-    "gs_image_pair_to_act": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_int32, C.c_void_p]),
-    "gs_image_pair_to_act_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "gs_image_cat_to_act": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                       C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "gs_image_cat_to_act_backward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32,

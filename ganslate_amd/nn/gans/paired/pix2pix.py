@@ -24,6 +24,13 @@ class Pix2PixConditionalGANConfig(configs.base.BaseGANConfig):
     optimizer: OptimizerConfig = field(default_factory=OptimizerConfig)
 
 
+def _takes_channel_sources(D):
+    """True when D converts images that lie side by side along the channel axis itself (NativeNet.forward_parts_cat);
+    every other discriminator takes the concatenated tensor"""
+    supports = getattr(D, "supports_channel_sources", None)
+    return supports is not None and supports()
+
+
 class Pix2PixConditionalGAN(BaseGAN):
     graph_capturable = True      # fixed launch sequence, no image pool
     side_stream_names = ("D",)
@@ -74,7 +81,7 @@ class Pix2PixConditionalGAN(BaseGAN):
         # the generated image feeds the discriminator and the L1 term: two aliases whose gradients the library adds
         # (losses/functional.py: fanout) instead of autograd's accumulation
         fake_B, fake_B2 = fanout(fake_B)
-        if hasattr(D, "forward_parts_cat"):      # D(torch.cat([real_A, fake_B], dim=1)) without the concatenated tensor
+        if _takes_channel_sources(D):      # D(torch.cat([real_A, fake_B], dim=1)) without the concatenated tensor
             pred, = D.forward_parts_cat([(real_A, fake_B)])
         else:
             pred = D(torch.cat([real_A, fake_B], dim=1))
@@ -89,7 +96,7 @@ class Pix2PixConditionalGAN(BaseGAN):
     def backward_D(self):
         real_A, real_B, fake_B = self.visuals["real_A"], self.visuals["real_B"], self.visuals["fake_B"]
         D = self.networks["D"]
-        if hasattr(D, "forward_parts_cat"):  # D(real pair) and D(fake pair) as one pass over both batches (per-sample norm),
+        if _takes_channel_sources(D):  # D(real pair) and D(fake pair) as one pass over both batches (per-sample norm),
             # each pair converted side by side (no torch.cat)
             self.pred_real, self.pred_fake = D.forward_parts_cat([(real_A, real_B), (real_A, fake_B.detach())])
         else:

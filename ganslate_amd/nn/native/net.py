@@ -559,11 +559,9 @@ class NativeNet:
     def forward_parts_cat(self, pairs):
         """forward_parts for batches that are each torch.cat([a, b], dim=1) of two images (the conditional discriminator:
         D(cat(real_A, fake_B)), pix2pix.py:70,80): the images are converted side by side into the first activation, no
-        concatenated tensor exists -> one output per batch"""
-        pairs = [(a.contiguous().float(), b.contiguous().float()) for a, b in pairs]
-        return run_pass(PassForm(self, lambda ts: pairs_shape(zip(ts[::2], ts[1::2])),
-                                 lambda gx: [g for pair in gx for g in pair], parts=pairs_shape(pairs)),
-                        [t for pair in pairs for t in pair])
+        concatenated tensor exists -> one output per batch. forward_sources with two whole-tensor sources per batch."""
+        return self.forward_sources([[(t, 0, t.shape[1]) for t in (a.contiguous().float(), b.contiguous().float())]
+                                     for a, b in pairs])
 
     def supports_channel_sources(self):
         """True when images enter this network through the plain image conversion (gs_image_to_act), which the channel-source
@@ -626,7 +624,7 @@ class NativeNet:
 
     # ---- the image boundary, batch part by batch part (shared with the executors that walk their own graph) ----------
     def _images_to_act(self, xs, a):
-        """the parts xs of a batch (tensors, ChannelCat pairs, ChannelSources) -> the first activation a"""
+        """the parts xs of a batch (tensors, ChannelSources) -> the first activation a"""
         ops, sp0, n0 = self.ops, self.nodes[0].spec, 0
         for xh in xs:
             ah = a[n0:n0 + xh.shape[0]]
@@ -634,9 +632,6 @@ class NativeNet:
             if isinstance(xh, ChannelSources):
                 assert sp0.wfold != "in", "channel sources enter through the plain image conversion"
                 ops.image_cat_to_act(list(xh), ah)
-            elif isinstance(xh, ChannelCat):
-                assert sp0.wfold != "in", "channel pairs enter through the plain image conversion"
-                ops.image_pair_to_act(xh[0], xh[1], ah)
             elif sp0.wfold == "in":      # the W taps of the stem become channels while the image is converted
                 ops.image_unfold(xh, ah, sp0.k, sp0.pad, sp0.pad_mode)
             else:
@@ -656,24 +651,18 @@ class NativeNet:
                 ops.act_to_image_backward(gh.contiguous().float(), outh, gah, act=self.out_act)
 
     def _act_grad_to_images(self, gx, xs, need, fold=0, fold_mode="reflect", each=None):
-        """gradient gx of the first activation -> one input gradient per part of xs (a ChannelCat / ChannelSources part: one
-        per image of it that wants one by `need`, the mask over the pass's input tensors, None elsewhere).
+        """gradient gx of the first activation -> one input gradient per part of xs (a ChannelSources part: one
+        per source of it that wants one by `need`, the mask over the pass's input tensors, None elsewhere).
         each(g_in, n0, n1): what else the executor adds to a plain part's gradient, issued right behind its launch"""
         ops, sp0 = self.ops, self.nodes[0].spec
         g_ins, n0, k = [], 0, 0
         for xh in xs:
             n1 = n0 + xh.shape[0]
-            if isinstance(xh, (ChannelSources, ChannelCat)):     # (no padded stem in these forms)
+            if isinstance(xh, ChannelSources):      # (no padded stem in this form)
                 assert fold == 0
                 want = need[k:k + len(xh)] if need is not None else (True,) * len(xh)
                 k += len(xh)
-                if isinstance(xh, ChannelSources):
-                    g_ins.append(xh.write_grads(ops, gx[n0:n1], want))
-                else:
-                    ga, gb = (torch.empty_like(t) if w else None for t, w in zip(xh, want))
-                    if ga is not None or gb is not None:
-                        ops.image_pair_to_act_backward(gx[n0:n1], ga, gb, xh[0].shape[1], xh[1].shape[1])
-                    g_ins.append((ga, gb))
+                g_ins.append(xh.write_grads(ops, gx[n0:n1], want))
             else:
                 g_in = torch.empty_like(xh)
                 if sp0.wfold == "in":
@@ -1052,26 +1041,12 @@ class NativeNet:
         return 1.0 / dist.get_world_size(self._dist)
 
 
-def pairs_shape(pairs):
-    return tuple(ChannelCat(p) for p in pairs)
-
-
 def _split_parts(out, parts):
     outs, n0 = [], 0
     for t in parts:
         outs.append(out[n0:n0 + t.shape[0]])
         n0 += t.shape[0]
     return tuple(outs)
-
-
-class ChannelCat(tuple):
-    """(a, b): two image batches that enter a network side by side along the channel axis — torch.cat([a, b], dim=1) without
-    the launch (NativeNet.forward_parts_cat); looks like the concatenated tensor where the executor asks for a shape"""
-
-    @property
-    def shape(self):
-        a, b = self
-        return torch.Size((a.shape[0], a.shape[1] + b.shape[1]) + tuple(a.shape[2:]))
 
 
 class ChannelSources(tuple):
@@ -1103,7 +1078,7 @@ def _sources(layout, tensors):
 # ---- a recorded pass as ONE autograd node ---------------------------------------------------------------------------------
 class PassForm:
     """What tells one input form of a pass from another. The node below sees the tensors of a pass as flat arguments:
-      pack(tensors) -> what `_forward` takes (a tensor, a tuple of batches / ChannelCat / ChannelSources, a twin pass's pair),
+      pack(tensors) -> what `_forward` takes (a tensor, a tuple of batches / ChannelSources, a twin pass's pair),
       flat(gx)      -> what `_backward` returned, laid back onto those arguments, one entry per tensor,
       parts         -> the batches the output is split along (None: the pass returns its one output whole),
       tw            -> the second network of a twin pass;  remember: the pass is one `recorded_pass` may hand out,

@@ -375,18 +375,13 @@ int gs_repeat_backward(const void* g, int32_t g_cs, int32_t g_co, float* g_img, 
 /* x NCHW fp32 [N,C,H,W] -> act [N,H,W,Cp]  (set_input, cyclegan.py:84-90) */
 int gs_image_to_act(const float* img, void* act, int32_t N, int32_t C, int32_t H, int32_t W, int32_t Cp,
                     void* stream);
-/* torch.cat([a, b], dim=1) -> act in one pass (the conditional discriminator's input, pix2pix.py:70,80), and its gradient into
- * the two images' own gradient tensors (ga / gb may be NULL: that image needs none) */
-int gs_image_pair_to_act(const float* a, int32_t Ca, const float* b, int32_t Cb, void* act, int32_t N, int32_t H, int32_t W,
-                         int32_t Cp, void* stream);
-int gs_image_pair_to_act_backward(const void* g, float* ga, int32_t Ca, float* gb, int32_t Cb, int32_t N, int32_t H, int32_t W,
-                                  int32_t Cp, void* stream);
 /* Channel sources: K (1..GS_CAT_MAX_SRCS) image tensors side by side along the channel axis -> act in one pass. Source k is a
  * channel window of a dense fp32 [N][C_k][S] tensor (S = D*H*W): src[k] points at the window's first element (c0 * S floats
  * into the tensor), sample_stride[k] = C_k * S floats lead from one sample to the next, channels[k] is the window's width.
  * src, sample_stride and channels are HOST arrays of K that reach the kernel by value; no source needs any alignment. Rounding
  * and the zeroed pad lanes are gs_image_to_act's. One windowed source is a discriminator's real input real_B[:, tB], two are
- * the splice torch.cat([fake_Bt, real_A[:, guide]], dim=1) of the balanced CycleGAN. */
+ * the splice torch.cat([fake_Bt, real_A[:, guide]], dim=1) of the balanced CycleGAN, two whole tensors the conditional
+ * discriminator's input torch.cat([real_A, fake_B], dim=1) (pix2pix.py:70,80). */
 #define GS_CAT_MAX_SRCS 4
 int gs_image_cat_to_act(const float* const* src, const int64_t* sample_stride, const int32_t* channels, int32_t K, void* act,
                         int32_t N, int64_t S, int32_t Cp, void* stream);

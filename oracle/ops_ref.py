@@ -506,15 +506,15 @@ class RefOps(TwinSplit):
         act_t.zero_()
         act_t[..., :Cc] = img.movedim(1, -1).to(act_t.dtype)
 
-    def image_pair_to_act(self, a, b, act_t):
-        self.image_to_act(torch.cat([a, b], dim=1), act_t)
+    def image_cat_to_act(self, srcs, act_t):
+        self.image_to_act(torch.cat([t[:, c0:c1] for t, c0, c1 in srcs], dim=1), act_t)
 
-    def image_pair_to_act_backward(self, g, ga, gb, Ca, Cb):
-        gi = g.float().movedim(-1, 1)
-        if ga is not None:
-            ga.copy_(gi[:, :Ca])
-        if gb is not None:
-            gb.copy_(gi[:, Ca:Ca + Cb])
+    def image_cat_to_act_backward(self, g, grads, channels):
+        gi, off = g.float().movedim(-1, 1), 0
+        for gk, ch in zip(grads, channels):
+            if gk is not None:
+                gk.copy_(gi[:, off:off + ch])
+            off += ch
 
     def act_to_image(self, act_t, img, act="none"):
         Cc = img.shape[1]

@@ -20,17 +20,7 @@ CONFIGS = Path(__file__).parent / "configs"
 
 
 class BalancedRefOps(RefOps):
-    """RefOps plus the channel-window methods of HipOps"""
-
-    def image_cat_to_act(self, srcs, act_t):
-        self.image_to_act(torch.cat([t[:, c0:c1] for t, c0, c1 in srcs], dim=1), act_t)
-
-    def image_cat_to_act_backward(self, g, grads, channels):
-        gi, off = g.float().movedim(-1, 1), 0
-        for gk, ch in zip(grads, channels):
-            if gk is not None:
-                gk.copy_(gi[:, off:off + ch])
-            off += ch
+    """RefOps plus the channel-window methods of HipOps that only this recipe calls"""
 
     def channel_embed(self, src, dst, c0):
         dst.zero_()

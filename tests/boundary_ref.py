@@ -680,11 +680,11 @@ def _build_pair(c, data):
 def _run_pair(ops, b, dev):
     c, to = b.case, _to(dev)
     o, wh = _bufs(b, dev, ["act", "ga", "gb", "ga_only", "gb_only"])
-    ops.image_pair_to_act(to(b.a), to(b.b), o["act"])
+    ops.image_cat_to_act([(to(b.a), 0, c.Ca), (to(b.b), 0, c.Cb)], o["act"])
     g = to(b.g)
-    ops.image_pair_to_act_backward(g, o["ga"], o["gb"], c.Ca, c.Cb)
-    ops.image_pair_to_act_backward(g, o["ga_only"], None, c.Ca, c.Cb)
-    ops.image_pair_to_act_backward(g, None, o["gb_only"], c.Ca, c.Cb)
+    ops.image_cat_to_act_backward(g, [o["ga"], o["gb"]], [c.Ca, c.Cb])
+    ops.image_cat_to_act_backward(g, [o["ga_only"], None], [c.Ca, c.Cb])
+    ops.image_cat_to_act_backward(g, [None, o["gb_only"]], [c.Ca, c.Cb])
     return _finish(o, wh)
 
 
@@ -906,33 +906,36 @@ def run(ops, b, dev="cpu"):
     return OPS[b.case.op][1](ops, b, dev)
 
 
-# ---- refusals: each raises the library's error before any launch ----------------------------------------------------------
+# ---- refusals: each raises before any launch ------------------------------------------------------------------------------
 def refusals(ops, dev):
-    """[(what, call)]; the tensors are real and large enough for what is asked, so that nothing but the check decides"""
+    """[(what, call, who)]; the tensors are real and large enough for what is asked, so that nothing but the check decides.
+    who = "library": the entry point's own error (rc = 2); "wrapper": HipOps' ValueError, raised before the library is asked
+    (the library's rc = 2 for the same condition: tests/test_boundary_edges_cpu.py)"""
     f32 = lambda *s: torch.zeros(*s, device=dev)
     bf = lambda *s: torch.zeros(*s, dtype=BF16, device=dev)
     ids = lambda n: torch.zeros(n, dtype=torch.int64, device=dev)
     return [
         ("replicate fold 4 (gs_image_to_act_backward)",
-         lambda: ops.image_to_act_backward(bf(1, 13, 13, 8), f32(1, 1, 5, 5), fold=4, fold_mode="replicate")),
+         lambda: ops.image_to_act_backward(bf(1, 13, 13, 8), f32(1, 1, 5, 5), fold=4, fold_mode="replicate"), "library"),
         ("replicate fold 4 (gs_image_unfold_backward)",
-         lambda: ops.image_unfold_backward(bf(1, 13, 15, 8), f32(1, 1, 5, 15), KW, PW, 4, "replicate")),
-        ("Qp < k C", lambda: ops.image_unfold(f32(1, 2, 2, 15), bf(1, 2, 15, 8), KW, PW, "reflect")),
-        ("Qp < k C (backward)", lambda: ops.image_unfold_backward(bf(1, 2, 15, 8), f32(1, 2, 2, 15), KW, PW, 0, "reflect")),
-        ("Qp no multiple of 8", lambda: ops.image_unfold(f32(1, 1, 2, 15), bf(1, 2, 15, 12), KW, PW, "reflect")),
-        ("pair with Cp < Ca + Cb", lambda: ops.image_pair_to_act(f32(1, 3, 2, 2), f32(1, 6, 2, 2), bf(1, 2, 2, 8))),
-        ("P = 16385", lambda: ops.image_tap_scatter(f32(1, 16385, 1), ids(16385), (1, 1, 4, 4), 0)),
+         lambda: ops.image_unfold_backward(bf(1, 13, 15, 8), f32(1, 1, 5, 15), KW, PW, 4, "replicate"), "library"),
+        ("Qp < k C", lambda: ops.image_unfold(f32(1, 2, 2, 15), bf(1, 2, 15, 8), KW, PW, "reflect"), "library"),
+        ("Qp < k C (backward)", lambda: ops.image_unfold_backward(bf(1, 2, 15, 8), f32(1, 2, 2, 15), KW, PW, 0, "reflect"), "library"),
+        ("Qp no multiple of 8", lambda: ops.image_unfold(f32(1, 1, 2, 15), bf(1, 2, 15, 12), KW, PW, "reflect"), "library"),
+        ("pair with Cp < Ca + Cb",
+         lambda: ops.image_cat_to_act([(f32(1, 3, 2, 2), 0, 3), (f32(1, 6, 2, 2), 0, 6)], bf(1, 2, 2, 8)), "wrapper"),
+        ("P = 16385", lambda: ops.image_tap_scatter(f32(1, 16385, 1), ids(16385), (1, 1, 4, 4), 0), "library"),
         ("reflect fold 3 with H = 3 (gs_image_to_act_backward)",
-         lambda: ops.image_to_act_backward(bf(1, 9, 11, 8), f32(1, 1, 3, 5), fold=3, fold_mode="reflect")),
+         lambda: ops.image_to_act_backward(bf(1, 9, 11, 8), f32(1, 1, 3, 5), fold=3, fold_mode="reflect"), "library"),
         ("reflect fold 2 with W = 2 (gs_image_to_act_backward)",
-         lambda: ops.image_to_act_backward(bf(1, 9, 6, 8), f32(1, 1, 5, 2), fold=2, fold_mode="reflect")),
+         lambda: ops.image_to_act_backward(bf(1, 9, 6, 8), f32(1, 1, 5, 2), fold=2, fold_mode="reflect"), "library"),
         ("reflect fold 2 with D = 2 (gs_image_to_act_backward)",
-         lambda: ops.image_to_act_backward(bf(1, 6, 9, 9, 8), f32(1, 1, 2, 5, 5), fold=2, fold_mode="reflect")),
-        ("reflect unfold with W = 3 = p", lambda: ops.image_unfold(f32(1, 1, 2, 3), bf(1, 2, 3, 8), KW, PW, "reflect")),
+         lambda: ops.image_to_act_backward(bf(1, 6, 9, 9, 8), f32(1, 1, 2, 5, 5), fold=2, fold_mode="reflect"), "library"),
+        ("reflect unfold with W = 3 = p", lambda: ops.image_unfold(f32(1, 1, 2, 3), bf(1, 2, 3, 8), KW, PW, "reflect"), "library"),
         ("reflect unfold backward with W = 3 = p",
-         lambda: ops.image_unfold_backward(bf(1, 2, 3, 8), f32(1, 1, 2, 3), KW, PW, 0, "reflect")),
+         lambda: ops.image_unfold_backward(bf(1, 2, 3, 8), f32(1, 1, 2, 3), KW, PW, 0, "reflect"), "library"),
         ("reflect unfold backward with H = fold",
-         lambda: ops.image_unfold_backward(bf(1, 6, 15, 8), f32(1, 1, 2, 15), KW, PW, 2, "reflect")),
+         lambda: ops.image_unfold_backward(bf(1, 6, 15, 8), f32(1, 1, 2, 15), KW, PW, 2, "reflect"), "library"),
         ("reflect unfold backward with D = fold",
-         lambda: ops.image_unfold_backward(bf(1, 6, 9, 15, 8), f32(1, 1, 2, 5, 15), KW, PW, 2, "reflect")),
+         lambda: ops.image_unfold_backward(bf(1, 6, 9, 15, 8), f32(1, 1, 2, 5, 15), KW, PW, 2, "reflect"), "library"),
     ]

@@ -140,7 +140,8 @@ def test_refusals_come_before_any_launch():
         lib.gs_image_unfold_backward(p, p, 1, 1, 1, 5, 15, 8, 7, 3, 4, L.BORDER["replicate"], 0, None),
         lib.gs_image_unfold(p, p, 1, 2, 2, 15, 8, 7, 3, L.BORDER["reflect"], None),
         lib.gs_image_unfold(p, p, 1, 1, 2, 15, 12, 7, 3, L.BORDER["reflect"], None),
-        lib.gs_image_pair_to_act(p, 3, p, 6, p, 1, 2, 2, 8, None),
+        lib.gs_image_cat_to_act((ctypes.c_void_p * 2)(4096, 4096), (ctypes.c_int64 * 2)(3 * 4, 6 * 4), (ctypes.c_int32 * 2)(3, 6), 2,
+                                p, 1, 4, 8, None),                   # 3 + 6 source channels, Cp = 8
         lib.gs_image_tap_scatter(p, 1, 1, 4, 4, 0, p, 16385, p, None),
         lib.gs_image_to_act_backward(p, p, 1, 1, 1, 3, 5, 8, 3, L.BORDER["reflect"], 0, None),
         lib.gs_image_to_act_backward(p, p, 1, 1, 2, 5, 5, 8, 2, L.BORDER["reflect"], 0, None),

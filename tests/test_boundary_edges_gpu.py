@@ -78,10 +78,11 @@ def test_boundary_case(hip_ops, op, name, data):
 
 
 def test_refusals(hip_ops):
-    """each raises the library's error (rc = 2: a refused argument, before any launch)"""
+    """each raises the library's error (rc = 2: a refused argument, before any launch), or the wrapper's ValueError where
+    the wrapper looks at the condition before the library does"""
     from ganslate_amd.hip.lib import HipError
-    for what, call in R.refusals(hip_ops, hip_ops.device):
-        with pytest.raises(HipError, match=r"rc=2"):
+    for what, call, who in R.refusals(hip_ops, hip_ops.device):
+        with pytest.raises(HipError, match=r"rc=2") if who == "library" else pytest.raises(ValueError, match="do not fit"):
             call()
         print(f"BOUNDARY_REFUSED {what}")
     torch.cuda.synchronize()

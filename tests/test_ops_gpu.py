@@ -1533,8 +1533,8 @@ def test_fused_adam_plan_follows_the_options(hip_ops):
 
 @pytest.mark.parametrize("shape", [(2, 3, 3, 16, 24), (1, 1, 4, 9, 7)], ids=lambda s: "x".join(map(str, s)))
 def test_image_pair_conversion(hip_ops, shape):
-    """gs_image_pair_to_act / _backward (torch.cat([a, b], dim=1) -> NHWC bf16 in one pass; the gradient into the two images' own
-    tensors, either optional) against cat + gs_image_to_act and its backward, bit for bit"""
+    """gs_image_cat_to_act / _backward on two whole tensors (torch.cat([a, b], dim=1) -> NHWC bf16 in one pass; the gradient into
+    the two images' own tensors, either optional) against cat + gs_image_to_act and its backward, bit for bit"""
     N, Ca, Cb, H, W = shape
     g = torch.Generator().manual_seed(91)
     dev = hip_ops.device
@@ -1542,7 +1542,7 @@ def test_image_pair_conversion(hip_ops, shape):
     Cp = (Ca + Cb + 7) // 8 * 8
     act1 = torch.full((N, H, W, Cp), 3.0, dtype=torch.bfloat16, device=dev)
     act2 = torch.full((N, H, W, Cp), 5.0, dtype=torch.bfloat16, device=dev)
-    hip_ops.image_pair_to_act(a, b, act1)
+    hip_ops.image_cat_to_act([(a, 0, Ca), (b, 0, Cb)], act1)
     hip_ops.image_to_act(torch.cat([a, b], dim=1), act2)
     assert torch.equal(act1, act2)
     gact = torch.randn(N, H, W, Cp, generator=g).to(torch.bfloat16).to(dev)
@@ -1551,7 +1551,7 @@ def test_image_pair_conversion(hip_ops, shape):
     for need in ((True, True), (False, True), (True, False)):
         ga = torch.full((N, Ca, H, W), 7.0, device=dev) if need[0] else None
         gb = torch.full((N, Cb, H, W), 7.0, device=dev) if need[1] else None
-        hip_ops.image_pair_to_act_backward(gact, ga, gb, Ca, Cb)
+        hip_ops.image_cat_to_act_backward(gact, [ga, gb], [Ca, Cb])
         if ga is not None:
             assert torch.equal(ga, want[:, :Ca])
         if gb is not None:

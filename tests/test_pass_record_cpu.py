@@ -10,12 +10,12 @@ import torch
 from ganslate_amd.nn.native import backend
 from ganslate_amd.nn.native.twin import TwinNet
 
-from .balanced_ref import BalancedRefOps
+from oracle.ops_ref import RefOps
 
 
 @pytest.fixture()
 def fp32_oracle_backend():
-    backend.set_ops(BalancedRefOps(act_dtype=torch.float32))      # (RefOps + the channel-window ops of forward_sources)
+    backend.set_ops(RefOps(act_dtype=torch.float32))
     yield
     backend.set_ops(None)
 
@@ -108,6 +108,43 @@ def test_channel_pair_pass_interleaved_with_a_plain_pass(fp32_oracle_backend):
     cat = lambda n: c.loss("cat", *n[0].forward_parts_cat([(c.leaf(0), c.leaf(1, grad=False))]))
     plain = lambda n: c.loss("plain", n[0](c.leaf(2)))
     run_pair([net], [ref], c, cat, plain)
+
+
+def test_pix2pix_concatenates_for_a_discriminator_without_channel_sources(fp32_oracle_backend):
+    """A discriminator whose images do not enter through the plain image conversion (a W-folded k7 stem:
+    supports_channel_sources() is False) has forward_parts_cat like every NativeNet, and refuses it. The recipe's two D calls
+    hand it torch.cat([real_A, fake_B], dim=1) instead: predictions, losses and parameter gradients are those of an identical
+    copy fed the concatenated tensors, bit for bit, and fake_B's gradient reaches the generator."""
+    from ganslate_amd.nn.generators import Resnet2D
+    from .helpers import build_product_pix2pix
+    c = dict(size=[32, 32], batch=1, n_iters=100, n_iters_decay=100, num_downs=5, ngf=8, use_dropout=False, n_layers=2,
+             lambda_pix2pix=30.0, seed=27)
+    model = build_product_pix2pix(c)
+    # one-channel images: the two-channel pair is few enough channels for the stem's W taps to be folded into them
+    model.networks["G"] = fresh(lambda: Resnet2D(1, 1, "instance", 1), 28)[0]
+    D, ref = fresh(lambda: Resnet2D(2, 1, "instance", 1), 29)
+    model.networks["D"] = D
+    A, B = (torch.rand(1, 1, 32, 32, generator=torch.Generator().manual_seed(30 + k)) * 2 - 1 for k in range(2))
+    assert D.nodes[0].spec.wfold == "in" and not D.supports_channel_sources()
+    with pytest.raises(NotImplementedError):
+        D.forward_parts_cat([(A, B)])
+    model.set_input({"A": A, "B": B})
+    model.forward()
+    fake_B = model.visuals["fake_B"].detach()
+    model.set_requires_grad(D, False)
+    model.backward_G()
+    with torch.no_grad():
+        assert float(model.losses["G"]) == float(model.criterion_adv(ref(torch.cat([A, fake_B], dim=1)), target_is_real=True))
+    model.networks["G"].flush_deferred_wgrads()
+    assert bool(model.networks["G"].master.grad.any()) and (D.master.grad is None or not bool(D.master.grad.any()))
+    model.set_requires_grad(D, True)
+    model.backward_D()
+    want_real, want_fake = ref.forward_parts((torch.cat([A, B], dim=1), torch.cat([A, fake_B], dim=1)))
+    assert torch.equal(model.pred_real, want_real) and torch.equal(model.pred_fake, want_fake)
+    (model.criterion_adv(want_real, target_is_real=True) + model.criterion_adv(want_fake, target_is_real=False)).backward()
+    D.flush_deferred_wgrads()
+    ref.flush_deferred_wgrads()
+    assert bool(D.master.grad.any()) and torch.equal(D.master.grad, ref.master.grad)
 
 
 @pytest.mark.parametrize("arch", ["native", "unet2d"])
